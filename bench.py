@@ -16,10 +16,15 @@ With --gpus N > 1 the same total problem is split over the ranks (strong scaling
 process then only SUPERVISES a child that does the work (it never touches the GPU): a first-contact preflight that hangs on the
 2-D layout is retried once on the 1-D layout instead of ending the run (supervise()).
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (the fp64 MFMA GEMM behind SYRK/TRSM; HIP
-events recorded on the launch stream by the library around every launch inside the timed region) and
-"cpu_baseline" (the oracle's reference-exact algorithm -- row-loop assembly + pinv + slogdet + per-point variance
-loop -- timed on the host cores on a bounded sample of the same workload, rank 0 at N=1 only).
+A plain run sets up, warms up, times --steps steps and prints the line; "roofline" there is the whole-step figure (algorithmic
+flops over the wall time of the timed region).  Everything that takes runs of its own comes with --full: the per-launch roofline
+figures (HIP events recorded on the launch stream by the library around every launch, in an identical instrumented repeat of
+the timed steps), fit and IVAR timed separately, the isolated assembly launches, "multi_gpu_replay" and "cpu_baseline" (the
+oracle's reference-exact algorithm -- row-loop assembly + pinv + slogdet + per-point variance loop -- timed on the host cores on
+a bounded sample of the same workload, rank 0 at N=1 only).
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -50,6 +55,13 @@ def hdot(a, b):
     """sum a_i b_i without BLAS (gpexp_amd._lib.hdot: np.dot wakes OpenBLAS' 64 threads, whose spinning stalls the next step's kernel
     launches in a CPU-quota'd container)."""
     return float(np.sum(np.multiply(a, b)))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float64 .npy per name in `path`."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def workload(n, d, m, seed):
@@ -274,6 +286,8 @@ def bench_c5(args, ctx, dev, world, rank, stdout_fd):
     barrier()
     dt = reduce_max(time.perf_counter() - t0)
     watchdog.cancel()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loglike": ll, "grad": grad, "mi_picks": picks})
     if rank == 0:
         fit_flops = float(N) ** 3 / 3.0
         grad_flops = 2.0 * float(N) ** 3 / 3.0
@@ -530,7 +544,14 @@ def main():
     ap.add_argument("--no-replay", action="store_true", help="skip the multi_gpu_replay object (rank 0 of a 2x4 grid replayed on this GPU)")
     ap.add_argument("--cpu-baseline", choices=["bounded", "full"], default="bounded",
                     help="full: SURVEY.md 8d's whole protocol (adds N=8192 and the fair-CPU Cholesky at N=32768; minutes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: instrumented repeat (per-launch roofline, phases), fit and "
+                         "IVAR separately, isolated assembly launches, multi_gpu_replay, cpu_baseline (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if (int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("GPX_BENCH_CHILD") != "1"
             and os.environ.get("GPX_BENCH_SUPERVISE", "1") == "1"):
@@ -564,6 +585,7 @@ def main():
     Xh, yh, Zh, noise = workload(N, d, M, seed=N)
     spec = dev.KernelSpec(dev.K_MATERN52 if args.kernel == "matern52" else dev.K_MATERN32, d, [0.5, 1.0])
     preflight = None
+    last = {}      # arrays of the last step beyond its (loglike, ivar), for --dump-outputs
 
     if world > 1 or os.environ.get("GPX_FORCE_DIST") == "1":  # GPX_FORCE_DIST: rehearse the RCCL runner on one GPU
         from gpexp_amd import dist
@@ -652,6 +674,7 @@ def main():
             ctx.sync()
             alpha = alpha_dev.to_host()[:N, 0]
             ll = -0.5 * hdot(yh, alpha) - 0.5 * logdet - N / 2.0 * np.log(2 * np.pi)   # (no BLAS: _lib.hdot)
+            last.update(alpha=alpha, logdet=logdet)
             return ll, iv
 
         def barrier():
@@ -697,34 +720,37 @@ def main():
     dt = time.perf_counter() - t0
     dt = reduce_max(dt)
     ll, iv = out
-    # ... they are recorded in an identical repeat right behind it (same steps, same inputs, same results): per-class spans,
-    # launch counts and algorithmic flops for the roofline object and the rocprofv3 cross-check
-    progress["at"] = "the instrumented repeat"
-    if world > 1 or os.environ.get("GPX_FORCE_DIST") == "1":
-        runner.force_interpret = True     # profiler events cannot live inside a captured graph: issue this repeat row by row
-    ctx.profile(True)
-    ctx.profile_reset()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out2 = step()
-    sync()
-    barrier()
-    dt_instr = reduce_max(time.perf_counter() - t0)
-    prof = ctx.profile_get()
-    ctx.profile(False)
-    if world == 1:
-        assert out2 == out, "the instrumented repeat must reproduce the timed steps bit for bit"
-    else:
-        # several ranks: the sums inside ncclReduce / ncclAllReduce are not promised to associate the same way twice; a
-        # mismatch beyond round-off is still an error, but it must not kill a timing run over the last bit
-        assert all(abs(a - b) <= 1e-12 * abs(b) for a, b in zip(out2, out)), (out2, out)
-    phases = {k: v["ms"] / args.steps for k, v in prof.items() if v["launches"]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, loglike=ll, ivar=iv))
+    if args.full:
+        # ... they are recorded in an identical repeat right behind it (same steps, same inputs, same results): per-class spans,
+        # launch counts and algorithmic flops for the roofline object and the rocprofv3 cross-check
+        progress["at"] = "the instrumented repeat"
+        if world > 1 or os.environ.get("GPX_FORCE_DIST") == "1":
+            runner.force_interpret = True     # profiler events cannot live inside a captured graph: issue this repeat row by row
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out2 = step()
+        sync()
+        barrier()
+        dt_instr = reduce_max(time.perf_counter() - t0)
+        prof = ctx.profile_get()
+        ctx.profile(False)
+        if world == 1:
+            assert out2 == out, "the instrumented repeat must reproduce the timed steps bit for bit"
+        else:
+            # several ranks: the sums inside ncclReduce / ncclAllReduce are not promised to associate the same way twice; a
+            # mismatch beyond round-off is still an error, but it must not kill a timing run over the last bit
+            assert all(abs(a - b) <= 1e-12 * abs(b) for a, b in zip(out2, out)), (out2, out)
+        phases = {k: v["ms"] / args.steps for k, v in prof.items() if v["launches"]}
     watchdog.cancel()
 
     # GP-fit and IVAR-eval separately (N / t_fit and M / t_IVAR), outside the timed region: inside it the
     # alpha sweeps run underneath the IVAR GEMMs, so the two phases overlap and do not add up to ms_per_step
     fit_ms = ivar_ms = None
-    if world == 1 and os.environ.get("GPX_FORCE_DIST") != "1":
+    if args.full and world == 1 and os.environ.get("GPX_FORCE_DIST") != "1":
         def fit_only():
             dev.kfill_into(ctx, spec, X, K, nugget=noise)
             dev.potrf(ctx, K)
@@ -767,35 +793,14 @@ def main():
 
     if rank == 0:
         ms = 1e3 * dt / args.steps
-        g = prof["gemm"]
-        kf = prof["kfill"]
-        kc = prof["kcross"]
-
-        def hbm(p):
-            gbs = p["bytes"] / (p["ms"] * 1e-3) / 1e9 if p["ms"] > 0 else 0.0
-            return {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
-                    "avg_launch_ms": p["ms"] / p["launches"] if p["launches"] else 0.0,
-                    "algorithmic_bytes_per_launch": p["bytes"] / p["launches"] if p["launches"] else 0.0}
         # The look-ahead factorisation runs GEMMs on three streams at once, so per-class event spans overlap and their sum
         # can exceed the wall time: the roofline divides the class's algorithmic flops by the WALL time of the timed region
         # (which also contains the ~1 % of assembly / reduction kernels) -- overlap cannot inflate it.
         # ALGORITHMIC flops of a step: N^3/3 (factorisation) + N^2 M (evaluation solve), SURVEY.md 8d.  The launched count of
         # the GEMM class (g["flops"]: adds the block-inverse builds and the padding of the triangular products, ~0.6 %) is
-        # reported beside it, never used for `achieved`.
+        # reported beside it (--full), never used for `achieved`.
         algo_flops = float(N) ** 3 / 3.0 + float(N) ** 2 * float(M)
         ach = algo_flops * args.steps / dt / 1e12 if dt > 0 else 0.0
-        traffic, traffic_src = None, None
-        try:  # PMC counters cannot be read from inside the process: take the committed rocprofv3 --pmc passes of this
-            # same command (profiles/), per launch like `achieved`; null when the profile is for another config
-            pmc = [f for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json")
-                   if os.path.exists(os.path.join(ROOT, "profiles", f))][0]
-            with open(os.path.join(ROOT, "profiles", pmc)) as f:
-                pj = json.load(f)
-            if world == 1 and (N, d, M) == (32768, 8, 32768) and args.kernel == "matern52":
-                traffic = (pj["fetch_bytes_per_step_corrected"] + pj["write_bytes_per_step"]) / pj["launches_per_step"]
-                traffic_src = pj["source"]
-        except (OSError, KeyError, ValueError):
-            pass
         line = {
             "metric": "GP-fit+IVAR-eval points/s at N=%d d=%d (wall-time in ms_per_step); value = (N+M)/t_step, SURVEY 8d's "
                       "N/t_fit and M/t_IVAR are points_per_s_fit / points_per_s_ivar right behind it" % (N, d),
@@ -819,43 +824,71 @@ def main():
                        "parallelism": layout if world == 1 else "%d ranks, %s" % (world, layout)},
             "roofline": {"bound": "mfma", "kernel": "gemm_f64_kernel (SYRK/TRSM updates)", "achieved": ach,
                          "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP64_MFMA_TFLOPS,
-                         "traffic": traffic, "traffic_unit": "bytes per launch (mean over the step's launches)",
-                         "traffic_source": traffic_src,
-                         "traffic_source_run": "builder" if traffic is not None else None,
                          "algorithmic_flop_per_step": algo_flops,
-                         "algorithmic_flop_per_launch": (algo_flops * args.steps / g["launches"]) if g["launches"] else 0.0,
-                         "launched_flop_per_step": g["flops"] / args.steps,
-                         "avg_launch_ms": (g["ms"] / g["launches"]) if g["launches"] else 0.0,
-                         "launches_per_step": g["launches"] / args.steps,
-                         "event_ms_per_step_summed_over_streams": g["ms"] / args.steps,
-                         "ms_per_step_instrumented": 1e3 * dt_instr / args.steps,
-                         "note": "achieved = algorithmic flops (N^3/3 + N^2 M) / wall time of the timed region (no profiler events inside it); the "
-                                 "per-launch figures are HIP-event spans from an identical instrumented repeat of the same "
-                                 "steps (bit-identical results, asserted); their sum counts time on concurrent streams twice "
-                                 "(look-ahead) and is reported for the rocprofv3 cross-check only"},
-            "roofline_kfill": dict(hbm(kf), kernel="kfill_kernel<SYM> (symmetric N x N assembly, mirror-written)",
-                                   traffic=None),
-            "roofline_kcross": dict(hbm(kc), kernel="kfill_rectn_kernel (rectangular N x M cross matrix, every element "
-                                                   "computed)", traffic=None),
-            "phase_note": "fit_ms (kfill + potrf + potrs + logdet) and ivar_ms are timed separately after the timed region "
-                          "(inside it the alpha sweeps run underneath the IVAR GEMMs); roofline_kfill / roofline_kcross are "
-                          "one isolated launch each between two host syncs, host clock, median of 5 (kernel duration + "
-                          "~0.03 ms)",
-            "phases_ms_per_step": phases,
-            "phases_note": "HIP-event spans per kernel class in the instrumented repeat; trsv and reduce run on a side stream UNDERNEATH the IVAR GEMMs, "
-                           "so their spans include waiting and the classes do not add up to ms_per_step",
+                         "note": "achieved = algorithmic flops (N^3/3 + N^2 M) / wall time of the timed region (no profiler "
+                                 "events inside it)"},
             "results": {"loglike": ll, "ivar": iv},
             "device": info["name"],
         }
+        if args.full:
+            g = prof["gemm"]
+            kf = prof["kfill"]
+            kc = prof["kcross"]
+
+            def hbm(p):
+                gbs = p["bytes"] / (p["ms"] * 1e-3) / 1e9 if p["ms"] > 0 else 0.0
+                return {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
+                        "avg_launch_ms": p["ms"] / p["launches"] if p["launches"] else 0.0,
+                        "algorithmic_bytes_per_launch": p["bytes"] / p["launches"] if p["launches"] else 0.0}
+            traffic, traffic_src = None, None
+            try:  # PMC counters cannot be read from inside the process: take the committed rocprofv3 --pmc passes of this
+                # same command (profiles/), per launch like `achieved`; null when the profile is for another config
+                pmc = [f for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json",
+                                   "r02_pmc_traffic.json", "r01_pmc_traffic.json")
+                       if os.path.exists(os.path.join(ROOT, "profiles", f))][0]
+                with open(os.path.join(ROOT, "profiles", pmc)) as f:
+                    pj = json.load(f)
+                if world == 1 and (N, d, M) == (32768, 8, 32768) and args.kernel == "matern52":
+                    traffic = (pj["fetch_bytes_per_step_corrected"] + pj["write_bytes_per_step"]) / pj["launches_per_step"]
+                    traffic_src = pj["source"]
+            except (OSError, KeyError, ValueError):
+                pass
+            line["roofline"].update({
+                "traffic": traffic, "traffic_unit": "bytes per launch (mean over the step's launches)",
+                "traffic_source": traffic_src,
+                "traffic_source_run": "builder" if traffic is not None else None,
+                "algorithmic_flop_per_launch": (algo_flops * args.steps / g["launches"]) if g["launches"] else 0.0,
+                "launched_flop_per_step": g["flops"] / args.steps,
+                "avg_launch_ms": (g["ms"] / g["launches"]) if g["launches"] else 0.0,
+                "launches_per_step": g["launches"] / args.steps,
+                "event_ms_per_step_summed_over_streams": g["ms"] / args.steps,
+                "ms_per_step_instrumented": 1e3 * dt_instr / args.steps,
+                "note": line["roofline"]["note"] + "; the per-launch figures are HIP-event spans from an identical instrumented "
+                        "repeat of the same steps (bit-identical results, asserted); their sum counts time on concurrent streams "
+                        "twice (look-ahead) and is reported for the rocprofv3 cross-check only"})
+            line.update({
+                "roofline_kfill": dict(hbm(kf), kernel="kfill_kernel<SYM> (symmetric N x N assembly, mirror-written)",
+                                       traffic=None),
+                "roofline_kcross": dict(hbm(kc), kernel="kfill_rectn_kernel (rectangular N x M cross matrix, every element "
+                                                       "computed)", traffic=None),
+                "phase_note": "fit_ms (kfill + potrf + potrs + logdet) and ivar_ms are timed separately after the timed region "
+                              "(inside it the alpha sweeps run underneath the IVAR GEMMs); roofline_kfill / roofline_kcross are "
+                              "one isolated launch each between two host syncs, host clock, median of 5 (kernel duration + "
+                              "~0.03 ms)",
+                "phases_ms_per_step": phases,
+                "phases_note": "HIP-event spans per kernel class in the instrumented repeat; trsv and reduce run on a side stream "
+                               "UNDERNEATH the IVAR GEMMs, so their spans include waiting and the classes do not add up to "
+                               "ms_per_step"})
         if preflight is not None:
             line["preflight"] = preflight
         if world > 1 or os.environ.get("GPX_FORCE_DIST") == "1":
             line["host_issue_ms_per_step"] = dict(getattr(runner, "host_ms", {}) or {})
+        if args.full and (world > 1 or os.environ.get("GPX_FORCE_DIST") == "1"):
             line["comm_note"] = ("phases_ms_per_step.comm = HIP-event spans around the collectives on the communication stream "
                                  "(includes waiting for the peers); gemm / leaf = the compute strands")
-        if world == 1 and not args.no_replay and os.environ.get("GPX_FORCE_DIST") != "1" and N >= 8192:
+        if args.full and world == 1 and not args.no_replay and os.environ.get("GPX_FORCE_DIST") != "1" and N >= 8192:
             line["multi_gpu_replay"] = multi_gpu_replay(ctx, dev, spec, Xh, yh, Zh, noise, K, X, fit_ms, ms)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(d, full=(args.cpu_baseline == "full"), kind=args.kernel)
             ref = os.path.join(ROOT, "profiles", "r02_bench_n1_cpu_full.json")
             if os.path.exists(ref):   # the WHOLE SURVEY 8d protocol takes ~5 minutes of CPU: a builder-run record, quoted here

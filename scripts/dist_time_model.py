@@ -1,6 +1,6 @@
 """Node PROJECTION of the 2-D block-cyclic fit from the paced replay, round 4.  MEASURED (on one MI355X): the chain
 across ranks and every rank's kernels, with each receive standing in as a device copy of the same bytes
-(bench.py `multi_gpu_replay`, or a `scripts/dist_replay.py --paced-grid` line).  MODELLED (RCCL with more than one rank has never
+(`bench.py --full`'s `multi_gpu_replay`, or a `scripts/dist_replay.py --paced-grid` line).  MODELLED (RCCL with more than one rank has never
 run on the build's hardware -- one GPU per lease): what xGMI adds.  The two are kept apart in the output.
 
     python scripts/dist_time_model.py [profiles/r04_bench_n1.json]

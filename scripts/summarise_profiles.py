@@ -32,7 +32,7 @@ lines = ["# " + tag + " -- HBM-side traffic of one bench step (C4, N=32768, d=8,
 res = {}
 for path, counter, mult in (("pmc_fetch", "FETCH_SIZE", 2.0), ("pmc_write", "WRITE_SIZE", 1.0)):
     agg = pmc(path, counter)
-    lines.append("%s (command: rocprofv3 --kernel-trace --pmc %s -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline)" % (counter, counter))
+    lines.append("%s (command: rocprofv3 --kernel-trace --pmc %s -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline)" % (counter, counter))
     for k, (n, v, ms) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
         b = v * 1024.0 * mult
         lines.append("  %-44s launches=%5d  bytes=%9.3f GB  kernel_ms=%8.2f  -> %.2f TB/s" % (k, n, b / 1e9, ms, b / ms / 1e9 if ms else 0))
@@ -44,7 +44,7 @@ lines.append("MFMA utilisation of the GEMM class over one step (rocprofv3 --pmc 
 lines.append("  SQ_VALU_MFMA_BUSY_CYCLES=%.4e (64 per v_mfma_f64_16x16x4_f64, summed over 1024 SIMDs)  GRBM_GUI_ACTIVE=%.4e (summed over 8 XCDs)  kernel_ms=%.2f" % (busy, gui, ms))
 lines.append("  -> MFMA pipe busy %.1f %% of SIMD cycles (busy / (GUI_ACTIVE/8 * 1024)); clock %.3f GHz (GUI_ACTIVE/8 / kernel time)" % (100.0 * busy / (gui / 8 * 1024), gui / 8 / ms / 1e6))
 open(os.path.join(out, tag + "_pmc_traffic.txt"), "w").write("\n".join(lines) + "\n")
-json.dump({"config": "C4 N=32768 d=8 M=32768: the profiled command = bench.py --steps 1 --warmup 0 = one timed step + the fit-only "
+json.dump({"config": "C4 N=32768 d=8 M=32768: the profiled command = bench.py --full --steps 1 --warmup 0 = one timed step + the fit-only "
                      "and IVAR-only passes (3 step-equivalents); the *_per_step fields are totals over that command, "
                      "bench.py divides bytes by launches (per-launch traffic, like roofline.achieved)",
            "kernel": "gemm class (gemm_f64_kernel variants + leaf_mul kernels)",
