@@ -1,0 +1,372 @@
+// Bayesian-optimisation acquisition costs -- gfx950.
+//
+// Replaces costFuncGPUCbound / costFuncPI / costFuncEI.evaluate (experimentalDesign.py:889-1003), which score ONE point per call
+// (a single-row GP.evaluate(compvar=1) + scipy.stats), by a pass over M candidates: the posterior of every chunk of Z exactly as
+// gpx_posterior forms it (api.hip, posterior_impl: B = K(X, Zc), mean = B^T alpha, W = L^-1 B, var = k(z, z) - colsum(W^2)), then
+// one epilogue that turns (mean, var) into the cost and a per-block (cost, index) partial, and one small kernel that reduces the
+// partials to the FIRST arg-min among the non-NaN costs.  With mu the mean, s = sqrt(|var|) (GP.evaluate's abs, gp.py:145),
+// g = (fBest - mu) / s, Phi = 0.5 erfc(-g / sqrt 2), phi the normal density:
+//     UCB  A = -(mu - kappa s)       PI  A = -Phi(g)       EI  A = -s (g Phi(g) + phi(g))
+//
+// Gradient w.r.t. the candidate (gpx_acq_grad).  With a = dA/dmu, b = dA/dvar (from the epilogue of the same chunk):
+//     UCB  a = -1          b = kappa sgn(var) / (2 s)
+//     PI   a = phi / s     b = phi g sgn(var) / (2 s^2)
+//     EI   a = Phi         b = -phi sgn(var) / (2 s)
+// and, k(z, z) being constant for the stationary kernels,
+//     grad_z A = sum_j dk(z, x_j)/dz (a alpha_j - 2 b beta_j),   beta = K^-1 K(X, z) = L^-T W.
+// The backward solve reuses the forward solve W of the values; the sum over j is one fused pass over the training points per
+// candidate (acq_grad_kernel).  These are the TRUE derivatives of the values returned (not the reference's SE `derivative`, which
+// multiplies by signalSize twice, kernels.py:177):
+//     SE        dk/dz_l = -(z_l - x_l) / cl_l^2 k
+//     Matern32  dk/dz   = -sig (3 / rho^2) e^-t (z - x)             t = sqrt(3) |z - x| / rho
+//     Matern52  dk/dz   = -sig (5 / (3 rho^2)) (1 + t) e^-t (z - x)  t = sqrt(5) |z - x| / rho
+// all smooth at z = x.  Where var == 0 exactly, a and b are NaN, and so is the gradient row.
+#include "gpx_internal.h"
+#include <math.h>
+
+namespace {
+
+constexpr int ACQ_EPI = 128;   // candidates per epilogue block = one arg-min partial; chunk starts are multiples of it
+
+struct ArgMin {
+  double c;
+  int64_t i;   // -1: no non-NaN cost seen
+};
+
+// first minimum: the smaller cost, on a tie the smaller index; NaN costs never enter.  Associative and commutative, so the
+// winner does not depend on the reduction tree or on the chunking.
+__device__ __forceinline__ ArgMin argmin_merge(ArgMin a, ArgMin b) {
+  if (a.i < 0) return b;
+  if (b.i < 0) return a;
+  return (b.c < a.c || (b.c == a.c && b.i < a.i)) ? b : a;
+}
+
+__device__ __forceinline__ ArgMin argmin_block(ArgMin v, double* sc, int64_t* si) {
+  const int t = threadIdx.x;
+  sc[t] = v.c;
+  si[t] = v.i;
+  __syncthreads();
+  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+    if (t < w) {
+      const ArgMin o = argmin_merge(ArgMin{sc[t], si[t]}, ArgMin{sc[t + w], si[t + w]});
+      sc[t] = o.c;
+      si[t] = o.i;
+    }
+    __syncthreads();
+  }
+  return ArgMin{sc[0], si[0]};
+}
+
+// values epilogue of one chunk [j0, j0 + mc): var = kd - ssq, the cost (written to cost[j0 + j]), the gradient coefficients
+// (a, b) per candidate of the chunk (coef, nullable) and one arg-min partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].
+__global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double param, const double* __restrict__ mean,
+                                                               const double* __restrict__ kd, const double* __restrict__ ssq,
+                                                               int64_t mc, int64_t j0, double* __restrict__ cost,
+                                                               double* __restrict__ coef, double* __restrict__ part_c,
+                                                               int64_t* __restrict__ part_i) {
+  __shared__ double sc[ACQ_EPI];
+  __shared__ int64_t si[ACQ_EPI];
+  const int64_t j = (int64_t)blockIdx.x * ACQ_EPI + threadIdx.x;
+  ArgMin v{0.0, -1};
+  if (j < mc) {
+    const double mu = mean[j], var = kd[j] - ssq[j];
+    const double s = sqrt(fabs(var));
+    const double sg = var > 0.0 ? 1.0 : (var < 0.0 ? -1.0 : 0.0);
+    double c, a, b;
+    if (acq == GPX_ACQ_UCB) {
+      c = -(mu - param * s);
+      a = -1.0;
+      b = param * sg / (2.0 * s);
+    } else {
+      const double g = (param - mu) / s;
+      const double Phi = 0.5 * erfc(-g * M_SQRT1_2);
+      const double phi = exp(-0.5 * g * g) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
+      if (acq == GPX_ACQ_PI) {
+        c = -Phi;
+        a = phi / s;
+        b = phi * g * sg / (2.0 * s * s);
+      } else {
+        c = -s * (g * Phi + phi);
+        a = Phi;
+        b = -phi * sg / (2.0 * s);
+      }
+    }
+    if (var == 0.0) a = b = __builtin_nan("");
+    cost[j0 + j] = c;
+    if (coef) {
+      coef[2 * j] = a;
+      coef[2 * j + 1] = b;
+    }
+    if (c == c) v = ArgMin{c, j0 + j};
+  }
+  const ArgMin r = argmin_block(v, sc, si);
+  if (threadIdx.x == 0) {
+    part_c[j0 / ACQ_EPI + blockIdx.x] = r.c;
+    part_i[j0 / ACQ_EPI + blockIdx.x] = r.i;
+  }
+}
+
+// the partials of all chunks -> out_c[0], out_i[0] (one workgroup; each thread folds a strided slice in index order first)
+__global__ __launch_bounds__(256) void acq_argmin_kernel(const double* __restrict__ part_c, const int64_t* __restrict__ part_i,
+                                                         int64_t np_, double* __restrict__ out_c, int64_t* __restrict__ out_i) {
+  __shared__ double sc[256];
+  __shared__ int64_t si[256];
+  ArgMin v{0.0, -1};
+  for (int64_t p = threadIdx.x; p < np_; p += 256) v = argmin_merge(v, ArgMin{part_c[p], part_i[p]});
+  const ArgMin r = argmin_block(v, sc, si);
+  if (threadIdx.x == 0) {
+    out_c[0] = r.i < 0 ? __builtin_nan("") : r.c;
+    out_i[0] = r.i;
+  }
+}
+
+// grad[m][l] = dA_m / dz_m[l] for the candidates of one chunk: one workgroup per candidate, one pass over the training points,
+// fixed-order tree reduction per coordinate.  betaT: row m = beta[:, m] (row stride ldt), coef[2m], coef[2m+1] = (a, b).
+// Per pair the radial factor f(r) multiplies (x_j - z) -- the derivative is linear in the coordinate difference for the three
+// kernels -- and the kernel's constant is applied once at the end:
+//     SE   f = k(z, x_j),              const_l = 1 / cl_l^2 = scale_l^2
+//     M32  f = e^-t,                   const   = sig scale^2
+//     M52  f = (1 + t) e^-t,           const   = sig scale^2 / 3
+template <int KIND, int DMAX>
+__global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double* __restrict__ X, int64_t n,
+                                                       const double* __restrict__ Zc, const double* __restrict__ betaT,
+                                                       int64_t ldt, const double* __restrict__ alpha,
+                                                       const double* __restrict__ coef, double* __restrict__ out) {
+  __shared__ double red[256];
+  const int64_t mm = blockIdx.x;
+  const int d = kp.d, t = threadIdx.x;
+  const double ca = coef[2 * mm], cb = -2.0 * coef[2 * mm + 1];
+  double zs[DMAX], s1[DMAX];
+#pragma unroll
+  for (int l = 0; l < DMAX; ++l) {
+    zs[l] = l < d ? Zc[mm * d + l] : 0.0;
+    s1[l] = 0.0;
+  }
+  const double* __restrict__ bt = betaT + mm * ldt;
+  for (int64_t j = t; j < n; j += 256) {
+    const double* xj = X + j * d;
+    double diff[DMAX], r2 = 0.0;
+#pragma unroll
+    for (int l = 0; l < DMAX; ++l) {
+      diff[l] = 0.0;
+      if (l < d) {
+        diff[l] = xj[l] - zs[l];
+        const double e = diff[l] * kp.scale[l];
+        r2 = fma(e, e, r2);
+      }
+    }
+    double f;
+    if (KIND == GPX_K_SE) {
+      f = kp.sig * exp(-0.5 * r2);
+    } else {
+      const double tt = sqrt(r2);
+      f = KIND == GPX_K_MATERN32 ? exp(-tt) : (1.0 + tt) * exp(-tt);
+    }
+    const double w = fma(ca, alpha[j], cb * bt[j]) * f;
+#pragma unroll
+    for (int l = 0; l < DMAX; ++l) s1[l] = fma(w, diff[l], s1[l]);
+  }
+#pragma unroll
+  for (int l = 0; l < DMAX; ++l) {
+    if (l < d) {   // (uniform)
+      double c = kp.scale[l] * kp.scale[l];
+      if (KIND == GPX_K_MATERN32) c *= kp.sig;
+      if (KIND == GPX_K_MATERN52) c *= kp.sig / 3.0;
+      red[t] = c * s1[l];
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+      }
+      if (t == 0) out[mm * d + l] = red[0];
+      __syncthreads();
+    }
+  }
+}
+
+int launch_acq_grad(gpx_ctx* ctx, const KParams& kp, const double* X, int64_t n, const double* Zc, int64_t mc,
+                    const double* betaT, int64_t ldt, const double* alpha, const double* coef, double* out) {
+#define GPX_CALL_K(K_, DM_)                                                                                               \
+  hipLaunchKernelGGL((acq_grad_kernel<K_, DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X, n, Zc, betaT, ldt, \
+                     alpha, coef, out)
+#define GPX_CALL_SE(DM_) GPX_CALL_K(GPX_K_SE, DM_)
+#define GPX_CALL_M32(DM_) GPX_CALL_K(GPX_K_MATERN32, DM_)
+#define GPX_CALL_M52(DM_) GPX_CALL_K(GPX_K_MATERN52, DM_)
+  if (kp.kind == GPX_K_SE) GPX_SE_DISPATCH(kp.d, GPX_CALL_SE);
+  else if (kp.kind == GPX_K_MATERN32) GPX_SE_DISPATCH(kp.d, GPX_CALL_M32);
+  else GPX_SE_DISPATCH(kp.d, GPX_CALL_M52);
+#undef GPX_CALL_M52
+#undef GPX_CALL_M32
+#undef GPX_CALL_SE
+#undef GPX_CALL_K
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+// Shared body of gpx_acq / gpx_acq_grad.  cost_host (M), grad_host (M x d) nullable; best / best_cost nullable.
+int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Z,
+             int acq, double param, double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
+  const int64_t n = L->rows, np = L->prows, M = Z->rows, d = kp.d;
+  const bool grad = grad_host != nullptr;
+  const int64_t mcmax = gpx_eval_chunk(np);
+  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  // the same solve as posterior_impl: from 2048 training points out of place through the block inverses
+  const bool oop = np >= 2048;
+  const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
+  const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
+  const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
+  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+  const int64_t bytesT = (grad && np >= 4096) ? mc_alloc * chol_binv_order(np) * 8 : 0;
+  void *pB = nullptr, *pW = nullptr, *pal = nullptr, *pmean = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
+  void *pcost = nullptr, *pcoef = nullptr, *pgrad = nullptr, *ppc = nullptr, *ppi = nullptr, *pbc = nullptr, *pbi = nullptr;
+  void* pT = nullptr;
+  int r = 0;
+  do {
+    if ((r = gpx_dev_alloc(ctx, bytesB, &pB)) != 0) break;
+    if ((oop || grad) && (r = gpx_dev_alloc(ctx, bytesB, &pW)) != 0) break;
+    if (bytesT && (r = gpx_dev_alloc(ctx, bytesT, &pT)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, np * 8, &pal)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytes_out, &pmean)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytes_out, &pout)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytes_out, &pkd)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, M * 8, &pcost)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppi)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, 8, &pbc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, 8, &pbi)) != 0) break;
+    if (grad) {
+      if ((r = gpx_dev_alloc(ctx, 2 * bytes_out, &pcoef)) != 0) break;
+      if ((r = gpx_dev_alloc(ctx, M * d * 8, &pgrad)) != 0) break;
+    }
+    if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      r = -2;
+      break;
+    }
+    for (int64_t j0 = 0; j0 < M && r == 0; j0 += mcmax) {
+      const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+      const int64_t mcp = gpx_round_up(mc, GPX_TILE);
+      double* B = (double*)pB;
+      const double* Zc = Z->p + j0 * d;
+      const int64_t ldb = gpx_skew_ld(mcp);
+      // posterior_impl's sequence, operation for operation: the values equal GP.evaluate's
+      if ((r = launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb)) != 0) break;
+      if ((r = launch_colreduce(ctx, B, ldb, n, mcp, (const double*)pal, (double*)pmean, (double*)ppart)) != 0) break;
+      double* Wsol = B;
+      if (oop) {
+        if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, (double*)pW, ldb, mcp)) != 0) break;
+        Wsol = (double*)pW;
+      } else if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp)) != 0) {
+        break;
+      }
+      if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, (double*)pout, (double*)ppart)) != 0) break;
+      if ((r = launch_kdiag(ctx, kp, Zc, mc, (double*)pkd)) != 0) break;
+      {
+        ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 5.0 * (double)mc);
+        hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
+                           param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, (double*)pcost,
+                           (double*)pcoef, (double*)ppc, (int64_t*)ppi);
+        if (hipGetLastError() != hipSuccess) {
+          r = -2;
+          break;
+        }
+      }
+      if (!grad) continue;
+      // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
+      double* Bt = Wsol == B ? (double*)pW : B;
+      if ((r = launch_transpose(ctx, Wsol, np, mcp, ldb, Bt, np)) != 0) break;
+      if (pT) r = chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, (double*)pT);
+      else r = chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np);
+      if (r != 0) break;
+      {
+        ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
+                     8.0 * ((double)n * (double)mc + (double)n * d));
+        r = launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, (const double*)pal, (const double*)pcoef,
+                            (double*)pgrad + j0 * d);
+      }
+    }
+    if (r != 0) break;
+    if (best || best_cost) {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
+      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                         (double*)pbc, (int64_t*)pbi);
+      if (hipGetLastError() != hipSuccess) {
+        r = -2;
+        break;
+      }
+      if ((best && hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+          (best_cost && hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
+        r = -2;
+        break;
+      }
+    }
+    if (cost_host && hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+      r = -2;
+      break;
+    }
+    if (grad_host && hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+      r = -2;
+      break;
+    }
+  } while (0);
+  (void)hipStreamSynchronize(ctx->stream);
+  if (pB) gpx_dev_release(ctx, pB, bytesB);
+  if (pW) gpx_dev_release(ctx, pW, bytesB);
+  if (pT) gpx_dev_release(ctx, pT, bytesT);
+  if (pal) gpx_dev_release(ctx, pal, np * 8);
+  if (pmean) gpx_dev_release(ctx, pmean, bytes_out);
+  if (pout) gpx_dev_release(ctx, pout, bytes_out);
+  if (pkd) gpx_dev_release(ctx, pkd, bytes_out);
+  if (ppart) gpx_dev_release(ctx, ppart, bytes_part);
+  if (pcost) gpx_dev_release(ctx, pcost, M * 8);
+  if (ppc) gpx_dev_release(ctx, ppc, nparts * 8);
+  if (ppi) gpx_dev_release(ctx, ppi, nparts * 8);
+  if (pbc) gpx_dev_release(ctx, pbc, 8);
+  if (pbi) gpx_dev_release(ctx, pbi, 8);
+  if (pcoef) gpx_dev_release(ctx, pcoef, 2 * bytes_out);
+  if (pgrad) gpx_dev_release(ctx, pgrad, M * d * 8);
+  if (r == -2) gpx_set_error("acq: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  return r;
+}
+
+int acq_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
+             const gpx_mat* Z, int acq, KParams* kp) {
+  GPX_ARG(ctx && L && X && Z && alpha, "NULL argument");
+  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
+  GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, kp));
+  GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
+  GPX_ARG(X->rows == L->rows, "X does not match the factor");
+  return gpx_kparams_sets(ctx, kp, X, Z);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpx_acq(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
+            const gpx_mat* Z, int acq, double param, double* cost, int64_t* best, double* best_cost) {
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, Z, acq, &kp));
+  if (Z->rows == 0) {
+    if (best) *best = -1;
+    if (best_cost) *best_cost = __builtin_nan("");
+    return 0;
+  }
+  return acq_impl(ctx, kp, L, X, alpha, Z, acq, param, cost, best, best_cost, nullptr);
+}
+
+int gpx_acq_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                 const double* alpha, const gpx_mat* Z, int acq, double param, double* cost, double* grad) {
+  GPX_ARG(grad != nullptr, "grad is NULL");
+  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
+          "acquisition gradients exist for the stationary kernels (SE, Matern 3/2, Matern 5/2) only: the Mehler kernel's "
+          "prior variance depends on the point");
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, Z, acq, &kp));
+  if (Z->rows == 0) return 0;
+  return acq_impl(ctx, kp, L, X, alpha, Z, acq, param, cost, nullptr, nullptr, grad);
+}
+
+}  // extern "C"

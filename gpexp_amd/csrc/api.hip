@@ -1194,6 +1194,7 @@ static int64_t eval_chunk(int64_t np) {
   if (mc < GPX_TILE) mc = GPX_TILE;
   return mc;
 }
+int64_t gpx_eval_chunk(int64_t np) { return eval_chunk(np); }
 
 // Shared body; mean/var are host arrays of length M (nullable).  For every chunk of Z: B = K(X, Zc) (N x chunk),
 // mean = B^T alpha (column dots), W = L^-1 B (recursive LEFT triangular solve: NN updates B2 -= L21 W1), var = k(z,z) -

@@ -204,6 +204,21 @@ struct ProfScope {
 };
 int gpx_prof_flush(gpx_ctx* ctx);
 
+// d rounded up to the instantiated register-array sizes of the per-point kernels templated on the dimension (grad.hip, acq.hip)
+#define GPX_SE_DISPATCH(d_, CALL) \
+  do {                            \
+    if ((d_) <= 1) { CALL(1); }   \
+    else if ((d_) <= 2) { CALL(2); } \
+    else if ((d_) <= 4) { CALL(4); } \
+    else if ((d_) <= 8) { CALL(8); } \
+    else if ((d_) <= 16) { CALL(16); } \
+    else { CALL(32); }            \
+  } while (0)
+
+// evaluation points per chunk of the posterior-shaped passes (gpx_posterior, gpx_acq): the N x chunk cross matrix under ~16 GiB,
+// or GPX_CROSS_BYTES
+extern "C" int64_t gpx_eval_chunk(int64_t np);
+
 // ---- kernel launchers (all asynchronous on ctx->stream) ------------------------------------------
 // kfill.hip
 int launch_kfill(gpx_ctx* ctx, const KParams& kp, const double* A, int64_t na, const double* B, int64_t nb,

@@ -433,17 +433,6 @@ int solve_scratch(gpx_ctx* ctx, Scratch& sc, int64_t np, int64_t mcp, double** T
   return 0;
 }
 
-// d rounded up to the instantiated register-array sizes
-#define GPX_SE_DISPATCH(d_, CALL) \
-  do {                            \
-    if ((d_) <= 1) { CALL(1); }   \
-    else if ((d_) <= 2) { CALL(2); } \
-    else if ((d_) <= 4) { CALL(4); } \
-    else if ((d_) <= 8) { CALL(8); } \
-    else if ((d_) <= 16) { CALL(16); } \
-    else { CALL(32); }            \
-  } while (0)
-
 int upload(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t count, double** dev) {
   *dev = nullptr;
   if (!host) return 0;

@@ -434,6 +434,31 @@ def greedy_ivar_step(ctx, spec, L, X, Cpts, Z, noise, want_costs=True):
     return best.value, costs
 
 
+ACQ_UCB, ACQ_PI, ACQ_EI = 0, 1, 2
+
+
+def acq(ctx, spec, L, X, alpha, Z, kind, param, want_costs=True):
+    """Bayesian-optimisation costs of the M candidates Z (gpx_acq): (first arg-min among the non-NaN costs or -1, its cost,
+    costs (M,) or None)."""
+    costs = np.empty(Z.shape[0]) if want_costs else None
+    best, best_cost = c_i64(), C.c_double()
+    al = as_f64(alpha)
+    check(ctx.lib.gpx_acq(ctx.h, *spec.args(), L.h, X.h, dptr(al), Z.h, int(kind), float(param), dptr(costs),
+                          C.byref(best), C.byref(best_cost)))
+    return best.value, best_cost.value, costs
+
+
+def acq_grad(ctx, spec, L, X, alpha, Z, kind, param):
+    """(costs (M,), d cost_m / d z_m (M, d)) of the M candidates Z (gpx_acq_grad)."""
+    m, d = Z.shape
+    costs = np.empty(m)
+    grad = np.empty((m, d))
+    al = as_f64(alpha)
+    check(ctx.lib.gpx_acq_grad(ctx.h, *spec.args(), L.h, X.h, dptr(al), Z.h, int(kind), float(param), dptr(costs),
+                               dptr(grad)))
+    return costs, grad
+
+
 def greedy_ivar(ctx, spec, L, X, Cpts, Z, noise, nsel, want_all=False):
     """nsel picks of discrete greedy IVAR with resident state (gpx_greedy_ivar): (indices, winner costs[, all costs nsel x M])."""
     nsel = int(nsel)

@@ -26,16 +26,20 @@ try:
 except ImportError:  # pragma: no cover
     slsqp = None
 import scipy.optimize as optimize
+import scipy.stats as spstats
+from scipy.optimize import fmin_l_bfgs_b as _bfgs
 
 from . import device as _dev
 from . import dist as _dist
 from . import gp_kernel_utilities  # noqa: F401  (the reference module exposes it)
+from .gp import GP as _GP
 
 NLOPT = False
 
 __all__ = ["costFunctionBase", "costFunctionGP_IVAR", "costFunctionGP_MI", "ExperimentalDesign",
            "ExperimentalDesignDerivative", "performGreedyVarExperimentalDesign",
-           "performGreedyMIExperimentalDesign", "greedyIVARStep", "performGreedyIVARExperimentalDesign", "np"]
+           "performGreedyMIExperimentalDesign", "greedyIVARStep", "performGreedyIVARExperimentalDesign", "costFuncGPUCbound",
+           "costFuncPI", "costFuncEI", "optimizeAcquisition", "np"]
 
 
 class costFunctionBase(object):
@@ -442,3 +446,205 @@ def performGreedyIVARExperimentalDesign(gaussianProcess, candidates, mcPoints, n
     if returnCosts:
         return idx, costs
     return candidates[list(idx), :]
+
+
+##########################################################
+# Bayesian-optimisation cost functions (experimentalDesign.py:886-1003)
+##########################################################
+def firstMinIndex(costs):
+    """Selection rule of bestCandidate (and of gpx_acq): the FIRST index of the minimum among the non-NaN costs, -1 when every
+    cost is NaN."""
+    c = np.asarray(costs, dtype=float).ravel()
+    ok = np.flatnonzero(~np.isnan(c))
+    if ok.size == 0:
+        return -1
+    return int(ok[np.argmin(c[ok])])
+
+
+class _costFuncBO(costFunctionBase):
+    """Shared part of the three Bayesian-optimisation costs.
+
+    Reference semantics (experimentalDesign.py:889-1003): the constructor takes a SHALLOW copy of the GP (`copy.copy`) and trains it
+    on (xTrain, yTrain) -- the caller's GP is left untouched (the copy's refit replaces its handles, gp.py) -- and `evaluate` scores
+    the LAST row of its argument only, through a single-row GP.evaluate(compvar=1) and scipy.stats.
+
+    Batched forms on the device (the new capability; dense models only -- a GP built with FITC=... raises NotImplementedError):
+      evaluateBatch(candidates)    (M,) costs                                gpx_acq
+      bestCandidate(candidates)    (first arg-min among the non-NaN costs or -1, its cost)   gpx_acq
+      derivativeBatch(candidates)  (M, d): row m = d cost_m / d candidate_m   gpx_acq_grad
+      derivative(trainPoints)      (d,): the gradient for the last row
+    Under a multi-process launch these run replicated: every rank makes the same deterministic single-GPU call on the factor."""
+
+    _acq = None
+
+    def __init__(self, gaussianProcess, xTrain, yTrain, nInputs, space):
+        super(_costFuncBO, self).__init__(nInputs, space)
+        self.xTrain = xTrain
+        self.yTrain = yTrain
+        self.gaussianProcess = copy.copy(gaussianProcess)
+        self.gaussianProcess.train(xTrain, yTrain)
+
+    def _fBest(self):
+        return np.max(self.yTrain)
+
+    def _param(self):
+        return self._fBest()
+
+    def _posterior(self, trainPoints):
+        newPoint = np.reshape(trainPoints[-1, :], (1, self.space.dimension))
+        predMean, predvar = self.gaussianProcess.evaluate(newPoint, compvar=1)
+        return predMean, np.sqrt(predvar)
+
+    def _dense(self, candidates):
+        gp = self.gaussianProcess
+        if gp._fitc is not None or not gp._has_factor():
+            raise NotImplementedError("batched acquisition costs need the dense Cholesky factor (GP built with FITC=... has none)")
+        # the device forms mean = K(Z, X) coeff: the zero prior mean of the base class (gp.py:73)
+        assert type(gp).gpPriorMean is _GP.gpPriorMean and "gpPriorMean" not in vars(gp), \
+            "batched acquisition costs assume the base class's zero gpPriorMean"
+        candidates = np.asarray(candidates, dtype=float)
+        assert candidates.ndim == 2 and candidates.shape[1] == self.space.dimension, \
+            ("candidates are the wrong size: ", candidates.shape)
+        ctx = _dev.context()
+        return ctx, gp, _dev.points(ctx, candidates)
+
+    def evaluateBatch(self, candidates):
+        """(M,) costs of the candidates (rows), one device call."""
+        ctx, gp, Z = self._dense(candidates)
+        return _dev.acq(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param())[2]
+
+    def bestCandidate(self, candidates):
+        """(index, cost): the first index of the minimum among the non-NaN costs (-1 and NaN when every cost is NaN)."""
+        ctx, gp, Z = self._dense(candidates)
+        best, cost, _ = _dev.acq(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param(), want_costs=False)
+        return best, cost
+
+    def evaluateBatchWithDerivative(self, candidates):
+        """((M,) costs, (M, d) gradients), one device call."""
+        ctx, gp, Z = self._dense(candidates)
+        return _dev.acq_grad(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param())
+
+    def derivativeBatch(self, candidates):
+        """(M, d): row m = d cost_m / d candidate_m -- the true derivative of evaluateBatch (squared exponential, Matern 3/2 and
+        5/2; the Mehler kernel raises)."""
+        return self.evaluateBatchWithDerivative(candidates)[1]
+
+    def derivative(self, trainPoints):
+        """(d,): the gradient of the cost of the last row."""
+        return self.derivativeBatch(np.reshape(trainPoints[-1, :], (1, self.space.dimension)))[0]
+
+
+class costFuncGPUCbound(_costFuncBO):
+    """GP upper confidence bound, minimisation form: -(mu - kappa s), s = sqrt(|var|) (experimentalDesign.py:889-923).
+
+    Quirks kept from the reference: only the last row of `trainPoints` is scored; fBest = max(yTrain) is computed there and unused;
+    the return value is a Python float (taken from the 1-element result without NumPy's array-to-scalar DeprecationWarning, which
+    the reference's `float(array)` triggers)."""
+
+    _acq = _dev.ACQ_UCB
+
+    def __init__(self, gaussianProcess, kappa, xTrain, yTrain, nInputs, space, **kwargs):
+        self.kappa = kappa  # kappa is tunable to balance exploit vs explore
+        super(costFuncGPUCbound, self).__init__(gaussianProcess, xTrain, yTrain, nInputs, space)
+
+    def _param(self):
+        return self.kappa
+
+    def evaluate(self, trainPoints):
+        predMean, predstd = self._posterior(trainPoints)
+        return -float((predMean - self.kappa * predstd)[0])
+
+
+class costFuncPI(_costFuncBO):
+    """Probability of improvement, minimisation form: -Phi((fBest - mu) / s) with fBest = max(yTrain) (experimentalDesign.py:925-960).
+
+    Quirks kept from the reference: only the last row of `trainPoints` is scored; fBest is the MAXIMUM of yTrain (paired with a
+    minimised cost; not "fixed"); the return value is a Python float (without the array-to-scalar DeprecationWarning)."""
+
+    _acq = _dev.ACQ_PI
+
+    def __init__(self, gaussianProcess, xTrain, yTrain, nInputs, space, **kwargs):
+        super(costFuncPI, self).__init__(gaussianProcess, xTrain, yTrain, nInputs, space)
+
+    def evaluate(self, trainPoints):
+        fBest = self._fBest()
+        predMean, predstd = self._posterior(trainPoints)
+        gamma = (fBest - predMean) / predstd
+        phiGamma = spstats.norm.cdf(gamma)
+        return -float(phiGamma[0])
+
+
+class costFuncEI(_costFuncBO):
+    """Expected improvement, minimisation form: -s (g Phi(g) + phi(g)), g = (fBest - mu) / s (experimentalDesign.py:962-1003).
+
+    Quirks kept from the reference: only the last row of `trainPoints` is scored; fBest is the `fBest=` keyword when given, else the
+    MAXIMUM of yTrain (paired with a minimised cost; not "fixed"); the return value is a NumPy scalar (`cost[0]`)."""
+
+    _acq = _dev.ACQ_EI
+
+    def __init__(self, gaussianProcess, xTrain, yTrain, nInputs, space, **kwargs):
+        super(costFuncEI, self).__init__(gaussianProcess, xTrain, yTrain, nInputs, space)
+        if 'fBest' in kwargs:
+            self.fBest = kwargs['fBest']
+
+    def _fBest(self):
+        return self.fBest if hasattr(self, 'fBest') else np.max(self.yTrain)
+
+    def evaluate(self, trainPoints):
+        fBest = self._fBest()
+        predMean, predstd = self._posterior(trainPoints)
+        gamma = (fBest - predMean) / predstd
+        phiGamma = spstats.norm.cdf(gamma)
+        probGamma = spstats.norm.pdf(gamma)
+        cost = -predstd * (gamma * phiGamma + probGamma)
+        return cost[0]
+
+
+def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rbounds=None, maxiter=50):
+    """Minimise a Bayesian-optimisation cost (costFuncGPUCbound / costFuncPI / costFuncEI) over a box: one discrete pass over the
+    candidates on the device (gpx_acq), then SciPy L-BFGS-B from the `nStarts` best distinct candidates at once -- the objective is
+    the SUM of the starts' costs over the stacked nStarts x d vector (separable), so every iteration is ONE gpx_acq_grad call.
+    The box defaults to the candidates' bounding box; candidates outside it take no part.
+
+    Returns (point (1 x d), cost, discreteIndex): the best polished start when it beats the discrete winner, else the discrete winner
+    itself -- the cost is never above the discrete winner's and never NaN.  Deterministic: the same inputs give the same output."""
+    allCandidates = np.asarray(candidates, dtype=float)
+    d = allCandidates.shape[1]
+    lb = np.min(allCandidates, axis=0) if lbounds is None else np.broadcast_to(np.asarray(lbounds, dtype=float), (d,))
+    ub = np.max(allCandidates, axis=0) if rbounds is None else np.broadcast_to(np.asarray(rbounds, dtype=float), (d,))
+    # candidates outside the box take no part (discreteIndex still counts rows of `candidates`)
+    inside = np.flatnonzero(np.all((allCandidates >= lb) & (allCandidates <= ub), axis=1))
+    candidates = allCandidates[inside]
+    if len(candidates) == 0:
+        raise ValueError("optimizeAcquisition: no candidate lies inside the bounds")
+    ctx, gp, Z = costFunction._dense(candidates)
+    spec = gp.kernel._spec()
+    best, bestCost, costs = _dev.acq(ctx, spec, gp._L, gp._X, gp.coeff, Z, costFunction._acq, costFunction._param())
+    if best < 0:
+        raise ValueError("optimizeAcquisition: every candidate's cost is NaN")
+    # starts: the nStarts best candidates (NaN costs last, ties in index order), duplicates of a chosen row skipped
+    order = np.argsort(np.where(np.isnan(costs), np.inf, costs), kind="stable")
+    starts = []
+    for j in order:
+        if len(starts) >= int(nStarts) or np.isnan(costs[j]):
+            break
+        if not any(np.array_equal(candidates[j], candidates[s]) for s in starts):
+            starts.append(int(j))
+    k = len(starts)
+    x0 = np.clip(candidates[starts], lb, ub).ravel()
+    bounds = list(zip(np.tile(lb, k), np.tile(ub, k)))
+
+    def objective(x):
+        P = np.ascontiguousarray(np.reshape(x, (k, d)))
+        c, g = _dev.acq_grad(ctx, spec, gp._L, gp._X, gp.coeff, _dev.points(ctx, P), costFunction._acq, costFunction._param())
+        if not np.all(np.isfinite(c)) or not np.all(np.isfinite(g)):   # (var == 0 exactly: steer the line search away)
+            return 1e300, np.zeros(k * d)
+        return float(np.sum(c)), g.ravel()
+
+    x = _bfgs(objective, x0, bounds=bounds, maxiter=int(maxiter))[0]
+    P = np.clip(np.reshape(x, (k, d)), lb, ub)
+    j, c = _dev.acq(ctx, spec, gp._L, gp._X, gp.coeff, _dev.points(ctx, P), costFunction._acq, costFunction._param(),
+                    want_costs=False)[:2]
+    if j >= 0 and c < bestCost:
+        return P[j:j + 1].copy(), float(c), int(inside[best])
+    return candidates[best:best + 1].copy(), float(bestCost), int(inside[best])

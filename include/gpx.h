@@ -192,6 +192,26 @@ int gpx_greedy_ivar(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
 int gpx_mi_greedy(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* C, double noise,
                   int64_t nsel, int64_t start, int64_t* out_idx, double* out_ratio);
 
+/* ---- Bayesian-optimisation costs (costFuncGPUCbound / costFuncPI / costFuncEI, experimentalDesign.py:889-1003) ----------------
+ * The reference scores ONE point per call (the last row of trainPoints: a single-row GP.evaluate(compvar=1) + scipy.stats); these
+ * score the M candidates of Z in one call, in minimisation form.  mu = posterior mean (alpha: the trained coefficients, host N),
+ * s = sqrt(|var|) (GP.evaluate's abs, gp.py:145), g = (fBest - mu) / s, Phi / phi the standard normal cdf / density:
+ *     GPX_ACQ_UCB  cost = -(mu - kappa s)            param = kappa   (experimentalDesign.py:899-923)
+ *     GPX_ACQ_PI   cost = -Phi(g)                    param = fBest   (experimentalDesign.py:934-960)
+ *     GPX_ACQ_EI   cost = -s (g Phi(g) + phi(g))     param = fBest   (experimentalDesign.py:973-1003)
+ * Dense factor only (gpx_potrf / gpx_refit_rows); the kernel's prior mean is zero (gp.py:73). */
+enum gpx_acq_kind { GPX_ACQ_UCB = 0, GPX_ACQ_PI = 1, GPX_ACQ_EI = 2 };
+/* cost (host M, nullable) every candidate's cost; *best (nullable) = the FIRST index of the minimum among the non-NaN costs, -1 when
+ * every cost is NaN; *best_cost (nullable) its cost (NaN when best == -1).  The arg-min is deterministic and does not depend on
+ * how Z is chunked (GPX_CROSS_BYTES).  Only cost (when asked for) and the winner reach the host. */
+int gpx_acq(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+            const double* alpha, const gpx_mat* Z, int acq, double param, double* cost, int64_t* best, double* best_cost);
+/* grad (host M x d): grad[m*d + l] = d cost_m / d z_m[l], the true derivative of gpx_acq's values (NaN rows where var == 0
+ * exactly); cost (host M, nullable) as gpx_acq.  Stationary kernels only (SE, Matern 3/2, Matern 5/2): Mehler is an argument
+ * error. */
+int gpx_acq_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                 const double* alpha, const gpx_mat* Z, int acq, double param, double* cost, double* grad);
+
 /* ---- hyper-parameter gradient -------------------------------------------------------------------- */
 /* grad[k] = 1/2 tr((alpha alpha^T - K^-1) dK/d theta_k), theta = {hyp[0..nhyp-1], noise}; the noise entry is
  * the raw 1/2 tr(alpha alpha^T - K^-1) (the caller applies the reference's x 2*noise, gp.py:463-464).

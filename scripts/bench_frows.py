@@ -3,7 +3,7 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq]
 """
 import json
 import os
@@ -221,3 +221,48 @@ if want("f3"):
         f3_case("C2: N=4096 d=3 iso-SE", lambda: KernelSquaredExponential([0.5], 1.0, 3), 4096, 3, 40)
         f3_case("N=16384 d=8 Matern-5/2", lambda: KernelIsoMatern(0.7, 1.0, 8, nu=2.5), 16384, 8, 24)
         f3_case("N=16384 d=8 ARD-SE", lambda: KernelSquaredExponential(list(0.5 + 0.05 * np.arange(8)), 1.0, 8), 16384, 8, 24)
+# ---- acq: Bayesian-optimisation costs (costFuncGPUCbound / costFuncPI / costFuncEI, experimentalDesign.py:889-1003)
+if want("acq"):
+    from gpExp.kernels import KernelIsoMatern
+    from gpExp.gp import GP
+    from gpExp.experimentalDesign import costFuncEI
+    import scipy.stats as spstats
+
+    class _Space(object):
+        dimension = 8
+
+    Na, Ma = (2048, 16384) if quick else (8192, 131072)
+    ra = np.random.default_rng(Na)
+    Xa = ra.uniform(-1, 1, (Na, 8))
+    ya = np.sin(3.0 * Xa[:, 0]) + 0.5 * np.cos(2.0 * Xa.sum(1)) + 0.05 * ra.standard_normal(Na)
+    Za = ra.uniform(-1, 1, (Ma, 8))
+    cf = costFuncEI(GP(KernelIsoMatern(1.5, 1.0, 8, nu=2.5), 1e-2), Xa, ya, 2, _Space())
+    size = dict(N=Na, d=8, M=Ma, kernel="Matern-5/2", acq="EI")
+
+    def values():
+        return cf.evaluateBatch(Za), cf.bestCandidate(Za)
+
+    values()
+    _, t = best(values)
+    report("gpx_acq (evaluateBatch + bestCandidate)", "costFuncEI.evaluate, one point per call (experimentalDesign.py:962-1003)",
+           size, t, flops=2.0 * Na * Na * Ma,
+           note="two passes (costs to the host, then the arg-min alone); each one is N^2 M (the forward solve)")
+    _, t1 = best(lambda: cf.bestCandidate(Za))
+    report("gpx_acq (bestCandidate only)", "costFuncEI.evaluate", size, t1, flops=1.0 * Na * Na * Ma)
+    _, t = best(lambda: cf.derivativeBatch(Za))
+    report("gpx_acq_grad (derivativeBatch)", "none in the reference (BO costs have no gradient there)", size, t,
+           flops=2.0 * Na * Na * Ma + 6.0 * Na * Ma * 8,
+           note="forward + backward solve 2 N^2 M, fused pass over the training points O(N M d)")
+    gpa = cf.gaussianProcess
+    fb = float(np.max(ya))
+
+    def composition():
+        mu, var = gpa.evaluate(Za, compvar=1)
+        s = np.sqrt(var)
+        g = (fb - mu) / s
+        c = -s * (g * spstats.norm.cdf(g) + spstats.norm.pdf(g))
+        return int(np.argmin(c))
+
+    _, t = best(composition)
+    report("composition GP.evaluate(compvar=1) + NumPy", "what a user writes today on this library", size, t,
+           flops=1.0 * Na * Na * Ma)
