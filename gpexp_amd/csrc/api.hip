@@ -1557,4 +1557,13 @@ int gpx_dbg_gemm(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C, i
   return 0;
 }
 
+int gpx_dbg_gemm_strassen(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C) {
+  GPX_ARG(ctx && A && B && C, "NULL argument");
+  const int64_t m = C->prows, n = C->pcols, k = A->pcols;
+  GPX_ARG(A->prows == m && B->prows == k && B->pcols == n, "operand shapes");
+  GPX_TRY(launch_gemm_strassen(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, nullptr, 0));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 }  // extern "C"

@@ -1462,6 +1462,10 @@ struct PotrsPlan {
   const double* binv;       // [ceil(n/sib)][sib][sib]
   const double* binvT;
   double* part;             // colreduce partials
+  // left solve only (chol_trsm_left_oop): updates above the size gate run as one Strassen level out of this scratch
+  bool strassen = false;
+  double* sscr = nullptr;
+  int64_t sscr_bytes = 0;
 };
 static inline int64_t blk_off(const PotrsPlan& P, int64_t b) { return b * P.ib < P.n ? b * P.ib : P.n; }
 // inverse of diagonal block b: the diagonal ib x ib sub-block of the stored sib-order inverse that contains it (the inverse
@@ -1508,6 +1512,22 @@ static int potrs_bwd(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64_t b1, d
 // W = L^-1 B, out of place: W_b = Binv_b B_b (lower-triangular operand: half the k range per row tile), then the block
 // rows below take B -= L[below, b] W_b.  Every update has K >= the inverse order (1024): none of the K = 128..512 products
 // of the leaf-level recursion (22-60 TF/s at C4), and the diagonal solves run as chip-filling GEMMs.
+//
+// The largest updates run as ONE LEVEL OF STRASSEN'S SCHEME (launch_gemm_strassen: 7 half-size products for 8).  The levels of
+// this recursion carry N^2 M / 2, / 4, / 8 ... flops, and the half-size products of the first two levels at C4 are shapes the
+// GEMM runs at its full rate (K >= 4096); further down the right operand's sums -- all m columns wide at every level -- cost as
+// much as the eighth product saves.  Gate: rows and k of the update, columns of the right-hand side (GPX_STRASSEN=0: never).
+#ifndef GPX_STRASSEN_MIN_ROWS
+#define GPX_STRASSEN_MIN_ROWS 8192
+#endif
+#ifndef GPX_STRASSEN_MIN_COLS
+#define GPX_STRASSEN_MIN_COLS 4096
+#endif
+static inline bool strassen_gate(int64_t rows, int64_t cols, int64_t k) {
+  return rows >= GPX_STRASSEN_MIN_ROWS && k >= GPX_STRASSEN_MIN_ROWS && cols >= GPX_STRASSEN_MIN_COLS &&
+         gemm_strassen_scratch_bytes(rows, cols, k) > 0;
+}
+
 static int trsm_left_oop_rec(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64_t b1, double* B, int64_t ldb, double* W,
                              int64_t ldw, int64_t m) {
   if (b1 - b0 == 1) {
@@ -1518,8 +1538,12 @@ static int trsm_left_oop_rec(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64
   const int64_t mid = (b0 + b1) / 2;
   GPX_TRY(trsm_left_oop_rec(ctx, P, b0, mid, B, ldb, W, ldw, m));
   const int64_t r0 = blk_off(P, mid), r1 = blk_off(P, b1), c0 = blk_off(P, b0);
-  GPX_TRY(launch_gemm(ctx, P.L + r0 * P.ld + c0, P.ld, W + c0 * ldw, ldw, B + r0 * ldb, ldb, r1 - r0, m, r0 - c0, false, true,
-                      false));
+  if (P.strassen && strassen_gate(r1 - r0, m, r0 - c0))
+    GPX_TRY(launch_gemm_strassen(ctx, P.L + r0 * P.ld + c0, P.ld, W + c0 * ldw, ldw, B + r0 * ldb, ldb, r1 - r0, m, r0 - c0,
+                                 P.sscr, P.sscr_bytes));
+  else
+    GPX_TRY(launch_gemm(ctx, P.L + r0 * P.ld + c0, P.ld, W + c0 * ldw, ldw, B + r0 * ldb, ldb, r1 - r0, m, r0 - c0, false,
+                        true, false));
   return trsm_left_oop_rec(ctx, P, mid, b1, B, ldb, W, ldw, m);
 }
 
@@ -1537,7 +1561,30 @@ int chol_trsm_left_oop(gpx_ctx* ctx, gpx_mat* Lm, double* B, int64_t ldb, double
   P.binv = Lm->binv;
   P.binvT = nullptr;
   P.part = nullptr;
-  return trsm_left_oop_rec(ctx, P, 0, P.nblk, B, ldb, W, ldw, m);
+  // Strassen scratch for the whole sweep: sized for the top-level update (the lower levels need less), taken from the pool
+  // once.  No scratch -> the classical sweep, as before.
+  void* ps = nullptr;
+  int64_t sbytes = 0;
+  if (P.nblk >= 2 && env_i64("GPX_STRASSEN", 1) != 0) {
+    const int64_t r0 = blk_off(P, P.nblk / 2);
+    if (strassen_gate(P.n - r0, m, r0)) {
+      // (the top-level update is the largest in rows x k; an uneven split further down can only be smaller in both)
+      sbytes = gemm_strassen_scratch_bytes(P.n - r0, m, r0);
+      if (gpx_dev_alloc(ctx, sbytes, &ps) != 0) {
+        (void)hipGetLastError();
+        ps = nullptr;
+      }
+    }
+  }
+  P.strassen = ps != nullptr;
+  P.sscr = (double*)ps;
+  P.sscr_bytes = sbytes;
+  const int r = trsm_left_oop_rec(ctx, P, 0, P.nblk, B, ldb, W, ldw, m);
+  if (ps) {
+    (void)hipStreamSynchronize(ctx->stream);   // the operand sums go back to the pool
+    gpx_dev_release(ctx, ps, sbytes);
+  }
+  return r;
 }
 
 int chol_trsm_left_group(gpx_ctx* ctx, const double* Lg, int64_t ld, const double* invd, int64_t w, int64_t below, int64_t ib,

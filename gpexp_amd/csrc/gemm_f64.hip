@@ -111,10 +111,24 @@ struct NoSeg {
   static constexpr bool on = false;
 };
 
+// TWO-DESTINATION epilogue (EPI::on, accumulating tiles only): C1 -= acc; C2 -= s * acc with s = +-1 (exact), C2 a second
+// matrix with C's row stride.  One Strassen product lands in both quadrants of the right-hand side that take it, with no
+// product temporary and no combine pass (launch_gemm_strassen).  Like SEGF, every use is behind `if constexpr`: the
+// single-destination instantiations compile to exactly the code they had before.
+struct NoDual {
+  static constexpr bool on = false;
+};
+struct Dual {
+  static constexpr bool on = true;
+  double* c2;
+  double s;
+};
+
 // (Variants measured and dropped: a 2-deep register prefetch; reading only two k-substeps' fragments at a time.)
-template <bool BT, bool ACC, int TE, class SEGF = NoSeg>
+template <bool BT, bool ACC, int TE, class SEGF = NoSeg, class EPI = NoDual>
 __device__ __forceinline__ void gemm_tile(Smem<BT, TE>& sm, const double* A, int64_t lda, const double* B, int64_t ldb,
-                                          double* C, int64_t ldc, int nk, int by, int bx, const SEGF& segf = SEGF()) {
+                                          double* C, int64_t ldc, int nk, int by, int bx, const SEGF& segf = SEGF(),
+                                          const EPI& epi = EPI()) {
   constexpr int SBN = TE + 16;     // row stride of the [k][n] image
   constexpr int FI = TE / 32;      // MFMA tiles per wave and dimension
   constexpr int NL = TE / 32;      // 16-byte staging loads per thread and operand
@@ -346,6 +360,30 @@ __device__ __forceinline__ void gemm_tile(Smem<BT, TE>& sm, const double* A, int
 
   // epilogue: reg v of lane l -> C[(l>>4)+4v][l&15] within each 16x16 tile
   double* Cw = C + (m0 + wm * WS + fk) * ldc + n0 + wn * WS + fr;
+  if constexpr (EPI::on) {
+    static_assert(ACC, "the two-destination epilogue accumulates");
+    double* Cw2 = epi.c2 + (m0 + wm * WS + fk) * ldc + n0 + wn * WS + fr;
+    const double s2 = epi.s;
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        double* cp = Cw + (int64_t)(i * 16 + 4 * v) * ldc;
+        double* cq = Cw2 + (int64_t)(i * 16 + 4 * v) * ldc;
+        double cv[FI], cw[FI];
+#pragma unroll
+        for (int j = 0; j < FI; ++j) {
+          cv[j] = cp[j * 16];
+          cw[j] = cq[j * 16];
+        }
+#pragma unroll
+        for (int j = 0; j < FI; ++j) {
+          cp[j * 16] = cv[j] - acc[i][j][v];
+          cq[j * 16] = cw[j] - s2 * acc[i][j][v];
+        }
+      }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < FI; ++i)
 #pragma unroll
@@ -418,6 +456,55 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(const double* A, int64
     nkt = nk - bx * (TE / KB);
   }
   gemm_tile<BT, ACC, TE>(sm, A, lda, B, ldb, C, ldc, nkt, by, bx);
+}
+
+// NN accumulating product into TWO destinations (see Dual): the rectangular, dense-operand map of gemm_f64_kernel, no tail.
+template <int TE>
+__global__ __launch_bounds__(256, 2) void gemm_f64_dual_kernel(const double* A, int64_t lda, const double* B, int64_t ldb,
+                                                               double* C, double* C2, double s, int64_t ldc, int nk,
+                                                               int tiles_m, int tiles_n, int sb_cols, int sb_shift) {
+  __shared__ Smem<false, TE> sm;
+  const int w = blockIdx.x;
+  const int xcd = w & 7, q = w >> 3;
+  const int sbs2 = 2 * sb_shift;
+  int by, bx;
+  if (!tile_of<false>((q >> sbs2) * 8 + xcd, q & ((1 << sbs2) - 1), tiles_m, tiles_n, sb_cols, sb_shift, &by, &bx, 0)) return;
+  gemm_tile<false, true, TE, NoSeg, Dual>(sm, A, lda, B, ldb, C, ldc, nk, by, bx, NoSeg(), Dual{C2, s});
+}
+
+// Operand sums of one Strassen level: X (2 hr x 2 hc, row stride ldx) is read ONCE, quadrant by quadrant, and the five
+// sums go to S[0..4] (hr x hc each, row stride lds, `sstride` doubles apart).  16-byte loads and stores; HBM-bound
+// (9 quadrant passes where five separate kernels would make 15).
+//   left operand  (BSIDE = false): X11+X22, X21+X22, X11+X12, X21-X11, X12-X22
+//   right operand (BSIDE = true):  X11+X22, X12-X22, X21-X11, X11+X12, X21+X22
+template <bool BSIDE>
+__global__ __launch_bounds__(256) void strassen_sums_kernel(const double* __restrict__ X, int64_t ldx, int64_t hr, int64_t hc,
+                                                            double* __restrict__ S, int64_t lds, int64_t sstride) {
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  if (j >= hc) return;   // (hc is even: j + 1 < hc)
+  for (int64_t i = blockIdx.y; i < hr; i += gridDim.y) {
+    const double* x1 = X + i * ldx + j;
+    const double* x2 = X + (i + hr) * ldx + j;
+    const double2 x11 = *reinterpret_cast<const double2*>(x1);
+    const double2 x12 = *reinterpret_cast<const double2*>(x1 + hc);
+    const double2 x21 = *reinterpret_cast<const double2*>(x2);
+    const double2 x22 = *reinterpret_cast<const double2*>(x2 + hc);
+    double* o = S + i * lds + j;
+#define GPX_S2(k_, ex_, ey_) *reinterpret_cast<double2*>(o + (k_) * sstride) = make_double2(ex_, ey_)
+    GPX_S2(0, x11.x + x22.x, x11.y + x22.y);
+    if (BSIDE) {
+      GPX_S2(1, x12.x - x22.x, x12.y - x22.y);
+      GPX_S2(2, x21.x - x11.x, x21.y - x11.y);
+      GPX_S2(3, x11.x + x12.x, x11.y + x12.y);
+      GPX_S2(4, x21.x + x22.x, x21.y + x22.y);
+    } else {
+      GPX_S2(1, x21.x + x22.x, x21.y + x22.y);
+      GPX_S2(2, x11.x + x12.x, x11.y + x12.y);
+      GPX_S2(3, x21.x - x11.x, x21.y - x11.y);
+      GPX_S2(4, x12.x - x22.x, x12.y - x22.y);
+    }
+#undef GPX_S2
+  }
 }
 
 // Batched form for many small independent products with constant strides (the block inverses of the triangular sweeps,
@@ -765,6 +852,98 @@ int launch_gemm_tri(gpx_ctx* ctx, const double* A, int64_t lda, const double* B,
 #undef GPX_KT
   GPX_HIP(hipGetLastError());
   return 0;
+}
+
+// ---- one level of Strassen's scheme for the large NN updates of the left solve ---------------------------------------------
+// C -= A B with 7 half-size products instead of 8 (A = [A11 A12; A21 A22], B and C likewise):
+//   M1 = (A11+A22)(B11+B22) -> C11, C22     M2 = (A21+A22) B11 -> C21, -C22     M3 = A11 (B12-B22) -> C12, C22
+//   M4 = A22 (B21-B11) -> C11, C21          M5 = (A11+A12) B22 -> C12, -C11     M6 = (A21-A11)(B11+B12) -> C22
+//   M7 = (A12-A22)(B21+B22) -> C11
+// The k-loop of the GEMM is not touched: the ten operand sums are formed by two HBM-bound launches into scratch
+// (strassen_sums_kernel), the products are ordinary launches, and M1 .. M5 subtract themselves from both of their quadrants in
+// the epilogue (gemm_f64_dual_kernel) -- no product temporaries, no combine pass.  The launches run in this fixed order on the
+// caller's stream: the result is deterministic.  Error: a few eps more than the classical product (2e-15 against 9e-16
+// max-norm on random 512 x 512 x 1024 operands).
+static int launch_gemm_dual(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C1, double* C2,
+                            double s, int64_t ldc, int64_t m, int64_t n, int64_t k) {
+  GPX_ARG(m % 128 == 0 && n % 128 == 0 && k % KB == 0 && k > 0 && m > 0 && n > 0, "gemm: m,n must be multiples of 128 and k of 16");
+  GPX_ARG((lda % 2) == 0 && (ldb % 2) == 0, "gemm: leading dimensions must be even (16-byte loads)");
+  const double tiles128 = (double)(m / 128) * (double)(n / 128);
+  const int te = tiles128 < 1024.0 ? 64 : 128;   // as launch_gemm
+  const Plan p = make_plan(m, n, false, te);
+  GPX_ARG(p.wgs < ((int64_t)1 << 31), "gemm: grid too large");
+  const int nk = (int)(k / KB);
+  ProfScope ps(ctx, GPX_PROF_GEMM, 2.0 * (double)m * (double)n * (double)k, 0.0);
+  if (te == 64)
+    hipLaunchKernelGGL(gemm_f64_dual_kernel<64>, dim3((unsigned)p.wgs), dim3(256), 0, ctx->stream, A, lda, B, ldb, C1, C2, s, ldc,
+                       nk, p.tm, p.tn, p.sbc, p.sb_shift);
+  else
+    hipLaunchKernelGGL(gemm_f64_dual_kernel<128>, dim3((unsigned)p.wgs), dim3(256), 0, ctx->stream, A, lda, B, ldb, C1, C2, s, ldc,
+                       nk, p.tm, p.tn, p.sbc, p.sb_shift);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+static inline bool strassen_shape_ok(int64_t m, int64_t n, int64_t k) {
+  return m > 0 && n > 0 && k > 0 && m % 256 == 0 && n % 256 == 0 && k % 32 == 0;
+}
+
+// bytes of scratch one level needs: five sums of each operand (0 = the shape is refused)
+int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k) {
+  if (!strassen_shape_ok(m, n, k)) return 0;
+  const int64_t hm = m / 2, hn = n / 2, hk = k / 2;
+  return 5 * (hm * gpx_skew_ld(hk) + hk * gpx_skew_ld(hn)) * 8;
+}
+
+// Same contract as launch_gemm(..., bt = false, accumulate = true, lower = false).  m, n multiples of 256 and k of 32;
+// any other shape, or no scratch to be had, runs the classical product.  scratch (scratch_bytes >= gemm_strassen_scratch_bytes)
+// may be NULL: then it comes from the pool for this call, which ends with a synchronisation of the stream.
+int launch_gemm_strassen(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                         int64_t m, int64_t n, int64_t k, double* scratch, int64_t scratch_bytes) {
+  const int64_t need = gemm_strassen_scratch_bytes(m, n, k);
+  if (need == 0 || (lda % 2) != 0 || (ldb % 2) != 0 || C == A || C == B)
+    return launch_gemm(ctx, A, lda, B, ldb, C, ldc, m, n, k, false, true, false);
+  void* own = nullptr;
+  if (!scratch || scratch_bytes < need) {
+    if (gpx_dev_alloc(ctx, need, &own) != 0) {   // no new out-of-memory failure: the classical product needs no scratch
+      (void)hipGetLastError();
+      return launch_gemm(ctx, A, lda, B, ldb, C, ldc, m, n, k, false, true, false);
+    }
+    scratch = (double*)own;
+  }
+  const int64_t hm = m / 2, hn = n / 2, hk = k / 2, lsa = gpx_skew_ld(hk), lsb = gpx_skew_ld(hn);
+  const int64_t sa = hm * lsa, sb = hk * lsb;
+  double* const S = scratch;            // S[0..4]: A11+A22, A21+A22, A11+A12, A21-A11, A12-A22
+  double* const T = scratch + 5 * sa;   // T[0..4]: B11+B22, B12-B22, B21-B11, B11+B12, B21+B22
+  int r = 0;
+  do {
+    {
+      ProfScope ps(ctx, GPX_PROF_REDUCE, 5.0 * (double)hm * hk + 5.0 * (double)hk * hn, 72.0 * ((double)hm * hk + (double)hk * hn));
+      hipLaunchKernelGGL(strassen_sums_kernel<false>, dim3((unsigned)((hk / 2 + 255) / 256), (unsigned)(hm < 65535 ? hm : 65535)),
+                         dim3(256), 0, ctx->stream, A, lda, hm, hk, S, lsa, sa);
+      hipLaunchKernelGGL(strassen_sums_kernel<true>, dim3((unsigned)((hn / 2 + 255) / 256), (unsigned)(hk < 65535 ? hk : 65535)),
+                         dim3(256), 0, ctx->stream, B, ldb, hk, hn, T, lsb, sb);
+      if (hipGetLastError() != hipSuccess) {
+        gpx_set_error("strassen: operand-sum launch failed");
+        r = -2;
+        break;
+      }
+    }
+    const double *A11 = A, *A22 = A + hm * lda + hk, *B11 = B, *B22 = B + hk * ldb + hn;
+    double *C11 = C, *C12 = C + hn, *C21 = C + hm * ldc, *C22 = C + hm * ldc + hn;
+    if ((r = launch_gemm_dual(ctx, S, lsa, T, lsb, C11, C22, 1.0, ldc, hm, hn, hk)) != 0) break;                 // M1
+    if ((r = launch_gemm_dual(ctx, S + sa, lsa, B11, ldb, C21, C22, -1.0, ldc, hm, hn, hk)) != 0) break;         // M2
+    if ((r = launch_gemm_dual(ctx, A11, lda, T + sb, lsb, C12, C22, 1.0, ldc, hm, hn, hk)) != 0) break;          // M3
+    if ((r = launch_gemm_dual(ctx, A22, lda, T + 2 * sb, lsb, C11, C21, 1.0, ldc, hm, hn, hk)) != 0) break;      // M4
+    if ((r = launch_gemm_dual(ctx, S + 2 * sa, lsa, B22, ldb, C12, C11, -1.0, ldc, hm, hn, hk)) != 0) break;     // M5
+    if ((r = launch_gemm(ctx, S + 3 * sa, lsa, T + 3 * sb, lsb, C22, ldc, hm, hn, hk, false, true, false)) != 0) break;  // M6
+    if ((r = launch_gemm(ctx, S + 4 * sa, lsa, T + 4 * sb, lsb, C11, ldc, hm, hn, hk, false, true, false)) != 0) break;  // M7
+  } while (0);
+  if (own) {
+    (void)hipStreamSynchronize(ctx->stream);   // the sums go back to the pool
+    gpx_dev_release(ctx, own, need);
+  }
+  return r;
 }
 
 // A[lr0 : lr0+m, lc0 : lc0+n] (local matrix, rank (pr, pc) of a Pr x Pc grid, block size nb) -= the contributions of the nseg

@@ -248,6 +248,11 @@ int launch_gemm(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int
 
 int launch_gemm_tri(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
                     int64_t m, int64_t n, int64_t k, bool bt, bool accumulate, bool lower, int tri);
+// C -= A B (NN) through one level of Strassen's scheme: 7 half-size products, operand sums in scratch (gemm_f64.hip).  m, n
+// multiples of 256, k of 32; other shapes, or no scratch, run launch_gemm.  scratch may be NULL (pool + a stream synchronisation).
+int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k);
+int launch_gemm_strassen(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                         int64_t m, int64_t n, int64_t k, double* scratch, int64_t scratch_bytes);
 int launch_gemm_ksplit(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
                        int64_t m, int64_t n, int64_t k, bool lower, int64_t parts, double* P, bool assign = false);
 int launch_gemm_ksplit_small(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,

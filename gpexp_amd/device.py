@@ -754,3 +754,8 @@ def dbg_gemm_ksplit(ctx, A, B, Cm, mode, parts):
 
 def dbg_gemm(ctx, A, B, Cm, bt, accumulate, lower=False):
     check(ctx.lib.gpx_dbg_gemm(ctx.h, A.h, B.h, Cm.h, int(bt), int(accumulate), int(lower)))
+
+
+def dbg_gemm_strassen(ctx, A, B, Cm):
+    """Cm -= A B through the one-level Strassen driver of the left solve, whatever its size gate says."""
+    check(ctx.lib.gpx_dbg_gemm_strassen(ctx.h, A.h, B.h, Cm.h))

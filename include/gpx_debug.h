@@ -20,6 +20,10 @@ int gpx_dbg_gemm_tri(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* 
  * transposed): mode 0 = C -= A B^T on 128-tiles, 1 = the same on/below the diagonal tiles only (square C), 2 = C -= A B^T on
  * 64-tiles (the few-row products of gpx_refit_rows), 3 = C = A B^T on 64-tiles (C may alias A) */
 int gpx_dbg_gemm_ksplit(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C, int mode, int parts);
+/* C (m x n) -= A (m x k) B (k x n) through the Strassen driver of the left solve's large updates (one level: 7 half-size
+ * products), whatever its size gate and GPX_STRASSEN say: lets a test check the scheme at sizes a host can multiply.  Shapes
+ * the driver refuses (m, n not multiples of 256, k not of 32) run the classical product, bit for bit gpx_dbg_gemm(0, 1, 0). */
+int gpx_dbg_gemm_strassen(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C);
 /* GPX_CHAOS=<seed> in the environment at gpx_create (debug): every launch site holds its stream back by a random 0.1-3 ms with
  * probability 1/4; results must not change (a dependency between the context's streams that is only met by lucky timing would). */
 /* queues a kernel that spins for ~ms milliseconds (<= 500) on the selected stream: lets a test hold one stream back so that a
