@@ -159,6 +159,7 @@ _SIGS = {
     "gpx_profile_get": (C.c_int, [c_vp, C.c_int, c_ip, c_dp, c_dp, c_dp]),
     "gpx_dbg_gemm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int]),
     "gpx_dbg_gemm_strassen": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gpx_dbg_gemm_strassen_depth": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int]),
     "gpx_dbg_gemm_tri": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int]),
     "gpx_dbg_gemm_ksplit": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int]),
     "gpx_dbg_kfill_plan": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, C.POINTER(C.c_int), c_dp]),

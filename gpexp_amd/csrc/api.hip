@@ -1561,7 +1561,17 @@ int gpx_dbg_gemm_strassen(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_
   GPX_ARG(ctx && A && B && C, "NULL argument");
   const int64_t m = C->prows, n = C->pcols, k = A->pcols;
   GPX_ARG(A->prows == m && B->prows == k && B->pcols == n, "operand shapes");
-  GPX_TRY(launch_gemm_strassen(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, nullptr, 0));
+  GPX_TRY(launch_gemm_strassen(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, 1, nullptr, 0));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int gpx_dbg_gemm_strassen_depth(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C, int depth) {
+  GPX_ARG(ctx && A && B && C, "NULL argument");
+  GPX_ARG(depth >= 0 && depth <= GPX_STRASSEN_MAX_DEPTH, "strassen: depth out of range");
+  const int64_t m = C->prows, n = C->pcols, k = A->pcols;
+  GPX_ARG(A->prows == m && B->prows == k && B->pcols == n, "operand shapes");
+  GPX_TRY(launch_gemm_strassen(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, depth, nullptr, 0));
   GPX_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }

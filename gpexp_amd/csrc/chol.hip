@@ -9,6 +9,7 @@
 // keeps the read-modify-write traffic on C far below the HBM roof.  Leaves: one workgroup factors a 128x128 diagonal block in
 // LDS and also inverts it, so that all triangular solves against a leaf are GEMMs with the inverse.
 #include "gpx_internal.h"
+#include <algorithm>
 #include <math.h>
 #include <stdlib.h>
 #include <stddef.h>
@@ -1462,8 +1463,9 @@ struct PotrsPlan {
   const double* binv;       // [ceil(n/sib)][sib][sib]
   const double* binvT;
   double* part;             // colreduce partials
-  // left solve only (chol_trsm_left_oop): updates above the size gate run as one Strassen level out of this scratch
-  bool strassen = false;
+  // left solve only (chol_trsm_left_oop): updates above the size gates run as Strassen's scheme, at most this many levels
+  // deep, out of this scratch
+  int strassen = 0;
   double* sscr = nullptr;
   int64_t sscr_bytes = 0;
 };
@@ -1516,16 +1518,33 @@ static int potrs_bwd(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64_t b1, d
 // The largest updates run as ONE LEVEL OF STRASSEN'S SCHEME (launch_gemm_strassen: 7 half-size products for 8).  The levels of
 // this recursion carry N^2 M / 2, / 4, / 8 ... flops, and the half-size products of the first two levels at C4 are shapes the
 // GEMM runs at its full rate (K >= 4096); further down the right operand's sums -- all m columns wide at every level -- cost as
-// much as the eighth product saves.  Gate: rows and k of the update, columns of the right-hand side (GPX_STRASSEN=0: never).
+// much as the eighth product saves.  Gate: rows and k of the update, columns of the right-hand side.
+//
+// The top update (rows, k >= 16384) runs TWO LEVELS deep when the right-hand side is wide enough that the 49 quarter-size
+// products still fill the chip with 128-tiles for several rounds (k >= 4096 each): from 16384 columns on (measured at C4's
+// factor: 32768 columns -13.2 ms, 16384 -3.9 ms, 8192 +1.1 ms; two levels in the second-level updates too: -0.3 ms, noise;
+// three levels in the top update: +14.5 ms -- profiles/strassen2_ivar_ab.json).  The gate returns the depth; GPX_STRASSEN caps
+// it (0: classical everywhere, 1: one level wherever the first gate admits it).
 #ifndef GPX_STRASSEN_MIN_ROWS
 #define GPX_STRASSEN_MIN_ROWS 8192
 #endif
 #ifndef GPX_STRASSEN_MIN_COLS
 #define GPX_STRASSEN_MIN_COLS 4096
 #endif
-static inline bool strassen_gate(int64_t rows, int64_t cols, int64_t k) {
-  return rows >= GPX_STRASSEN_MIN_ROWS && k >= GPX_STRASSEN_MIN_ROWS && cols >= GPX_STRASSEN_MIN_COLS &&
-         gemm_strassen_scratch_bytes(rows, cols, k) > 0;
+#ifndef GPX_STRASSEN2_MIN_ROWS
+#define GPX_STRASSEN2_MIN_ROWS 16384
+#endif
+#ifndef GPX_STRASSEN2_MIN_COLS
+#define GPX_STRASSEN2_MIN_COLS 16384
+#endif
+static inline int strassen_gate(int64_t rows, int64_t cols, int64_t k) {
+  if (!(rows >= GPX_STRASSEN_MIN_ROWS && k >= GPX_STRASSEN_MIN_ROWS && cols >= GPX_STRASSEN_MIN_COLS &&
+        gemm_strassen_scratch_bytes(rows, cols, k, 1) > 0))
+    return 0;
+  if (!(rows >= GPX_STRASSEN2_MIN_ROWS && k >= GPX_STRASSEN2_MIN_ROWS && cols >= GPX_STRASSEN2_MIN_COLS &&
+        gemm_strassen_scratch_bytes(rows, cols, k, 2) > 0))
+    return 1;
+  return 2;
 }
 
 static int trsm_left_oop_rec(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64_t b1, double* B, int64_t ldb, double* W,
@@ -1538,9 +1557,10 @@ static int trsm_left_oop_rec(gpx_ctx* ctx, const PotrsPlan& P, int64_t b0, int64
   const int64_t mid = (b0 + b1) / 2;
   GPX_TRY(trsm_left_oop_rec(ctx, P, b0, mid, B, ldb, W, ldw, m));
   const int64_t r0 = blk_off(P, mid), r1 = blk_off(P, b1), c0 = blk_off(P, b0);
-  if (P.strassen && strassen_gate(r1 - r0, m, r0 - c0))
+  const int depth = P.strassen ? std::min(P.strassen, strassen_gate(r1 - r0, m, r0 - c0)) : 0;
+  if (depth > 0)
     GPX_TRY(launch_gemm_strassen(ctx, P.L + r0 * P.ld + c0, P.ld, W + c0 * ldw, ldw, B + r0 * ldb, ldb, r1 - r0, m, r0 - c0,
-                                 P.sscr, P.sscr_bytes));
+                                 depth, P.sscr, P.sscr_bytes));
   else
     GPX_TRY(launch_gemm(ctx, P.L + r0 * P.ld + c0, P.ld, W + c0 * ldw, ldw, B + r0 * ldb, ldb, r1 - r0, m, r0 - c0, false,
                         true, false));
@@ -1562,21 +1582,22 @@ int chol_trsm_left_oop(gpx_ctx* ctx, gpx_mat* Lm, double* B, int64_t ldb, double
   P.binvT = nullptr;
   P.part = nullptr;
   // Strassen scratch for the whole sweep: sized for the top-level update (the lower levels need less), taken from the pool
-  // once.  No scratch -> the classical sweep, as before.
+  // once -- for the depth the gate gives it, else for one level less.  No scratch -> the classical sweep, as before.
   void* ps = nullptr;
   int64_t sbytes = 0;
-  if (P.nblk >= 2 && env_i64("GPX_STRASSEN", 1) != 0) {
+  int depth = 0;
+  const int64_t max_depth = env_i64("GPX_STRASSEN", GPX_STRASSEN_MAX_DEPTH);
+  if (P.nblk >= 2 && max_depth > 0) {
     const int64_t r0 = blk_off(P, P.nblk / 2);
-    if (strassen_gate(P.n - r0, m, r0)) {
-      // (the top-level update is the largest in rows x k; an uneven split further down can only be smaller in both)
-      sbytes = gemm_strassen_scratch_bytes(P.n - r0, m, r0);
-      if (gpx_dev_alloc(ctx, sbytes, &ps) != 0) {
-        (void)hipGetLastError();
-        ps = nullptr;
-      }
+    // (the top-level update is the largest in rows x k; an uneven split further down can only be smaller in both)
+    for (depth = (int)std::min<int64_t>(max_depth, strassen_gate(P.n - r0, m, r0)); depth > 0; --depth) {
+      sbytes = gemm_strassen_scratch_bytes(P.n - r0, m, r0, depth);
+      if (sbytes > 0 && gpx_dev_alloc(ctx, sbytes, &ps) == 0) break;
+      (void)hipGetLastError();
+      ps = nullptr;
     }
   }
-  P.strassen = ps != nullptr;
+  P.strassen = ps ? depth : 0;
   P.sscr = (double*)ps;
   P.sscr_bytes = sbytes;
   const int r = trsm_left_oop_rec(ctx, P, 0, P.nblk, B, ldb, W, ldw, m);

@@ -117,11 +117,24 @@ struct NoSeg {
 // single-destination instantiations compile to exactly the code they had before.
 struct NoDual {
   static constexpr bool on = false;
+  static constexpr bool multi = false;
 };
 struct Dual {
   static constexpr bool on = true;
+  static constexpr bool multi = false;
   double* c2;
   double s;
+};
+// SEVERAL destinations (EPI::multi): C_d -= s_d * acc for d < nd <= GPX_MULTI_MAX, s_d = +-1 (exact), every C_d with C's row
+// stride and all of them distinct memory.  A product of the inner level of a nested Strassen scheme belongs into up to two inner
+// quadrants of up to two outer quadrants (four destinations at depth 2).  The destinations are processed one after the other: no
+// more live registers than Dual.
+constexpr int GPX_MULTI_MAX = 1 << GPX_STRASSEN_MAX_DEPTH;
+struct Multi {
+  static constexpr bool multi = true;
+  double* c[GPX_MULTI_MAX];
+  double s[GPX_MULTI_MAX];
+  int nd;
 };
 
 // (Variants measured and dropped: a 2-deep register prefetch; reading only two k-substeps' fragments at a time.)
@@ -360,7 +373,28 @@ __device__ __forceinline__ void gemm_tile(Smem<BT, TE>& sm, const double* A, int
 
   // epilogue: reg v of lane l -> C[(l>>4)+4v][l&15] within each 16x16 tile
   double* Cw = C + (m0 + wm * WS + fk) * ldc + n0 + wn * WS + fr;
-  if constexpr (EPI::on) {
+  if constexpr (EPI::multi) {
+    static_assert(ACC, "the multi-destination epilogue accumulates");
+    const int64_t coff = (m0 + wm * WS + fk) * ldc + n0 + wn * WS + fr;
+#pragma unroll
+    for (int d = 0; d < GPX_MULTI_MAX; ++d) {   // (unrolled: the destination table is read with constant indices)
+      if (d >= epi.nd) break;
+      double* const Cd = epi.c[d] + coff;
+      const double sd = epi.s[d];
+#pragma unroll
+      for (int i = 0; i < FI; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          double* cp = Cd + (int64_t)(i * 16 + 4 * v) * ldc;
+          double cv[FI];
+#pragma unroll
+          for (int j = 0; j < FI; ++j) cv[j] = cp[j * 16];
+#pragma unroll
+          for (int j = 0; j < FI; ++j) cp[j * 16] = cv[j] - sd * acc[i][j][v];
+        }
+    }
+    return;
+  } else if constexpr (EPI::on) {
     static_assert(ACC, "the two-destination epilogue accumulates");
     double* Cw2 = epi.c2 + (m0 + wm * WS + fk) * ldc + n0 + wn * WS + fr;
     const double s2 = epi.s;
@@ -470,6 +504,20 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_dual_kernel(const double* A, 
   int by, bx;
   if (!tile_of<false>((q >> sbs2) * 8 + xcd, q & ((1 << sbs2) - 1), tiles_m, tiles_n, sb_cols, sb_shift, &by, &bx, 0)) return;
   gemm_tile<false, true, TE, NoSeg, Dual>(sm, A, lda, B, ldb, C, ldc, nk, by, bx, NoSeg(), Dual{C2, s});
+}
+
+// NN accumulating product into several destinations (see Multi): the same map, no tail.
+template <int TE>
+__global__ __launch_bounds__(256, 2) void gemm_f64_multi_kernel(const double* A, int64_t lda, const double* B, int64_t ldb,
+                                                                const Multi dst, int64_t ldc, int nk, int tiles_m, int tiles_n,
+                                                                int sb_cols, int sb_shift) {
+  __shared__ Smem<false, TE> sm;
+  const int w = blockIdx.x;
+  const int xcd = w & 7, q = w >> 3;
+  const int sbs2 = 2 * sb_shift;
+  int by, bx;
+  if (!tile_of<false>((q >> sbs2) * 8 + xcd, q & ((1 << sbs2) - 1), tiles_m, tiles_n, sb_cols, sb_shift, &by, &bx, 0)) return;
+  gemm_tile<false, true, TE, NoSeg, Multi>(sm, A, lda, B, ldb, dst.c[0], ldc, nk, by, bx, NoSeg(), dst);
 }
 
 // Operand sums of one Strassen level: X (2 hr x 2 hc, row stride ldx) is read ONCE, quadrant by quadrant, and the five
@@ -854,7 +902,7 @@ int launch_gemm_tri(gpx_ctx* ctx, const double* A, int64_t lda, const double* B,
   return 0;
 }
 
-// ---- one level of Strassen's scheme for the large NN updates of the left solve ---------------------------------------------
+// ---- Strassen's scheme for the large NN updates of the left solve, one or more levels deep ---------------------------------
 // C -= A B with 7 half-size products instead of 8 (A = [A11 A12; A21 A22], B and C likewise):
 //   M1 = (A11+A22)(B11+B22) -> C11, C22     M2 = (A21+A22) B11 -> C21, -C22     M3 = A11 (B12-B22) -> C12, C22
 //   M4 = A22 (B21-B11) -> C11, C21          M5 = (A11+A12) B22 -> C12, -C11     M6 = (A21-A11)(B11+B12) -> C22
@@ -864,6 +912,12 @@ int launch_gemm_tri(gpx_ctx* ctx, const double* A, int64_t lda, const double* B,
 // the epilogue (gemm_f64_dual_kernel) -- no product temporaries, no combine pass.  The launches run in this fixed order on the
 // caller's stream: the result is deterministic.  Error: a few eps more than the classical product (2e-15 against 9e-16
 // max-norm on random 512 x 512 x 1024 operands).
+//
+// DEPTH > 1 applies the scheme again inside each of the seven products (49 quarter-size products for 64 at depth 2): a product
+// is handed the LIST of its destinations (matrix, sign); above the last level it forms the sums of ITS two operands -- raw
+// quadrants come from the caller's matrix, sums of the level above from scratch -- and hands each of its seven products the list
+// expanded by the table above (quadrant q of every destination, signs multiplied); at the last level a product is one launch:
+// the plain kernel for one destination, the dual kernel for two, gemm_f64_multi_kernel for more (four at depth 2).
 static int launch_gemm_dual(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C1, double* C2,
                             double s, int64_t ldc, int64_t m, int64_t n, int64_t k) {
   GPX_ARG(m % 128 == 0 && n % 128 == 0 && k % KB == 0 && k > 0 && m > 0 && n > 0, "gemm: m,n must be multiples of 128 and k of 16");
@@ -884,61 +938,146 @@ static int launch_gemm_dual(gpx_ctx* ctx, const double* A, int64_t lda, const do
   return 0;
 }
 
-static inline bool strassen_shape_ok(int64_t m, int64_t n, int64_t k) {
-  return m > 0 && n > 0 && k > 0 && m % 256 == 0 && n % 256 == 0 && k % 32 == 0;
+static int launch_gemm_multi(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, const Multi& dst,
+                             int64_t ldc, int64_t m, int64_t n, int64_t k) {
+  GPX_ARG(m % 128 == 0 && n % 128 == 0 && k % KB == 0 && k > 0 && m > 0 && n > 0, "gemm: m,n must be multiples of 128 and k of 16");
+  GPX_ARG((lda % 2) == 0 && (ldb % 2) == 0, "gemm: leading dimensions must be even (16-byte loads)");
+  GPX_ARG(dst.nd >= 1 && dst.nd <= GPX_MULTI_MAX, "gemm: bad destination count");
+  const double tiles128 = (double)(m / 128) * (double)(n / 128);
+  const int te = tiles128 < 1024.0 ? 64 : 128;   // as launch_gemm
+  const Plan p = make_plan(m, n, false, te);
+  GPX_ARG(p.wgs < ((int64_t)1 << 31), "gemm: grid too large");
+  const int nk = (int)(k / KB);
+  ProfScope ps(ctx, GPX_PROF_GEMM, 2.0 * (double)m * (double)n * (double)k, 0.0);
+  if (te == 64)
+    hipLaunchKernelGGL(gemm_f64_multi_kernel<64>, dim3((unsigned)p.wgs), dim3(256), 0, ctx->stream, A, lda, B, ldb, dst, ldc, nk,
+                       p.tm, p.tn, p.sbc, p.sb_shift);
+  else
+    hipLaunchKernelGGL(gemm_f64_multi_kernel<128>, dim3((unsigned)p.wgs), dim3(256), 0, ctx->stream, A, lda, B, ldb, dst, ldc, nk,
+                       p.tm, p.tn, p.sbc, p.sb_shift);
+  GPX_HIP(hipGetLastError());
+  return 0;
 }
 
-// bytes of scratch one level needs: five sums of each operand (0 = the shape is refused)
-int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k) {
-  if (!strassen_shape_ok(m, n, k)) return 0;
-  const int64_t hm = m / 2, hn = n / 2, hk = k / 2;
-  return 5 * (hm * gpx_skew_ld(hk) + hk * gpx_skew_ld(hn)) * 8;
+// depth levels need m, n multiples of 128 * 2^depth and k of 16 * 2^depth: the products of the last level are GEMM shapes
+static inline bool strassen_shape_ok(int64_t m, int64_t n, int64_t k, int depth) {
+  return depth >= 1 && depth <= GPX_STRASSEN_MAX_DEPTH && m > 0 && n > 0 && k > 0 && m % ((int64_t)128 << depth) == 0 &&
+         n % ((int64_t)128 << depth) == 0 && k % ((int64_t)KB << depth) == 0;
 }
 
-// Same contract as launch_gemm(..., bt = false, accumulate = true, lower = false).  m, n multiples of 256 and k of 32;
-// any other shape, or no scratch to be had, runs the classical product.  scratch (scratch_bytes >= gemm_strassen_scratch_bytes)
-// may be NULL: then it comes from the pool for this call, which ends with a synchronisation of the stream.
-int launch_gemm_strassen(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
-                         int64_t m, int64_t n, int64_t k, double* scratch, int64_t scratch_bytes) {
-  const int64_t need = gemm_strassen_scratch_bytes(m, n, k);
-  if (need == 0 || (lda % 2) != 0 || (ldb % 2) != 0 || C == A || C == B)
-    return launch_gemm(ctx, A, lda, B, ldb, C, ldc, m, n, k, false, true, false);
-  void* own = nullptr;
-  if (!scratch || scratch_bytes < need) {
-    if (gpx_dev_alloc(ctx, need, &own) != 0) {   // no new out-of-memory failure: the classical product needs no scratch
-      (void)hipGetLastError();
-      return launch_gemm(ctx, A, lda, B, ldb, C, ldc, m, n, k, false, true, false);
+// doubles of scratch one level holds: five sums of each operand
+static inline int64_t strassen_level_elems(int64_t hm, int64_t hn, int64_t hk) {
+  return 5 * (hm * gpx_skew_ld(hk) + hk * gpx_skew_ld(hn));
+}
+
+// bytes of scratch `depth` levels need (0 = the shape is refused at this depth): the sums of a level stay live while ONE of its
+// products runs its own level out of the block behind them; the seven products use that block in turn.
+int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k, int depth) {
+  if (!strassen_shape_ok(m, n, k, depth)) return 0;
+  int64_t elems = 0;
+  for (int d = 0; d < depth; ++d) {
+    m /= 2, n /= 2, k /= 2;
+    elems += strassen_level_elems(m, n, k);
+  }
+  return elems * 8;
+}
+
+namespace {
+struct SDest {   // one destination of a product: C_d -= s * (A B)
+  double* c;
+  double s;
+};
+// products M1 .. M7: operands (< 0: sum number -1-x of strassen_sums_kernel, else raw quadrant 0 = X11, 3 = X22) and the
+// quadrants of C (0 = C11, 1 = C12, 2 = C21, 3 = C22) they go to, with signs
+struct SProd {
+  int a, b, nq, q[2];
+  double s[2];
+};
+constexpr SProd kStrassen[7] = {
+    {-1, -1, 2, {0, 3}, {1.0, 1.0}},    // M1 = (A11+A22)(B11+B22)
+    {-2, 0, 2, {2, 3}, {1.0, -1.0}},    // M2 = (A21+A22) B11
+    {0, -2, 2, {1, 3}, {1.0, 1.0}},     // M3 = A11 (B12-B22)
+    {3, -3, 2, {0, 2}, {1.0, 1.0}},     // M4 = A22 (B21-B11)
+    {-3, 3, 2, {1, 0}, {1.0, -1.0}},    // M5 = (A11+A12) B22
+    {-4, -4, 1, {3, 0}, {1.0, 0.0}},    // M6 = (A21-A11)(B11+B12)
+    {-5, -5, 1, {0, 0}, {1.0, 0.0}},    // M7 = (A12-A22)(B21+B22)
+};
+}  // namespace
+
+// dst[0 .. nd) -= s_d * (A B), `depth` levels deep; scratch holds gemm_strassen_scratch_bytes(m, n, k, depth)
+static int strassen_rec(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, const SDest* dst, int nd,
+                        int64_t ldc, int64_t m, int64_t n, int64_t k, int depth, double* scratch) {
+  if (depth == 0) {
+    // distinct memory: quadrants of one grid of m x n blocks (outer quadrants differ, or inner quadrants differ)
+    for (int d = 1; d < nd; ++d)
+      for (int e = 0; e < d; ++e) GPX_ARG(dst[d].c != dst[e].c, "strassen: two destinations of one product coincide");
+    if (nd == 1 && dst[0].s == 1.0) return launch_gemm(ctx, A, lda, B, ldb, dst[0].c, ldc, m, n, k, false, true, false);
+    if (nd == 2 && dst[0].s == 1.0) return launch_gemm_dual(ctx, A, lda, B, ldb, dst[0].c, dst[1].c, dst[1].s, ldc, m, n, k);
+    GPX_ARG(nd >= 1 && nd <= GPX_MULTI_MAX, "strassen: too many destinations for one product");
+    Multi md;
+    for (int d = 0; d < GPX_MULTI_MAX; ++d) {
+      md.c[d] = d < nd ? dst[d].c : nullptr;
+      md.s[d] = d < nd ? dst[d].s : 0.0;
     }
-    scratch = (double*)own;
+    md.nd = nd;
+    return launch_gemm_multi(ctx, A, lda, B, ldb, md, ldc, m, n, k);
   }
   const int64_t hm = m / 2, hn = n / 2, hk = k / 2, lsa = gpx_skew_ld(hk), lsb = gpx_skew_ld(hn);
   const int64_t sa = hm * lsa, sb = hk * lsb;
   double* const S = scratch;            // S[0..4]: A11+A22, A21+A22, A11+A12, A21-A11, A12-A22
   double* const T = scratch + 5 * sa;   // T[0..4]: B11+B22, B12-B22, B21-B11, B11+B12, B21+B22
-  int r = 0;
-  do {
-    {
-      ProfScope ps(ctx, GPX_PROF_REDUCE, 5.0 * (double)hm * hk + 5.0 * (double)hk * hn, 72.0 * ((double)hm * hk + (double)hk * hn));
-      hipLaunchKernelGGL(strassen_sums_kernel<false>, dim3((unsigned)((hk / 2 + 255) / 256), (unsigned)(hm < 65535 ? hm : 65535)),
-                         dim3(256), 0, ctx->stream, A, lda, hm, hk, S, lsa, sa);
-      hipLaunchKernelGGL(strassen_sums_kernel<true>, dim3((unsigned)((hn / 2 + 255) / 256), (unsigned)(hk < 65535 ? hk : 65535)),
-                         dim3(256), 0, ctx->stream, B, ldb, hk, hn, T, lsb, sb);
-      if (hipGetLastError() != hipSuccess) {
-        gpx_set_error("strassen: operand-sum launch failed");
-        r = -2;
-        break;
-      }
+  double* const below = T + 5 * sb;     // the levels below
+  {
+    ProfScope ps(ctx, GPX_PROF_REDUCE, 5.0 * (double)hm * hk + 5.0 * (double)hk * hn, 72.0 * ((double)hm * hk + (double)hk * hn));
+    hipLaunchKernelGGL(strassen_sums_kernel<false>, dim3((unsigned)((hk / 2 + 255) / 256), (unsigned)(hm < 65535 ? hm : 65535)),
+                       dim3(256), 0, ctx->stream, A, lda, hm, hk, S, lsa, sa);
+    hipLaunchKernelGGL(strassen_sums_kernel<true>, dim3((unsigned)((hn / 2 + 255) / 256), (unsigned)(hk < 65535 ? hk : 65535)),
+                       dim3(256), 0, ctx->stream, B, ldb, hk, hn, T, lsb, sb);
+    if (hipGetLastError() != hipSuccess) {
+      gpx_set_error("strassen: operand-sum launch failed");
+      return -2;
     }
-    const double *A11 = A, *A22 = A + hm * lda + hk, *B11 = B, *B22 = B + hk * ldb + hn;
-    double *C11 = C, *C12 = C + hn, *C21 = C + hm * ldc, *C22 = C + hm * ldc + hn;
-    if ((r = launch_gemm_dual(ctx, S, lsa, T, lsb, C11, C22, 1.0, ldc, hm, hn, hk)) != 0) break;                 // M1
-    if ((r = launch_gemm_dual(ctx, S + sa, lsa, B11, ldb, C21, C22, -1.0, ldc, hm, hn, hk)) != 0) break;         // M2
-    if ((r = launch_gemm_dual(ctx, A11, lda, T + sb, lsb, C12, C22, 1.0, ldc, hm, hn, hk)) != 0) break;          // M3
-    if ((r = launch_gemm_dual(ctx, A22, lda, T + 2 * sb, lsb, C11, C21, 1.0, ldc, hm, hn, hk)) != 0) break;      // M4
-    if ((r = launch_gemm_dual(ctx, S + 2 * sa, lsa, B22, ldb, C12, C11, -1.0, ldc, hm, hn, hk)) != 0) break;     // M5
-    if ((r = launch_gemm(ctx, S + 3 * sa, lsa, T + 3 * sb, lsb, C22, ldc, hm, hn, hk, false, true, false)) != 0) break;  // M6
-    if ((r = launch_gemm(ctx, S + 4 * sa, lsa, T + 4 * sb, lsb, C11, ldc, hm, hn, hk, false, true, false)) != 0) break;  // M7
-  } while (0);
+  }
+  const int64_t qoff[4] = {0, hn, hm * ldc, hm * ldc + hn};
+  for (const SProd& p : kStrassen) {
+    const double* Ap = p.a < 0 ? S + (-1 - p.a) * sa : (p.a == 0 ? A : A + hm * lda + hk);
+    const double* Bp = p.b < 0 ? T + (-1 - p.b) * sb : (p.b == 0 ? B : B + hk * ldb + hn);
+    SDest sub[GPX_MULTI_MAX];
+    int ns = 0;
+    for (int d = 0; d < nd; ++d)
+      for (int j = 0; j < p.nq; ++j) {
+        GPX_ARG(ns < GPX_MULTI_MAX, "strassen: too many destinations for one product");
+        sub[ns++] = SDest{dst[d].c + qoff[p.q[j]], dst[d].s * p.s[j]};
+      }
+    GPX_TRY(strassen_rec(ctx, Ap, p.a < 0 ? lsa : lda, Bp, p.b < 0 ? lsb : ldb, sub, ns, ldc, hm, hn, hk, depth - 1, below));
+  }
+  return 0;
+}
+
+// Same contract as launch_gemm(..., bt = false, accumulate = true, lower = false), up to `depth` levels deep: the deepest level
+// <= depth the shape admits (see strassen_shape_ok) and scratch can be had for; none -> the classical product.  scratch
+// (scratch_bytes >= gemm_strassen_scratch_bytes) may be NULL: then it comes from the pool for this call, which ends with a
+// synchronisation of the stream.
+int launch_gemm_strassen(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                         int64_t m, int64_t n, int64_t k, int depth, double* scratch, int64_t scratch_bytes) {
+  if (depth > GPX_STRASSEN_MAX_DEPTH) depth = GPX_STRASSEN_MAX_DEPTH;
+  if ((lda % 2) != 0 || (ldb % 2) != 0 || C == A || C == B) depth = 0;
+  void* own = nullptr;
+  int64_t need = 0;
+  for (; depth > 0; --depth) {
+    need = gemm_strassen_scratch_bytes(m, n, k, depth);
+    if (need == 0) continue;
+    if (scratch && scratch_bytes >= need) break;
+    if (gpx_dev_alloc(ctx, need, &own) == 0) {   // no new out-of-memory failure: the classical product needs no scratch
+      scratch = (double*)own;
+      break;
+    }
+    (void)hipGetLastError();
+    own = nullptr;
+  }
+  if (depth <= 0) return launch_gemm(ctx, A, lda, B, ldb, C, ldc, m, n, k, false, true, false);
+  const SDest top{C, 1.0};
+  const int r = strassen_rec(ctx, A, lda, B, ldb, &top, 1, ldc, m, n, k, depth, scratch);
   if (own) {
     (void)hipStreamSynchronize(ctx->stream);   // the sums go back to the pool
     gpx_dev_release(ctx, own, need);

@@ -248,11 +248,16 @@ int launch_gemm(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int
 
 int launch_gemm_tri(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
                     int64_t m, int64_t n, int64_t k, bool bt, bool accumulate, bool lower, int tri);
-// C -= A B (NN) through one level of Strassen's scheme: 7 half-size products, operand sums in scratch (gemm_f64.hip).  m, n
-// multiples of 256, k of 32; other shapes, or no scratch, run launch_gemm.  scratch may be NULL (pool + a stream synchronisation).
-int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k);
+// C -= A B (NN) through up to `depth` levels of Strassen's scheme: 7 half-size products per level, operand sums in scratch
+// (gemm_f64.hip).  depth levels need m, n multiples of 128 * 2^depth and k of 16 * 2^depth (gemm_strassen_scratch_bytes: 0 =
+// refused); the driver runs the deepest level <= depth that the shape admits and scratch can be had for, down to launch_gemm.
+// scratch may be NULL (pool + a stream synchronisation).
+// (a product of the last level has up to 2^depth destinations: gemm_f64_multi_kernel is built for 2^GPX_STRASSEN_MAX_DEPTH.  Three
+// levels in the top update at C4 were measured slower than two and than one, profiles/strassen2_ivar_ab.json.)
+constexpr int GPX_STRASSEN_MAX_DEPTH = 2;
+int64_t gemm_strassen_scratch_bytes(int64_t m, int64_t n, int64_t k, int depth);
 int launch_gemm_strassen(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
-                         int64_t m, int64_t n, int64_t k, double* scratch, int64_t scratch_bytes);
+                         int64_t m, int64_t n, int64_t k, int depth, double* scratch, int64_t scratch_bytes);
 int launch_gemm_ksplit(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
                        int64_t m, int64_t n, int64_t k, bool lower, int64_t parts, double* P, bool assign = false);
 int launch_gemm_ksplit_small(gpx_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,

@@ -759,3 +759,8 @@ def dbg_gemm(ctx, A, B, Cm, bt, accumulate, lower=False):
 def dbg_gemm_strassen(ctx, A, B, Cm):
     """Cm -= A B through the one-level Strassen driver of the left solve, whatever its size gate says."""
     check(ctx.lib.gpx_dbg_gemm_strassen(ctx.h, A.h, B.h, Cm.h))
+
+
+def dbg_gemm_strassen_depth(ctx, A, B, Cm, depth):
+    """Cm -= A B through the Strassen driver, up to `depth` levels deep (a shape a depth refuses runs one level less)."""
+    check(ctx.lib.gpx_dbg_gemm_strassen_depth(ctx.h, A.h, B.h, Cm.h, int(depth)))

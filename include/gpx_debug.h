@@ -24,6 +24,9 @@ int gpx_dbg_gemm_ksplit(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_ma
  * products), whatever its size gate and GPX_STRASSEN say: lets a test check the scheme at sizes a host can multiply.  Shapes
  * the driver refuses (m, n not multiples of 256, k not of 32) run the classical product, bit for bit gpx_dbg_gemm(0, 1, 0). */
 int gpx_dbg_gemm_strassen(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C);
+/* the same, up to `depth` levels deep (0 .. 2; depth levels need m, n multiples of 128 * 2^depth and k of 16 * 2^depth): a shape
+ * that depth refuses runs one level less, bit for bit, down to the classical product */
+int gpx_dbg_gemm_strassen_depth(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C, int depth);
 /* GPX_CHAOS=<seed> in the environment at gpx_create (debug): every launch site holds its stream back by a random 0.1-3 ms with
  * probability 1/4; results must not change (a dependency between the context's streams that is only met by lucky timing would). */
 /* queues a kernel that spins for ~ms milliseconds (<= 500) on the selected stream: lets a test hold one stream back so that a
