@@ -57,6 +57,36 @@ __device__ __forceinline__ ArgMin argmin_block(ArgMin v, double* sc, int64_t* si
   return ArgMin{sc[0], si[0]};
 }
 
+// cost of one candidate from its posterior mean and SIGNED variance -- the one formula of gpx_acq's epilogue and of the batch
+// selection's per-pick kernel.  a = dA/dmu, b = dA/dvar (NaN where var == 0 exactly).
+__device__ __forceinline__ double acq_cost(int acq, double param, double mu, double var, double* a_out, double* b_out) {
+  const double s = sqrt(fabs(var));
+  const double sg = var > 0.0 ? 1.0 : (var < 0.0 ? -1.0 : 0.0);
+  double c, a, b;
+  if (acq == GPX_ACQ_UCB) {
+    c = -(mu - param * s);
+    a = -1.0;
+    b = param * sg / (2.0 * s);
+  } else {
+    const double g = (param - mu) / s;
+    const double Phi = 0.5 * erfc(-g * M_SQRT1_2);
+    const double phi = exp(-0.5 * g * g) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
+    if (acq == GPX_ACQ_PI) {
+      c = -Phi;
+      a = phi / s;
+      b = phi * g * sg / (2.0 * s * s);
+    } else {
+      c = -s * (g * Phi + phi);
+      a = Phi;
+      b = -phi * sg / (2.0 * s);
+    }
+  }
+  if (var == 0.0) a = b = __builtin_nan("");
+  *a_out = a;
+  *b_out = b;
+  return c;
+}
+
 // values epilogue of one chunk [j0, j0 + mc): var = kd - ssq, the cost (written to cost[j0 + j]), the gradient coefficients
 // (a, b) per candidate of the chunk (coef, nullable) and one arg-min partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].
 __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double param, const double* __restrict__ mean,
@@ -69,29 +99,8 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double p
   const int64_t j = (int64_t)blockIdx.x * ACQ_EPI + threadIdx.x;
   ArgMin v{0.0, -1};
   if (j < mc) {
-    const double mu = mean[j], var = kd[j] - ssq[j];
-    const double s = sqrt(fabs(var));
-    const double sg = var > 0.0 ? 1.0 : (var < 0.0 ? -1.0 : 0.0);
-    double c, a, b;
-    if (acq == GPX_ACQ_UCB) {
-      c = -(mu - param * s);
-      a = -1.0;
-      b = param * sg / (2.0 * s);
-    } else {
-      const double g = (param - mu) / s;
-      const double Phi = 0.5 * erfc(-g * M_SQRT1_2);
-      const double phi = exp(-0.5 * g * g) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
-      if (acq == GPX_ACQ_PI) {
-        c = -Phi;
-        a = phi / s;
-        b = phi * g * sg / (2.0 * s * s);
-      } else {
-        c = -s * (g * Phi + phi);
-        a = Phi;
-        b = -phi * sg / (2.0 * s);
-      }
-    }
-    if (var == 0.0) a = b = __builtin_nan("");
+    double a, b;
+    const double c = acq_cost(acq, param, mean[j], kd[j] - ssq[j], &a, &b);
     cost[j0 + j] = c;
     if (coef) {
       coef[2 * j] = a;
@@ -341,6 +350,221 @@ int acq_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const g
   return gpx_kparams_sets(ctx, kp, X, Z);
 }
 
+// ---- q-point batch selection with resident state (gpx_acq_batch) ------------------------------------------------------------
+// Conditioning the model on one more (hallucinated) observation at candidate s is a rank-one change of everything the cost
+// needs.  State: W_C = L^-1 K(X, C) (np x Mp, resident), mu, v (signed variance), the rows U[t] of the earlier picks.  Per pick
+//     delta = v_s + noise,  y_s = mu_s (believer) or the caller's constant,
+//     u_j   = (k(c_s, c_j) - W_C[:, s]^T W_C[:, j] - sum_{r<t} U[r][s] U[r][j]) / sqrt(delta),   U[t] = u,
+//     mu_j += u_j (y_s - mu_s) / sqrt(delta),   v_j -= u_j^2,   param = max(param, y_s) when track_best
+// which is the posterior of the model refitted on X + picks, y + lies with the same scalar noise.  The only pass of size N x M is
+// the weighted column reduction h = W_C[:, s]^T W_C (launch_colreduce, fixed order); acq_batch_kernel does the rest in one pass
+// over the candidates.  A pivot with delta <= 1e-13 k(c_s, c_s) adds no information (greedy_row_kernel's rule): u = 0.
+
+// scalars of the current pick, written by acq_pick_kernel, read by acq_batch_kernel
+enum { SC_DELTA = 0, SC_MU = 1, SC_LIE = 2, SC_PARAM = 3, SC_LIVE = 4, SC_N = 8 };
+
+__global__ __launch_bounds__(256) void acq_batch_v_kernel(const double* __restrict__ kd, const double* __restrict__ ss, int64_t M,
+                                                          double* __restrict__ v) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < M) v[j] = kd[j] - ss[j];
+}
+
+// pick `cur` = candidate s: its column of W_C (w, np), its coordinates along the earlier picks (uc, cur), the pick's scalars,
+// and the mask.  Reads mu / v / U only: the state is changed by the NEXT acq_batch_kernel.
+__global__ __launch_bounds__(256) void acq_pick_kernel(const double* __restrict__ Wc, int64_t ld, int64_t np, int64_t s,
+                                                       const double* __restrict__ U, int64_t ldu, int cur,
+                                                       const double* __restrict__ mu, const double* __restrict__ v,
+                                                       const double* __restrict__ kd, double noise, int lie, double lie_value,
+                                                       int track_best, double* __restrict__ sc, double* __restrict__ uc,
+                                                       double* __restrict__ w, int* __restrict__ mask) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < np) w[i] = Wc[i * ld + s];
+  if (i < cur) uc[i] = U[i * ldu + s];
+  if (i == 0) {
+    const double delta = v[s] + noise, mus = mu[s];
+    const double ys = lie == GPX_LIE_BELIEVER ? mus : lie_value;
+    sc[SC_DELTA] = delta;
+    sc[SC_MU] = mus;
+    sc[SC_LIE] = ys;
+    if (track_best && ys > sc[SC_PARAM]) sc[SC_PARAM] = ys;
+    sc[SC_LIVE] = delta > 1e-13 * kd[s] ? 1.0 : 0.0;
+    mask[s] = 1;
+  }
+}
+
+// One pass over the candidates: (upd) condition mu, v on the pick `cur` = candidate s and store its row U[cur]; then the costs
+// under the mask (NaN for a picked candidate) and one arg-min partial per block.  Only j < M is touched: the padding columns of
+// W_C / U never enter a result.
+__global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq, const double* __restrict__ Cp, int64_t M,
+                                                            int upd, int64_t s, int cur, const double* __restrict__ sc,
+                                                            const double* __restrict__ uc, const double* __restrict__ hdot,
+                                                            double* __restrict__ U, int64_t ldu, double* __restrict__ mu,
+                                                            double* __restrict__ v, const int* __restrict__ mask,
+                                                            double* __restrict__ cost, double* __restrict__ part_c,
+                                                            int64_t* __restrict__ part_i) {
+  __shared__ double shc[ACQ_EPI];
+  __shared__ int64_t shi[ACQ_EPI];
+  const int64_t j = (int64_t)blockIdx.x * ACQ_EPI + threadIdx.x;
+  ArgMin best{0.0, -1};
+  if (j < M) {
+    double m = mu[j], var = v[j];
+    if (upd) {
+      double u = 0.0;
+      if (sc[SC_LIVE] != 0.0) {   // (uniform)
+        const double rs = 1.0 / sqrt(sc[SC_DELTA]);
+        double acc = kpair(kp, Cp + s * kp.d, Cp + j * kp.d) - hdot[j];
+        for (int r = 0; r < cur; ++r) acc = fma(-uc[r], U[(int64_t)r * ldu + j], acc);
+        u = acc * rs;
+        m = fma(u, (sc[SC_LIE] - sc[SC_MU]) * rs, m);
+        var = fma(-u, u, var);
+        mu[j] = m;
+        v[j] = var;
+      }
+      U[(int64_t)cur * ldu + j] = u;
+    }
+    double a, b;
+    double c = acq_cost(acq, sc[SC_PARAM], m, var, &a, &b);
+    if (mask[j]) c = __builtin_nan("");
+    cost[j] = c;
+    if (c == c) best = ArgMin{c, j};
+  }
+  const ArgMin r = argmin_block(best, shc, shi);
+  if (threadIdx.x == 0) {
+    part_c[blockIdx.x] = r.c;
+    part_i[blockIdx.x] = r.i;
+  }
+}
+
+int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Cm,
+                   double noise, int acq, double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx,
+                   double* out_cost, double* out_lie, double* all_costs) {
+  const int64_t n = L->rows, np = L->prows, M = Cm->rows, d = kp.d;
+  const int64_t Mp = gpx_round_up(M, GPX_TILE), ld = gpx_skew_ld(Mp);
+  // the solve of gpx_acq: in place below 2048 training points, above out of place through the block inverses, the cross matrix
+  // chunk by chunk into the resident W_C
+  const bool oop = np >= 2048;
+  const int64_t mcmax = gpx_round_up(gpx_eval_chunk(np), GPX_TILE);
+  const int64_t mcw = Mp < mcmax ? Mp : mcmax, ldb = gpx_skew_ld(mcw);
+  const int64_t bytesW = np * ld * 8, bytesB = oop ? np * ldb * 8 : 0, bytesU = q * Mp * 8, bytesM = Mp * 8;
+  const int64_t bytes_part = colreduce_partial_elems(np, Mp) * 8 + 8;
+  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+  const int64_t bytes_w = (np > q ? np : q) * 8;
+  void *pW = nullptr, *pB = nullptr, *pU = nullptr, *pal = nullptr, *pmu = nullptr, *pv = nullptr, *pkd = nullptr, *pss = nullptr;
+  void *ppart = nullptr, *pcost = nullptr, *ppc = nullptr, *ppi = nullptr, *pbc = nullptr, *pbi = nullptr, *psc = nullptr;
+  void *puc = nullptr, *pw = nullptr, *pmask = nullptr;
+  const dim3 gEpi((unsigned)nparts), gM((unsigned)((M + 255) / 256));
+  const dim3 gPick((unsigned)(((np > q ? np : q) + 255) / 256));
+  int r = 0;
+  do {
+    if ((r = gpx_dev_alloc(ctx, bytesW, &pW)) != 0) break;
+    if (oop && (r = gpx_dev_alloc(ctx, bytesB, &pB)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytesU, &pU)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, np * 8, &pal)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytesM, &pmu)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytesM, &pv)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytesM, &pkd)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytesM, &pss)) != 0) break;    // |W_C[:, j]|^2 at the set-up, then h of every pick
+    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, M * 8, &pcost)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppi)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, 8, &pbc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, 8, &pbi)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, SC_N * 8, &psc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, q * 8, &puc)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, bytes_w, &pw)) != 0) break;
+    if ((r = gpx_dev_alloc(ctx, Mp * 4, &pmask)) != 0) break;
+    double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
+    if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      r = -2;
+      break;
+    }
+    double *Wc = (double*)pW, *U = (double*)pU, *mu = (double*)pmu, *v = (double*)pv, *hd = (double*)pss;
+    // ---- set-up: gpx_acq's posterior pass, operation for operation, with W kept ----
+    for (int64_t j0 = 0; j0 < Mp && r == 0; j0 += mcw) {
+      const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
+      const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
+      double* B = oop ? (double*)pB : Wc + j0;
+      const int64_t ldc = oop ? gpx_skew_ld(mcp) : ld;
+      if ((r = launch_kfill(ctx, kp, X->p, n, Cm->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldc)) != 0) break;
+      if ((r = launch_colreduce(ctx, B, ldc, n, mcp, (const double*)pal, mu + j0, (double*)ppart)) != 0) break;
+      if (oop) r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldc, Wc + j0, ld, mcp);
+      else r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldc, np, mcp);
+    }
+    if (r != 0) break;
+    if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, (double*)ppart)) != 0) break;
+    if ((r = launch_kdiag(ctx, kp, Cm->p, M, (double*)pkd)) != 0) break;
+    hipLaunchKernelGGL(acq_batch_v_kernel, gM, dim3(256), 0, ctx->stream, (const double*)pkd, (const double*)hd, M, v);
+    if (hipGetLastError() != hipSuccess) {
+      r = -2;
+      break;
+    }
+    // ---- the picks ----
+    int64_t s = -1;
+    for (int64_t t = 0; t < q; ++t) {
+      {
+        ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
+        hipLaunchKernelGGL(acq_batch_kernel, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M, t > 0 ? 1 : 0,
+                           s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
+                           (const int*)pmask, (double*)pcost, (double*)ppc, (int64_t*)ppi);
+        hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                           (double*)pbc, (int64_t*)pbi);
+      }
+      double c = 0.0;
+      if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          (all_costs &&
+           hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+          hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        r = -2;
+        break;
+      }
+      if (s < 0 || s >= M) {
+        gpx_set_error("acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
+        r = -1;
+        break;
+      }
+      out_idx[t] = s;
+      if (out_cost) out_cost[t] = c;
+      if (t + 1 == q && !out_lie) break;
+      hipLaunchKernelGGL(acq_pick_kernel, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
+                         (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
+                         (double*)psc, (double*)puc, (double*)pw, (int*)pmask);
+      if (hipGetLastError() != hipSuccess ||
+          (out_lie && hipMemcpyAsync(out_lie + t, (double*)psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
+        r = -2;
+        break;
+      }
+      if (t + 1 == q) break;
+      if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, (const double*)pw, hd, (double*)ppart)) != 0) break;
+    }
+  } while (0);
+  (void)hipStreamSynchronize(ctx->stream);
+  if (pW) gpx_dev_release(ctx, pW, bytesW);
+  if (pB) gpx_dev_release(ctx, pB, bytesB);
+  if (pU) gpx_dev_release(ctx, pU, bytesU);
+  if (pal) gpx_dev_release(ctx, pal, np * 8);
+  if (pmu) gpx_dev_release(ctx, pmu, bytesM);
+  if (pv) gpx_dev_release(ctx, pv, bytesM);
+  if (pkd) gpx_dev_release(ctx, pkd, bytesM);
+  if (pss) gpx_dev_release(ctx, pss, bytesM);
+  if (ppart) gpx_dev_release(ctx, ppart, bytes_part);
+  if (pcost) gpx_dev_release(ctx, pcost, M * 8);
+  if (ppc) gpx_dev_release(ctx, ppc, nparts * 8);
+  if (ppi) gpx_dev_release(ctx, ppi, nparts * 8);
+  if (pbc) gpx_dev_release(ctx, pbc, 8);
+  if (pbi) gpx_dev_release(ctx, pbi, 8);
+  if (psc) gpx_dev_release(ctx, psc, SC_N * 8);
+  if (puc) gpx_dev_release(ctx, puc, q * 8);
+  if (pw) gpx_dev_release(ctx, pw, bytes_w);
+  if (pmask) gpx_dev_release(ctx, pmask, Mp * 4);
+  if (r == -2) gpx_set_error("acq batch: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -367,6 +591,20 @@ int gpx_acq_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
   GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, Z, acq, &kp));
   if (Z->rows == 0) return 0;
   return acq_impl(ctx, kp, L, X, alpha, Z, acq, param, cost, nullptr, nullptr, grad);
+}
+
+int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                  const double* alpha, const gpx_mat* C, double noise, int acq, double param, int track_best, int lie,
+                  double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs) {
+  GPX_ARG(out_idx != nullptr, "out_idx is NULL");
+  GPX_ARG(lie == GPX_LIE_BELIEVER || lie == GPX_LIE_CONSTANT, "lie must be GPX_LIE_BELIEVER or GPX_LIE_CONSTANT");
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, C, acq, &kp));
+  GPX_ARG(q >= 1, "need at least one pick");
+  GPX_ARG(q <= C->rows, "more picks than candidates");
+  GPX_ARG(noise >= 0.0, "noise variance must not be negative");
+  return acq_batch_impl(ctx, kp, L, X, alpha, C, noise, acq, param, track_best != 0, lie, lie_value, q, out_idx, out_cost, out_lie,
+                        all_costs);
 }
 
 }  // extern "C"

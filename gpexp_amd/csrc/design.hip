@@ -45,29 +45,6 @@ __global__ __launch_bounds__(256) void set_identity_kernel(double* __restrict__ 
   if (idx < n) A[idx * ld + idx] = 1.0;
 }
 
-// ---- covariance value for a pair of points given in global memory (generic d) -------------------------
-__device__ __forceinline__ double kpair(const KParams& kp, const double* __restrict__ a, const double* __restrict__ b) {
-  double acc = 0.0;
-  if (kp.kind == GPX_K_MEHLER) {
-    double pa = 0.0, pb = 0.0, cr = 0.0;
-    for (int k = 0; k < kp.d; ++k) {
-      const double x = a[k], y = b[k];
-      pa = fma(kp.c1[k] * x, x, pa);
-      pb = fma(kp.c1[k] * y, y, pb);
-      cr = fma(kp.c2[k] * x, y, cr);
-    }
-    return kp.sig * exp(-(pa + pb - cr));
-  }
-  for (int k = 0; k < kp.d; ++k) {
-    const double e = (a[k] - b[k]) * kp.scale[k];  // difference first, as the reference (kernels.py:121-122)
-    acc = fma(e, e, acc);
-  }
-  if (kp.kind == GPX_K_SE) return kp.sig * exp(-0.5 * acc);
-  const double t = sqrt(acc);
-  if (kp.kind == GPX_K_MATERN32) return kp.sig * (1.0 + t) * exp(-t);
-  return kp.sig * (1.0 + t + acc * (1.0 / 3.0)) * exp(-t);
-}
-
 // ---- greedy variance ---------------------------------------------------------------------------------------
 // One selection step.  sel[cur] holds the index s chosen for this step.  For every candidate c:
 //   w_c = (k(c_s, c) - sum_{t<cur} W[t][s] W[t][c]) / sqrt(d_s);  W[cur][c] = w_c;  d_out[c] = d_in[c] - w_c^2

@@ -86,6 +86,29 @@ struct KParams {
 };
 int gpx_make_kparams(int kind, int d, const double* hyp, int nhyp, KParams* out);
 
+// ---- covariance value for a pair of points given in global memory (generic d; design.hip, acq.hip) ----
+static __device__ __forceinline__ double kpair(const KParams& kp, const double* __restrict__ a, const double* __restrict__ b) {
+  double acc = 0.0;
+  if (kp.kind == GPX_K_MEHLER) {
+    double pa = 0.0, pb = 0.0, cr = 0.0;
+    for (int k = 0; k < kp.d; ++k) {
+      const double x = a[k], y = b[k];
+      pa = fma(kp.c1[k] * x, x, pa);
+      pb = fma(kp.c1[k] * y, y, pb);
+      cr = fma(kp.c2[k] * x, y, cr);
+    }
+    return kp.sig * exp(-(pa + pb - cr));
+  }
+  for (int k = 0; k < kp.d; ++k) {
+    const double e = (a[k] - b[k]) * kp.scale[k];  // difference first, as the reference (kernels.py:121-122)
+    acc = fma(e, e, acc);
+  }
+  if (kp.kind == GPX_K_SE) return kp.sig * exp(-0.5 * acc);
+  const double t = sqrt(acc);
+  if (kp.kind == GPX_K_MATERN32) return kp.sig * (1.0 + t) * exp(-t);
+  return kp.sig * (1.0 + t + acc * (1.0 / 3.0)) * exp(-t);
+}
+
 // ---- objects --------------------------------------------------------------------------------------
 struct gpx_mat {
   double* p;

@@ -459,6 +459,25 @@ def acq_grad(ctx, spec, L, X, alpha, Z, kind, param):
     return costs, grad
 
 
+LIE_BELIEVER, LIE_CONSTANT = 0, 1
+
+
+def acq_batch(ctx, spec, L, X, alpha, C, noise, kind, param, track_best, lie, lie_value, q, want_all=False):
+    """q picks of batch acquisition with resident state (gpx_acq_batch): every pick is scored on the model conditioned on the
+    earlier picks' believed values (lie: LIE_BELIEVER = the posterior mean at the pick, LIE_CONSTANT = lie_value).
+    (indices (q,) int64, winner costs (q,), believed values (q,)[, all costs q x M])."""
+    q = int(q)
+    idx = np.empty(max(q, 0), dtype=np.int64)
+    cost = np.empty(max(q, 0))
+    lies = np.empty(max(q, 0))
+    allc = np.empty((max(q, 0), C.shape[0])) if want_all else None
+    al = as_f64(alpha)
+    check(ctx.lib.gpx_acq_batch(ctx.h, *spec.args(), L.h, X.h, dptr(al), C.h, float(noise), int(kind), float(param),
+                                int(bool(track_best)), int(lie), float(lie_value), q, idx.ctypes.data_as(_lib.c_ip),
+                                dptr(cost), dptr(lies), dptr(allc)))
+    return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
+
+
 def greedy_ivar(ctx, spec, L, X, Cpts, Z, noise, nsel, want_all=False):
     """nsel picks of discrete greedy IVAR with resident state (gpx_greedy_ivar): (indices, winner costs[, all costs nsel x M])."""
     nsel = int(nsel)

@@ -533,6 +533,85 @@ class _costFuncBO(costFunctionBase):
         """(d,): the gradient of the cost of the last row."""
         return self.derivativeBatch(np.reshape(trainPoints[-1, :], (1, self.space.dimension)))[0]
 
+    def _trackBest(self):
+        """Whether a batch's believed values raise fBest from pick to pick -- what constructing the cost anew on the grown data
+        would do (`_fBest` is max(yTrain))."""
+        return True
+
+    def _lie(self, lie):
+        """(device lie kind, value) of selectBatch's `lie` argument."""
+        if isinstance(lie, str):
+            if lie == "believer":
+                return _dev.LIE_BELIEVER, 0.0
+            reducers = {"min": np.min, "max": np.max, "mean": np.mean}
+            if lie not in reducers:
+                raise ValueError("lie must be 'believer', 'min', 'max', 'mean' or a number, not %r" % (lie,))
+            return _dev.LIE_CONSTANT, float(reducers[lie](self.yTrain))
+        return _dev.LIE_CONSTANT, float(lie)
+
+    def selectBatch(self, candidates, nPoints, lie="believer", returnAllCosts=False):
+        """The next `nPoints` candidates to evaluate TOGETHER: the loop
+
+            for t in range(nPoints):
+                j, c = type(self)(gp, X_t, y_t, ...).bestCandidate(candidates)     # candidates picked before are skipped
+                X_t, y_t = vstack(X_t, candidates[j]), append(y_t, believed value at candidates[j])
+
+        without refitting (gpx_acq_batch: L^-1 K(X, candidates) stays on the device and every pick conditions the candidates' means
+        and variances by a rank-one update; the GP's scalar noise is used at the picked points).  `lie` is the value believed at a
+        pick: "believer" = the current posterior mean there (Kriging believer: means frozen, variances shrink), "min" / "max" /
+        "mean" of yTrain or a number (constant liar).  For PI, and for EI unless the constructor was given fBest=, fBest rises to
+        the largest believed value from pick to pick; kappa / a given fBest stay.
+
+        Returns (indices (nPoints,) int64, costs (nPoints,)): costs[t] is the winner's cost at pick t; with returnAllCosts=True also
+        allCosts (nPoints, M), row t = the costs pick t was chosen from (NaN at the candidates picked before).  Dense models only; the
+        cost object and its GP are not modified.  Under a multi-process launch the call runs replicated: every rank makes the same
+        deterministic single-GPU call on the factor."""
+        kindLie, lieValue = self._lie(lie)
+        q = int(nPoints)
+        ctx, gp, C = self._dense(candidates)
+        n, m = gp.pts.shape[0], C.shape[0]
+        if q > m:
+            raise ValueError("selectBatch: %d points asked of %d candidates" % (q, m))
+        spec, noise, param, track = gp.kernel._spec(), float(gp.noise), self._param(), self._trackBest()
+        if not hasattr(ctx, "_hbm_bytes"):
+            ctx._hbm_bytes = ctx.info()["hbm_bytes"]
+        resident = 8.0 * (m + 128) * (n + q + 512)              # W_C, the picks' rows (+ padding)
+        transient = 8.0 * (m + 128) * (n + 512) if n >= 1920 else 0.0   # set-up: the cross matrix the out-of-place solve consumes
+        if resident + transient + 8.0 * n * n > 0.8 * ctx._hbm_bytes:
+            return self._selectBatchRefit(candidates, q, kindLie, lieValue, param, track, returnAllCosts)
+        out = _dev.acq_batch(ctx, spec, gp._L, gp._X, gp.coeff, C, noise, self._acq, param, track, kindLie, lieValue, q,
+                             want_all=returnAllCosts)
+        idx, costs, allc = out[0], out[1], (out[3] if returnAllCosts else None)
+        return (idx, costs, allc) if returnAllCosts else (idx, costs)
+
+    def _selectBatchRefit(self, candidates, q, kindLie, lieValue, param, track, returnAllCosts):
+        """selectBatch when the resident state does not fit beside the factor: the refit loop it replaces, with the existing calls
+        (gpx_acq chunks the candidates)."""
+        candidates = np.asarray(candidates, dtype=float)
+        ctx = _dev.context()
+        g2 = copy.copy(self.gaussianProcess)
+        X, y = np.array(self.xTrain, dtype=float, copy=True), np.array(self.yTrain, dtype=float, copy=True).ravel()
+        idx, costs, rows = [], [], []
+        for t in range(q):
+            if t > 0:
+                g2.train(X, y)
+            c = _dev.acq(ctx, g2.kernel._spec(), g2._L, g2._X, g2.coeff, _dev.points(ctx, candidates), self._acq, param)[2]
+            c[idx] = np.nan
+            j = firstMinIndex(c)
+            if j < 0:
+                raise _dev._lib.GpxError("selectBatch: pick %d of %d: no candidate has a non-NaN cost" % (t + 1, q))
+            believed = lieValue
+            if kindLie == _dev.LIE_BELIEVER:
+                believed = float(g2.evaluate(candidates[j:j + 1], compvar=0)[0])
+            idx.append(j)
+            costs.append(float(c[j]))
+            rows.append(c)
+            X, y = np.vstack((X, candidates[j:j + 1])), np.append(y, believed)
+            if track:
+                param = max(param, believed)
+        out = (np.array(idx, dtype=np.int64), np.array(costs))
+        return out + (np.array(rows),) if returnAllCosts else out
+
 
 class costFuncGPUCbound(_costFuncBO):
     """GP upper confidence bound, minimisation form: -(mu - kappa s), s = sqrt(|var|) (experimentalDesign.py:889-923).
@@ -549,6 +628,9 @@ class costFuncGPUCbound(_costFuncBO):
 
     def _param(self):
         return self.kappa
+
+    def _trackBest(self):
+        return False
 
     def evaluate(self, trainPoints):
         predMean, predstd = self._posterior(trainPoints)
@@ -589,6 +671,9 @@ class costFuncEI(_costFuncBO):
 
     def _fBest(self):
         return self.fBest if hasattr(self, 'fBest') else np.max(self.yTrain)
+
+    def _trackBest(self):
+        return not hasattr(self, 'fBest')      # a given fBest= is the caller's constant
 
     def evaluate(self, trainPoints):
         fBest = self._fBest()

@@ -212,6 +212,26 @@ int gpx_acq(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gp
 int gpx_acq_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                  const double* alpha, const gpx_mat* Z, int acq, double param, double* cost, double* grad);
 
+/* q-point batch selection (Kriging believer / constant liar): q candidates picked one after the other, each pick scored on the
+ * model CONDITIONED on the earlier picks' hallucinated observations -- the loop "cost = costFuncEI(gp, X_t, y_t); j = bestCandidate(C);
+ * append (c_j, lie)" without refitting.  Resident state W_C = L^-1 K(X, C) (N x M), mu_j = K(c_j, X) alpha,
+ * v_j = k(c_j, c_j) - |W_C[:, j]|^2 (signed, as gpx_posterior); `noise` is the model's scalar noise variance.  Pick t = 0 .. q-1:
+ *     cost_j = A(mu_j, |v_j|; param) as gpx_acq, NaN for the candidates already picked;  s = first arg-min among the non-NaN costs
+ *     delta  = v_s + noise;   y_s = mu_s (GPX_LIE_BELIEVER) or lie_value (GPX_LIE_CONSTANT)
+ *     u_j    = (k(c_s, c_j) - W_C[:, s]^T W_C[:, j] - sum_{r<t} U[r][s] U[r][j]) / sqrt(delta);   U[t] = u
+ *     mu_j  += u_j (y_s - mu_s) / sqrt(delta);   v_j -= u_j^2;   param = max(param, y_s) when track_best != 0
+ * i.e. pick by pick the posterior of the model refitted on X + picks, y + lies.  A pivot with delta <= 1e-13 k(c_s, c_s) is
+ * recorded and masked but conditions nothing (u = 0), as in gpx_greedy_var.  Per pick one pass over W_C (8 N M bytes), no refit,
+ * no N^2 solve; all reductions in a fixed order (two runs agree bit for bit).  Every kernel of gpx_acq is accepted.
+ * out_idx[q]; out_cost[q] (nullable) the winner's cost at each pick; out_lie[q] (nullable) the value believed at each pick;
+ * all_costs (q x M, nullable) row t = the costs pick t was chosen from.  q < 1 and q > M are argument errors; a pick at which every
+ * remaining cost is NaN fails with an error that names the pick. */
+enum gpx_acq_lie { GPX_LIE_BELIEVER = 0, GPX_LIE_CONSTANT = 1 };
+int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                  const double* alpha, const gpx_mat* C, double noise, int acq, double param, int track_best,
+                  int lie, double lie_value, int64_t q,
+                  int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs);
+
 /* ---- hyper-parameter gradient -------------------------------------------------------------------- */
 /* grad[k] = 1/2 tr((alpha alpha^T - K^-1) dK/d theta_k), theta = {hyp[0..nhyp-1], noise}; the noise entry is
  * the raw 1/2 tr(alpha alpha^T - K^-1) (the caller applies the reference's x 2*noise, gp.py:463-464).

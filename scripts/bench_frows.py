@@ -266,3 +266,34 @@ if want("acq"):
     _, t = best(composition)
     report("composition GP.evaluate(compvar=1) + NumPy", "what a user writes today on this library", size, t,
            flops=1.0 * Na * Na * Ma)
+    # q-point batch selection (selectBatch -> gpx_acq_batch) against the refit loop it replaces, half of Za, 16 picks
+    Mb, qb = Ma // 2, 16
+    Zb = Za[:Mb]
+    sizeb = dict(N=Na, d=8, M=Mb, q=qb, kernel="Matern-5/2", acq="EI", lie="believer")
+    cf.selectBatch(Zb, 2)
+    _, t_one = best(lambda: cf.selectBatch(Zb, 1))
+    _, t_all = best(lambda: cf.selectBatch(Zb, qb))
+    _, t_bc = best(lambda: cf.bestCandidate(Zb))
+    t_pick = (t_all - t_one) / (qb - 1)
+    report("gpx_acq_batch set-up (selectBatch, 1 pick)", "costFuncEI(...) + bestCandidate, the first pass of the loop", sizeb, t_one,
+           flops=1.0 * Na * Na * Mb, note="the posterior pass of gpx_acq with W_C = L^-1 K(X, C) kept; bestCandidate alone on the same "
+           "candidates: %.2f ms; %d picks in one call: %.2f ms" % (1e3 * t_bc, qb, 1e3 * t_all))
+    report("gpx_acq_batch per pick", "refit on the grown data + bestCandidate per pick", sizeb, t_pick, nbytes=8.0 * Na * Mb,
+           note="(time of %d picks - time of 1 pick) / %d: one weighted column reduction over W_C + one fused pass over the "
+                "candidates per pick" % (qb, qb - 1))
+
+    def refit_loop(picks):
+        Xt, yt, out = Xa, ya, []
+        for _ in range(picks):
+            c = costFuncEI(GP(KernelIsoMatern(1.5, 1.0, 8, nu=2.5), 1e-2), Xt, yt, 2, _Space())
+            j, _ = c.bestCandidate(Zb)                      # (masking the earlier picks is host index work: left out of the timing)
+            mu = c.gaussianProcess.evaluate(Zb[j:j + 1])
+            Xt, yt = np.vstack((Xt, Zb[j:j + 1])), np.append(yt, mu)
+            out.append(j)
+        return out
+
+    _, t = best(lambda: refit_loop(2))
+    report("refit loop per pick (costFuncEI + bestCandidate)", "what a user writes today for a batch", sizeb, t / 2,
+           flops=1.0 * Na * Na * Mb + Na ** 3 / 3.0,
+           note="2 picks timed, per pick: one factorisation + the forward solve over all candidates; gpx_acq_batch per pick is "
+                "%.1f x below it" % (t / 2 / t_pick))
