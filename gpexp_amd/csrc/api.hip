@@ -220,16 +220,24 @@ int gpx_make_kparams(int kind, int d, const double* hyp, int nhyp, KParams* kp) 
 }
 
 // ---- point-set bounding boxes, centring and the exact-path decision (see KParams) -----------------------
+// Also records the first non-finite coordinate (bad_row / bad_col, -1 = none): the comparisons below skip a NaN, and the fill
+// kernels' clamps (v_max_f64 returns its non-NaN operand) would turn it into a covariance of exactly 0 -- gpx_kparams_sets
+// refuses such a set instead, at no cost to the kernels.
 static void bbox_from_host(gpx_mat* m, const double* src, int64_t rows, int64_t cols, int64_t ld) {
   m->bbox_ok = 0;
+  m->bad_row = m->bad_col = -1;
   if (cols < 1 || cols > GPX_MAXD || rows < 1) return;
   for (int64_t k = 0; k < cols; ++k) m->lo[k] = m->hi[k] = src[k];
-  for (int64_t i = 1; i < rows; ++i) {
+  for (int64_t i = 0; i < rows; ++i) {
     const double* r = src + i * ld;
     for (int64_t k = 0; k < cols; ++k) {
       const double v = r[k];
       if (v < m->lo[k]) m->lo[k] = v;
       if (v > m->hi[k]) m->hi[k] = v;
+      if (!(fabs(v) <= 1.79769313486231570815e308) && m->bad_row < 0) {  // NaN or +-inf
+        m->bad_row = i;
+        m->bad_col = k;
+      }
     }
   }
   m->bbox_ok = 1;
@@ -252,6 +260,10 @@ static int mat_bbox(gpx_ctx* ctx, const gpx_mat* cm) {
 // the sharded greedy-IVAR state differed from the single-rank one in the last bits, enough to flip a near-tie)
 extern "C" int gpx_points_set_box(gpx_ctx* ctx, gpx_mat* P, const double* lo, const double* hi, int d) {
   GPX_ARG(ctx && P && lo && hi && d >= 1 && d <= GPX_MAXD && P->cols == d, "points_set_box: bad arguments");
+  // the box is the caller's; the scan for non-finite coordinates (bad_row) is still of P's own rows.  Free for a set uploaded
+  // from the host (scanned at upload: all gpexp_amd/device.py does); a set last written on the device pays one copy to the
+  // host and a stream synchronisation here, as it would in the first fill it enters.
+  GPX_TRY(mat_bbox(ctx, P));
   for (int k = 0; k < d; ++k) {
     GPX_ARG(lo[k] <= hi[k], "points_set_box: empty box");
     P->lo[k] = lo[k];
@@ -262,7 +274,8 @@ extern "C" int gpx_points_set_box(gpx_ctx* ctx, gpx_mat* P, const double* lo, co
 }
 
 // S * sensitivity above which the expanded-form distance would cost more than ~2e-14 of relative kernel error
-// (measured: 7.6e-15 at S*sens = 75); sensitivity = max |dk/ds| / sig: 1/2 for SE and Matern-3/2, 1/6 for Matern-5/2
+// (measured: 7.6e-15 at S*sens = 75, 5.8e-15 at 119: tests/test_gpu_kfill_accuracy.py, family d);
+// sensitivity = max |dk/ds| / sig: 1/2 for SE and Matern-3/2, 1/6 for Matern-5/2
 static double exact_threshold() {
   const char* e = getenv("GPX_EXACT_S");  // read per call: the tests force either path on the same data
   return e ? atof(e) : 120.0;
@@ -271,24 +284,29 @@ static double exact_threshold() {
 int gpx_kparams_sets(gpx_ctx* ctx, KParams* kp, const gpx_mat* A, const gpx_mat* B, const gpx_mat* C) {
   for (int k = 0; k < GPX_MAXD; ++k) kp->center[k] = 0.0;
   kp->exact = 0;
-  if (kp->kind == GPX_K_MEHLER) return 0;
   const gpx_mat* sets[3] = {A, B, C};
   double lo[GPX_MAXD], hi[GPX_MAXD];
   bool any = false;
   for (const gpx_mat* s : sets) {
     if (!s || s->rows < 1) continue;
     GPX_TRY(mat_bbox(ctx, s));
+    if (s->bad_row >= 0) {  // every kind, Mehler included (include/gpx.h, gpx_kfill)
+      gpx_set_error("point set has a non-finite coordinate (NaN or infinity) at row %lld, column %lld",
+                    (long long)s->bad_row, (long long)s->bad_col);
+      return -1;
+    }
+    if (kp->kind == GPX_K_MEHLER) continue;
     for (int k = 0; k < kp->d; ++k) {
       if (!any || s->lo[k] < lo[k]) lo[k] = s->lo[k];
       if (!any || s->hi[k] > hi[k]) hi[k] = s->hi[k];
     }
     any = true;
   }
-  if (!any) return 0;
+  if (!any || kp->kind == GPX_K_MEHLER) return 0;
   double S = 0.0;
   for (int k = 0; k < kp->d; ++k) {
     const double c = 0.5 * lo[k] + 0.5 * hi[k];
-    kp->center[k] = (c == c && fabs(c) < 1e300) ? c : 0.0;  // non-finite inputs: leave them to the kernel
+    kp->center[k] = fabs(c) < 1e300 ? c : 0.0;  // finite inputs whose midpoint would overflow the centred squares
     const double hw = (hi[k] - kp->center[k]) * kp->scale[k];
     S += 2.0 * hw * hw;  // both operands of a pair may sit at the edge of the box
   }
@@ -328,6 +346,7 @@ int gpx_mat_new(gpx_ctx* ctx, int64_t rows, int64_t cols, int pad, gpx_mat** out
   m->aux_bytes = 0;
   m->factored = 0;
   m->bbox_ok = 0;
+  m->bad_row = m->bad_col = -1;
   m->binv = nullptr;
   m->binv_bytes = 0;
   m->binv_ib = 0;
@@ -674,6 +693,8 @@ int gpx_mat_clone(gpx_ctx* ctx, const gpx_mat* src, gpx_mat** out) {
   }
   m->factored = src->factored;
   m->bbox_ok = src->bbox_ok;
+  m->bad_row = src->bad_row;
+  m->bad_col = src->bad_col;
   for (int k = 0; k < GPX_MAXD; ++k) {
     m->lo[k] = src->lo[k];
     m->hi[k] = src->hi[k];

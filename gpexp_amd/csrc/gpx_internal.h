@@ -122,6 +122,7 @@ struct gpx_mat {
   // bounding box of a point set (cols <= GPX_MAXD), computed on the host at upload (gpx_mat_from_host) or on first use
   int bbox_ok;
   double lo[GPX_MAXD], hi[GPX_MAXD];
+  int64_t bad_row, bad_col;  // first non-finite coordinate seen by that scan, -1 = none (valid while bbox_ok)
   // explicit inverses of the IB x IB diagonal blocks of the factor (and their transposes), built on the first gpx_potrs
   // after a factorisation (chol_potrs): ceil(prows / IB) blocks of IB x IB each, twice
   double* binv;

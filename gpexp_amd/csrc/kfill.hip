@@ -19,9 +19,13 @@
 //     scaling, and fills whose centred, scaled domain is still wide take the EXACT variant, which forms
 //     (a_k - b_k) * scale_k from the raw coordinates on the VALU -- the reference's own order of operations
 //     (kernels.py:121-122) -- instead of the expanded product.
-//   * exp: argument clamped at -750, shifter-trick rounding + one-constant reduction to |r| <= ln2/512 + 256-entry
+//   * exp: argument clamped at -5e6, shifter-trick rounding + one-constant reduction to |r| <= ln2/512 + 256-entry
 //     2^(j/256) table in LDS + degree-4 polynomial (truncation 3.8e-17) + v_ldexp; sqrt: v_rsq_f64 (2^-23) + one coupled
-//     Newton step + residual correction.  Both stay within 2 ulp (tests: 1e-13 against the oracle / the reference).
+//     Newton step + residual correction.  Measured: sqrt stays within 1 ulp; exp within about 1.5 + 0.16 |x| units of 2^-52
+//     (2.8 at x = -9, 31 at -199, 108 at -707: the m * (C - ln2/256) of the one-constant reduction), which is below the effect
+//     of rounding its own argument (|x| * 2^-53 relative); results in the denormal range are rounded to the grid once.  Every
+//     entry is held to an element-wise bound built from these figures by tests/test_gpu_kfill_accuracy.py (the emulation
+//     that measured them: tests/test_kernel_reference_host.py).
 #include "gpx_internal.h"
 #include <math.h>
 #include <stdlib.h>
@@ -47,16 +51,23 @@ struct KCyclic { int nbt, Pr, pr, Pc, pc; };  // nbt = block size in tiles; 0 = 
 // 1.5*2^52 trick: the rounded integer is also the low dword of the shifted sum, so there is no v_rndne / v_cvt.  The
 // reduction uses ONE constant: the fma forms m*C exactly, so the only error is m * (C - ln2/256) <= |x| * 8e-17, below the
 // rounding of the argument itself.  The integer trick holds for |x| < 2^31 * ln2/256 = 5.8e6, so the argument is clamped
-// at -750 first (exp(-750) already underflows to 0; a point pair 1e5 length scales apart must give 0, not garbage from a
-// wrapped exponent).  10 fp64 ops + 4 integer ops.  (Rounds 1-2a used 64 entries and degree 5: one fma more per element --
-// the rectangular Matern fill is VALU-bound, profiles/r02_kfill_valu.txt.)
+// at -5e6 first: a point pair 1e5 length scales apart must give 0, not garbage from a wrapped exponent.  The clamp sits at
+// the far end of that range, not at -750 where exp alone underflows, because the factor f below is multiplied in before the
+// exponent is applied: 2^n with n = -7.2e6 takes EVERY finite f to 0, whereas f * exp(-750) with the Matern factor
+// f = 1 + t = 1e9 would have come out as 2e-317.  (f itself overflows from t = 1e154: include/gpx.h, gpx_kfill.)
+// 10 fp64 ops + 4 integer ops.  (Rounds 1-2a used 64 entries and degree 5: one fma more per element -- the rectangular
+// Matern fill is VALU-bound, profiles/r02_kfill_valu.txt.)
 constexpr int EXP_TAB = 256;
 __device__ __forceinline__ double vmax1(double a, double b);
 __device__ __forceinline__ double vmax1_neg(double a, double b);
+// The result is f * exp(x) with the factor f (sig, or sig times the Matern polynomial) multiplied in BEFORE the exponent is
+// applied: for normal results that is bit for bit f * ldexp(tj * p, n), and a result in the denormal range is rounded to the
+// denormal grid once, at the end -- f times an already denormal exp(x) carried half a grid step times f (373 steps for a
+// Matern-3/2 value at t = 745; found by the argument sweep of tests/test_gpu_kfill_accuracy.py).
 template <bool NEG = false>  // NEG: exp(-xin), the sign folded into the clamp's source modifier
-__device__ __forceinline__ double fast_exp(double xin, const double* __restrict__ tab) {
+__device__ __forceinline__ double fast_exp(double xin, double f, const double* __restrict__ tab) {
   const double SHIFT = 6755399441055744.0;                    // 1.5 * 2^52
-  const double x = NEG ? vmax1_neg(xin, -750.0) : vmax1(xin, -750.0);
+  const double x = NEG ? vmax1_neg(xin, -5.0e6) : vmax1(xin, -5.0e6);
   const double sh = fma(x, 369.3299304675746, SHIFT);          // 256 / ln 2
   const int mi = __double2loint(sh);
   const double m = sh - SHIFT;
@@ -67,7 +78,7 @@ __device__ __forceinline__ double fast_exp(double xin, const double* __restrict_
   p = fma(p, r, 0.5);
   p = fma(p, r, 1.0);
   p = fma(p, r, 1.0);
-  return ldexp(tj * p, mi >> 8);
+  return ldexp((tj * p) * f, mi >> 8);
 }
 
 // max(a, b) as ONE v_max_f64: fmax() compiles to a canonicalising v_max(a, a) in front of the real one (a comes out of the
@@ -104,16 +115,16 @@ __device__ __forceinline__ double fast_sqrt(double x) {  // DIST2_MIN <= x (clam
 template <int KIND>
 __device__ __forceinline__ double kvalue(double accin, double sig, double sig3, const double* __restrict__ tab) {
   if (KIND == GPX_K_SE) {
-    return sig * fast_exp(-0.5 * accin, tab);
+    return fast_exp(-0.5 * accin, sig, tab);
   } else if (KIND == GPX_K_MATERN32) {
     const double t = fast_sqrt(vmax1(accin, DIST2_MIN));
-    return fma(t, sig, sig) * fast_exp<true>(t, tab);
+    return fast_exp<true>(t, fma(t, sig, sig), tab);
   } else if (KIND == GPX_K_MATERN52) {
     const double acc = vmax1(accin, DIST2_MIN);
     const double t = fast_sqrt(acc);
-    return fma(acc, sig3, fma(t, sig, sig)) * fast_exp<true>(t, tab);
+    return fast_exp<true>(t, fma(acc, sig3, fma(t, sig, sig)), tab);
   } else {  // Mehler
-    return sig * fast_exp<true>(accin, tab);
+    return fast_exp<true>(accin, sig, tab);
   }
 }
 

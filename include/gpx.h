@@ -87,7 +87,16 @@ int gpx_mat_to_host(gpx_ctx* ctx, const gpx_mat* m, double* dst, int tri);
 /* K[i][j] = k(X_i, X_j) + nugget_i*delta_ij  (Z == NULL; N x N)      gp_kernel_utilities.py:34-68
  * K[i][j] = k(X_i, Z_j)                      (Z != NULL; N x M)      gp.py:132-135, 246-249;
  *                                                                    experimentalDesign.py:829-831
- * X, Z: device point sets (rows = points, cols = d).  nugget: host, nugget_len in {0,1,N}. */
+ * X, Z: device point sets (rows = points, cols = d).  nugget: host, nugget_len in {0,1,N}.
+ * Non-finite coordinates: a point set holding a NaN or an infinity is REFUSED (-1, the message names the first such row and
+ * column) by this and by every other entry point that assembles covariances between point sets.  The host looks while it
+ * computes the set's bounding box (at upload, or on first use after a device-side write); the fill kernels themselves do not
+ * check, and their clamps would turn a NaN coordinate into a covariance of exactly 0 -- which a fit would accept in silence.
+ * Matrices that are not point sets (y, K, ...) are not looked at.  gpx_kdiag and gpx_kernel_eval take no such decision:
+ * gpx_kernel_eval propagates NaN as libm does, gpx_kdiag of a stationary kind does not read the coordinates at all.
+ * Far pairs: a pair of finite points whose covariance is below half a denormal step comes out as exactly 0, however far apart
+ * (the exponent argument is clamped at -5e6 and 2^-7.2e6 takes any finite factor to 0) -- up to the point where the squared
+ * scaled distance or the Matern polynomial overflows a double (scaled distance ~1e154): beyond it the entry is inf or NaN. */
 int gpx_kfill(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp,
               const gpx_mat* X, const gpx_mat* Z, const double* nugget, int64_t nugget_len,
               gpx_mat** outK);
