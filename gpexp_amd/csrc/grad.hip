@@ -3,12 +3,17 @@
 // Replaces GP.evaluateVarianceDerivative (gp.py:282-341: an (N*d x M) matrix built from O(N*d) dense N x N products in
 // Python), GP.evaluateVarianceDerivWRTnewpt (gp.py:261-280) and costFunctionGP_IVAR.derivative (experimentalDesign.py:
 // 168-179: the column mean of the former), for the two kernels the reference differentiates: the squared exponential
-// (kernels.py:146-181) and the 1-D Mehler kernel (kernels.py:295-324), with or without a heteroscedastic noise model
-// (gp.py:314-320).  Nothing N x N ever goes to the host.
+// (kernels.py:146-181) and the 1-D Mehler kernel (kernels.py:295-324), and for the isotropic Matern kernels (nu = 3/2, 5/2),
+// which the reference does not differentiate -- with or without a heteroscedastic noise model (gp.py:314-320).  Nothing
+// N x N ever goes to the host.
 //
-// Notation: dk(u, p)[l] = d k(u, p) / d u_l in the REFERENCE's convention --
+// Notation: dk(u, p)[l] = d k(u, p) / d u_l in the REFERENCE's convention where it has one --
 //     SE        -s (u_l - p_l) / cl_l^2 * k(u, p)   with k already containing s: the doubled signalSize of kernels.py:177
 //     Mehler1D  -(t^2 u - t p) / (1 - t^2) * k(u, p)
+// -- and the TRUE derivative for Matern (as acq.hip; t = kp.scale |u - p|, kp.scale = sqrt(3) / rho or sqrt(5) / rho):
+//     Matern32  -s (3 / rho^2) e^-t (u_l - p_l)
+//     Matern52  -s (5 / (3 rho^2)) (1 + t) e^-t (u_l - p_l)
+// both smooth at u = p, where they vanish: nothing divides by |u - p|.
 // beta = K^-1 K(X, Z) (N x M, two triangular solves against the factor), nd[j][l] = d noise(x_j) / d x_jl (optional).
 // With c_jl[i] = dk(x_j, x_i)[l] + [x_i == x_j] nd[j][l]   (gp.py:310, 316: `indUse` marks coincident training points)
 // and  T_j[m][l] = -dk(z_m, x_j)[l]                        (gp.py:312)
@@ -45,6 +50,22 @@ __device__ __forceinline__ double kval(const KParams& kp, const double* __restri
 __device__ __forceinline__ double dk(const KParams& kp, double ul, double pl, int l, double kv) {
   if (kp.kind == GPX_K_MEHLER) return -(2.0 * kp.c1[l] * ul - kp.c2[l] * pl) * kv;
   return -kp.sig * (ul - pl) * kp.scale[l] * kp.scale[l] * kv;
+}
+
+// d k(u, p) / d u_l for a pair of points (the element-wise kernels below).  SE, Mehler: dk of kval, as before.  Matern: the
+// radial factor times the difference -- it is not a multiple of k(u, p), so it does not go through kval / dk.
+__device__ __forceinline__ double dkpair(const KParams& kp, const double* __restrict__ u, const double* __restrict__ p, int l) {
+  if (kp.kind == GPX_K_MATERN32 || kp.kind == GPX_K_MATERN52) {
+    double r2 = 0.0;
+    for (int k = 0; k < kp.d; ++k) {
+      const double e = (u[k] - p[k]) * kp.scale[k];
+      r2 = fma(e, e, r2);
+    }
+    const double t = sqrt(r2);
+    const double f = kp.kind == GPX_K_MATERN32 ? exp(-t) : (1.0 + t) * exp(-t) * (1.0 / 3.0);
+    return -kp.sig * kp.scale[l] * kp.scale[l] * f * (u[l] - p[l]);
+  }
+  return dk(kp, u[l], p[l], l, kval(kp, u, p));
 }
 
 // coincident training points: np.linalg.norm(pp - p) < 1e-10 (gp.py:308)
@@ -135,8 +156,13 @@ __global__ __launch_bounds__(256) void ivar_grad_row_kernel(KParams kp, const do
 // distance needs anyway, one exp and d fused multiply-adds -- instead of d derivative evaluations, which the generic kernels
 // above (kept for the Mehler kernel) unroll to GPX_MAXD = 32 predicated ones: 10.7 ms of gpx_ivar_grad's 120 at N = 8192,
 // M = 32768, d = 8 (3.4e8 pairs) against 1.3 ms of fp64 issue.  DMAX = d rounded up to a power of two.
-template <int DMAX>
-__device__ __forceinline__ double se_pair(const KParams& kp, const double* __restrict__ u, const double (&p)[DMAX],
+// The Matern derivatives have the same shape -- a radial factor times the difference (acq.hip) -- with one sqrt more per pair:
+//     KIND      radial_pair returns      radial_finish multiplies s_l by
+//     SE        s e^(-r2/2) = k(u, p)    -s scale_l^2
+//     Matern32  e^-t                     -s scale^2
+//     Matern52  (1 + t) e^-t             -s scale^2 / 3                   r2 = sum_l ((u_l - p_l) scale_l)^2, t = sqrt(r2)
+template <int KIND, int DMAX>
+__device__ __forceinline__ double radial_pair(const KParams& kp, const double* __restrict__ u, const double (&p)[DMAX],
                                           double (&diff)[DMAX]) {
   double r2 = 0.0;
 #pragma unroll
@@ -148,18 +174,21 @@ __device__ __forceinline__ double se_pair(const KParams& kp, const double* __res
       r2 = fma(e, e, r2);
     }
   }
-  return kp.sig * exp(-0.5 * r2);
+  if (KIND == GPX_K_SE) return kp.sig * exp(-0.5 * r2);
+  const double t = sqrt(r2);
+  return KIND == GPX_K_MATERN32 ? exp(-t) : (1.0 + t) * exp(-t);
 }
 
 // c_l * s_l for every coordinate, reduced over the workgroup in the fixed tree order, written to out[0 .. d)
-template <int DMAX>
-__device__ __forceinline__ void se_finish(const KParams& kp, const double (&s1)[DMAX], double extra_w, const double* extra,
+template <int KIND, int DMAX>
+__device__ __forceinline__ void radial_finish(const KParams& kp, const double (&s1)[DMAX], double extra_w, const double* extra,
                                           double scale_out, double* red, double* __restrict__ out) {
   const int t = threadIdx.x;
 #pragma unroll
   for (int l = 0; l < DMAX; ++l) {
     if (l < kp.d) {   // (uniform)
       double v = -kp.sig * kp.scale[l] * kp.scale[l] * s1[l];
+      if (KIND == GPX_K_MATERN52) v *= 1.0 / 3.0;
       if (extra) v += extra_w * extra[l];
       red[t] = v;
       __syncthreads();
@@ -173,8 +202,8 @@ __device__ __forceinline__ void se_finish(const KParams& kp, const double (&s1)[
   }
 }
 
-template <int DMAX>
-__global__ __launch_bounds__(256) void ivar_grad_row_se_kernel(KParams kp, const double* __restrict__ X, int64_t n,
+template <int KIND, int DMAX>
+__global__ __launch_bounds__(256) void ivar_grad_row_radial_kernel(KParams kp, const double* __restrict__ X, int64_t n,
                                                                const double* __restrict__ Z, int64_t m,
                                                                const double* __restrict__ Bm, int64_t ldb,
                                                                const double* __restrict__ S, int64_t lds_,
@@ -195,7 +224,7 @@ __global__ __launch_bounds__(256) void ivar_grad_row_se_kernel(KParams kp, const
   }
   // evaluation points: 2 beta[a][j] dk(z_j, x_a)
   for (int64_t j = t; j < m; j += 256) {
-    const double w = 2.0 * Bm[a * ldb + j] * se_pair<DMAX>(kp, Z + j * d, xa, diff);
+    const double w = 2.0 * Bm[a * ldb + j] * radial_pair<KIND, DMAX>(kp, Z + j * d, xa, diff);
 #pragma unroll
     for (int l = 0; l < DMAX; ++l) s1[l] = fma(w, diff[l], s1[l]);
   }
@@ -203,7 +232,7 @@ __global__ __launch_bounds__(256) void ivar_grad_row_se_kernel(KParams kp, const
   double dups = 0.0;
   for (int64_t i = t; i < n; i += 256) {
     const double sai = (i == a ? 1.0 : 2.0) * S[a * lds_ + i];
-    const double w = sai * se_pair<DMAX>(kp, X + i * d, xa, diff);
+    const double w = sai * radial_pair<KIND, DMAX>(kp, X + i * d, xa, diff);
 #pragma unroll
     for (int l = 0; l < DMAX; ++l) s1[l] = fma(-w, diff[l], s1[l]);
     if (nd != nullptr) {
@@ -213,12 +242,12 @@ __global__ __launch_bounds__(256) void ivar_grad_row_se_kernel(KParams kp, const
       if (i == a || sqrt(q) < 1e-10) dups += sai;   // coincident training points (gp.py:308)
     }
   }
-  se_finish<DMAX>(kp, s1, dups, nd ? nd + a * d : nullptr, inv_m, red, grad + a * d);
+  radial_finish<KIND, DMAX>(kp, s1, dups, nd ? nd + a * d : nullptr, inv_m, red, grad + a * d);
 }
 
 // out[m][l] = -2 sum_j dk(z_m, x_j)[l] beta[j][m] from beta^T (row m contiguous over j): one workgroup per evaluation point
-template <int DMAX>
-__global__ __launch_bounds__(256) void var_grad_newpt_se_kernel(KParams kp, const double* __restrict__ X, int64_t n,
+template <int KIND, int DMAX>
+__global__ __launch_bounds__(256) void var_grad_newpt_radial_kernel(KParams kp, const double* __restrict__ X, int64_t n,
                                                                 const double* __restrict__ Z,
                                                                 const double* __restrict__ betaT, int64_t ldt, int64_t col0,
                                                                 double* __restrict__ out) {
@@ -232,11 +261,11 @@ __global__ __launch_bounds__(256) void var_grad_newpt_se_kernel(KParams kp, cons
     s1[l] = 0.0;
   }
   for (int64_t j = t; j < n; j += 256) {
-    const double w = -2.0 * betaT[mm * ldt + j] * se_pair<DMAX>(kp, X + j * d, zs, diff);   // diff = x_j - z = -(u - p)
+    const double w = -2.0 * betaT[mm * ldt + j] * radial_pair<KIND, DMAX>(kp, X + j * d, zs, diff);   // diff = x_j - z = -(u - p)
 #pragma unroll
     for (int l = 0; l < DMAX; ++l) s1[l] = fma(-w, diff[l], s1[l]);
   }
-  se_finish<DMAX>(kp, s1, 0.0, nullptr, 1.0, red, out + (col0 + mm) * d);
+  radial_finish<KIND, DMAX>(kp, s1, 0.0, nullptr, 1.0, red, out + (col0 + mm) * d);
 }
 
 // ---- full matrix: A_l[j][i] = c_jl[i] (np x np, zero outside the n x n block) ----------------------------------------
@@ -251,7 +280,7 @@ __global__ __launch_bounds__(256) void dcov_kernel(KParams kp, const double* __r
     const int d = kp.d;
     const double* xj = X + j * d;
     const double* xi = X + i * d;
-    v = dk(kp, xj[l], xi[l], l, kval(kp, xj, xi));
+    v = dkpair(kp, xj, xi, l);
     if (nd != nullptr && (i == j || same_point(xj, xi, d))) v += nd[j * d + l];
   }
   A[j * lda + i] = v;
@@ -272,7 +301,7 @@ __global__ __launch_bounds__(256) void var_grad_finish_kernel(KParams kp, const 
   const double* z = Z + mm * d;
   const double* xj = X + j * d;
   const double b = beta[j * ldb + mm];
-  double t2 = 2.0 * dk(kp, z[l], xj[l], l, kval(kp, z, xj));  // -2 T
+  double t2 = 2.0 * dkpair(kp, z, xj, l);                         // -2 T
   if (dkb) t2 += 2.0 * dkb[j * d + l];                          // gp.py:320: derivTotal[-1] -= noiseFunc.deriv(p)
   out[j * ldo + mm] = b * (t2 + 2.0 * Cl[j * ldb + mm] - A[j * lda + j] * b);
 }
@@ -336,12 +365,21 @@ struct Scratch {
   }
 };
 
+// CALL(KIND, DMAX) for a kernel whose derivative is a radial factor times the difference (SE, Matern 3/2, Matern 5/2), d rounded
+// up as GPX_SE_DISPATCH does it
+#define GPX_RADIAL_DISPATCH(kind_, d_, CALL)                               \
+  do {                                                                     \
+    if ((kind_) == GPX_K_SE) GPX_SE_DISPATCH(d_, CALL##_SE);               \
+    else if ((kind_) == GPX_K_MATERN32) GPX_SE_DISPATCH(d_, CALL##_M32);   \
+    else GPX_SE_DISPATCH(d_, CALL##_M52);                                  \
+  } while (0)
+
 int check_args(int kind, int d, const gpx_mat* L, const gpx_mat* X, const gpx_mat* Z, const gpx_fitc* fitc = nullptr) {
   GPX_ARG((L || fitc) && X && Z, "NULL argument");
   GPX_ARG(fitc || (L->factored && L->aux), "matrix has not been factored by gpx_potrf");
-  GPX_ARG(kind == GPX_K_SE || (kind == GPX_K_MEHLER && d == 1),
-          "point derivatives exist for the squared-exponential and the 1-D Mehler kernel only "
-          "(as in the reference: kernels.py:146-181, 295-324)");
+  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52 || (kind == GPX_K_MEHLER && d == 1),
+          "point derivatives exist for the squared-exponential, the Matern (nu = 3/2, 5/2) and the 1-D Mehler kernel only "
+          "(the reference's: kernels.py:146-181, 295-324; Matern: the true derivative)");
   GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
   GPX_ARG(X->rows == (fitc ? fitc_n(fitc) : L->rows) && Z->rows > 0, "X does not match the factor / no evaluation points");
   return 0;
@@ -506,11 +544,18 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   }
   {
     ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 8.0 * ((double)n * m + (double)n * n));
-    if (kind == GPX_K_SE) {
-#define GPX_CALL(DM_)                                                                                                        \
-  hipLaunchKernelGGL((ivar_grad_row_se_kernel<DM_>), dim3((unsigned)n), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, m,     \
-                     (const double*)W, mp, (const double*)pS, np, (const double*)d_nd, 1.0 / (double)m, (double*)pg, (int64_t)0)
-      GPX_SE_DISPATCH(d, GPX_CALL);
+    if (kind != GPX_K_MEHLER) {
+#define GPX_CALL(K_, DM_)                                                                                                     \
+  hipLaunchKernelGGL((ivar_grad_row_radial_kernel<K_, DM_>), dim3((unsigned)n), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, \
+                     m, (const double*)W, mp, (const double*)pS, np, (const double*)d_nd, 1.0 / (double)m, (double*)pg,       \
+                     (int64_t)0)
+#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
+#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
+#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
+      GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
+#undef GPX_CALL_M52
+#undef GPX_CALL_M32
+#undef GPX_CALL_SE
 #undef GPX_CALL
     } else {
       hipLaunchKernelGGL(ivar_grad_row_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, m,
@@ -525,7 +570,7 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
 
 // The gradient for the design points from r0 on ONLY -- the batch loop pins the earlier ones by equal bounds
 // (experimentalDesign.py:719-724), their entries are never used -- from the kept forward solve W = L^-1 K(X, Z), squared
-// exponential, homoscedastic.  With T the rows from r0 on:
+// exponential or Matern, homoscedastic.  With T the rows from r0 on:
 //     beta_T = L_TT^-T W_T                 (back substitution touches nothing above T:   (n - r0)^2 M flops)
 //     S_T    = beta_T beta^T = (beta_T W^T) L^-1          (one (n - r0) x N x M product + a few-row right solve)
 // and the row kernel for those rows: 2 (n - r0) N M flops where the full gradient needs the whole backward solve and the whole
@@ -534,7 +579,7 @@ int gpx_ivar_grad_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhy
                        const gpx_mat* Z, const gpx_mat* W, int64_t r0, double* grad) {
   GPX_ARG(ctx && grad && W, "NULL argument");
   GPX_TRY(check_args(kind, d, L, X, Z));
-  GPX_ARG(kind == GPX_K_SE, "ivar_grad_rows: squared-exponential kernel only");
+  GPX_ARG(kind != GPX_K_MEHLER, "ivar_grad_rows: squared-exponential and Matern kernels only");
   GPX_ARG(ctx->live_mats.count(W), "ivar_grad_rows: W is not a live matrix of this context");
   KParams kp;
   GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
@@ -573,10 +618,16 @@ int gpx_ivar_grad_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhy
   }
   {
     ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 8.0 * ((double)b * m + (double)b * n));
-#define GPX_CALL(DM_)                                                                                                        \
-  hipLaunchKernelGGL((ivar_grad_row_se_kernel<DM_>), dim3((unsigned)b), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, m,     \
-                     (const double*)B, mp, (const double*)G, np, (const double*)nullptr, 1.0 / (double)m, (double*)pg, r0)
-    GPX_SE_DISPATCH(d, GPX_CALL);
+#define GPX_CALL(K_, DM_)                                                                                                     \
+  hipLaunchKernelGGL((ivar_grad_row_radial_kernel<K_, DM_>), dim3((unsigned)b), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, \
+                     m, (const double*)B, mp, (const double*)G, np, (const double*)nullptr, 1.0 / (double)m, (double*)pg, r0)
+#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
+#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
+#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
+    GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
+#undef GPX_CALL_M52
+#undef GPX_CALL_M32
+#undef GPX_CALL_SE
 #undef GPX_CALL
   }
   GPX_HIP(hipGetLastError());
@@ -689,13 +740,19 @@ static int var_grad_newpt_impl(gpx_ctx* ctx, int kind, int d, const double* hyp,
     const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
     const int64_t mcp = gpx_round_up(mc, GPX_TILE);
     double* beta;
-    if (kind == GPX_K_SE) {   // beta^T: row m contiguous over the training points, and no transpose back
+    if (kind != GPX_K_MEHLER) {   // beta^T: row m contiguous over the training points, and no transpose back
       GPX_TRY(solve_beta(ctx, kp, L, X, Z->p + j0 * d, mc, mcp, nullptr, (double*)pW, (double*)pWt, T, 1, &beta, nullptr, fitc,
                          (double*)pU));
-#define GPX_CALL(DM_)                                                                                                      \
-  hipLaunchKernelGGL((var_grad_newpt_se_kernel<DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p,     \
-                     (const double*)beta, np, j0, (double*)pO)
-      GPX_SE_DISPATCH(d, GPX_CALL);
+#define GPX_CALL(K_, DM_)                                                                                                    \
+  hipLaunchKernelGGL((var_grad_newpt_radial_kernel<K_, DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X->p, n,    \
+                     Z->p, (const double*)beta, np, j0, (double*)pO)
+#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
+#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
+#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
+      GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
+#undef GPX_CALL_M52
+#undef GPX_CALL_M32
+#undef GPX_CALL_SE
 #undef GPX_CALL
     } else {
       GPX_TRY(solve_beta(ctx, kp, L, X, Z->p + j0 * d, mc, mcp, nullptr, (double*)pW, (double*)pWt, T, 0, &beta, nullptr, fitc,

@@ -131,8 +131,8 @@ class costFunctionGP_IVAR(costFunctionBase):
     def derivative(self, inputPoints):
         """d IVAR / d design coordinates, flattened (experimentalDesign.py:168-179): gpx_ivar_grad --
         two triangular solves, one MFMA GEMM and a fused row reduction instead of the reference's (N*d x M) matrix --
-        for the kernels the reference differentiates (squared exponential, 1-D Mehler), with the heteroscedastic terms of
-        `space.noiseFunc` when there is one.  With `pinnedPoints` set (the batch driver: the leading points are fixed by equal
+        for the kernels the reference differentiates (squared exponential, 1-D Mehler: its convention, GP.varianceGradient) and
+        the isotropic Matern kernels (the true gradient), with the heteroscedastic terms of `space.noiseFunc` when there is one.  With `pinnedPoints` set (the batch driver: the leading points are fixed by equal
         bounds) the entries of the pinned points are returned as ZEROS -- not the full gradient."""
         gp = self.gaussianProcess
         nd = None
@@ -141,7 +141,7 @@ class costFunctionGP_IVAR(costFunctionBase):
         else:
             gp.addNodesAndComputeCovariance(inputPoints, noiseIn=self.space.noiseFunc(inputPoints))
             nd = np.asarray(self.space.noiseFunc.deriv(inputPoints), dtype=float).reshape(inputPoints.shape)
-        gp._point_derivative_ready(self.mcPoints)
+        gp._point_derivative_ready(self.mcPoints, referenceOnly=False)
         if gp._fitc is not None:
             # FITC model: the reference sums evaluateVarianceDerivative over the MC points (experimentalDesign.py:171-177), which
             # reads the Woodbury precision (gp.py:322); gpx_fitc_var_grad, then the same mean over the MC points
@@ -153,7 +153,7 @@ class costFunctionGP_IVAR(costFunctionBase):
         # the optimiser never uses their entries): the gradient of the free points alone from the kept solve -- gpx_ivar_grad_rows,
         # 2 (N - r0) N M flops instead of 2 N^2 M; the pinned entries are returned as zeros
         r0 = (int(getattr(self, "pinnedPoints", 0)) // 128) * 128
-        if W is not None and r0 > 0 and gp.kernel._spec().kind == _dev.K_SE:
+        if W is not None and r0 > 0 and gp.kernel._spec().kind != _dev.K_MEHLER:
             g = np.zeros(inputPoints.shape[0] * self.space.dimension)
             g[r0 * self.space.dimension:] = _dev.ivar_grad_rows(_dev.context(), gp.kernel._spec(), gp._L, gp._X, self._mc(), W, r0)
             return g

@@ -351,11 +351,16 @@ class GP:
         return var
 
     # ---- variance gradients w.r.t. point locations, on the device ---------------------------------------
-    def _point_derivative_ready(self, newpt):
+    def _point_derivative_ready(self, newpt, referenceOnly=True):
+        """Shape checks and the kernel gate of the point-derivative routines.  `referenceOnly` (the reference-named methods):
+        only the kernels whose `derivative` the reference defines; False (varianceGradient / varianceGradientWRTnewpt, the
+        IVAR gradient): also the kernels with a `pointDerivative` -- the isotropic Matern kernels."""
         assert self.pts is not None, "must specify training points before running this"
         assert newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
         if not self._has_factor() and self._fitc is None:
             raise NotImplementedError("variance derivatives need a fitted model")
+        if not referenceOnly and hasattr(self.kernel, "pointDerivative"):
+            return
         if not hasattr(self.kernel, "derivative") or (self.kernel._spec().kind == _dev.K_MEHLER
                                                       and self.kernel.dimension != 1):
             # the reference defines Kernel.derivative for the squared exponential and the 1-D Mehler kernel only
@@ -364,6 +369,9 @@ class GP:
     def evaluateVarianceDerivWRTnewpt(self, newpt):
         """d var(newpt_i) / d newpt_i, flattened (gp.py:261-280): gpx_var_grad_newpt."""
         self._point_derivative_ready(newpt)
+        return self._var_grad_newpt(newpt)
+
+    def _var_grad_newpt(self, newpt):
         ctx = _dev.context()
         if self._fitc is not None:    # the reference reads `precisionMatrix`: for FITC the Woodbury precision (gp.py:204-206)
             return self._fitc.var_grad_newpt(self.kernel._spec(), _dev.points(ctx, newpt))
@@ -376,6 +384,9 @@ class GP:
         points (gp.py:314-317) and, when the WHOLE evaluation set coincides with a training point, the terms of
         gp.py:318-320 (the reference tests `np.linalg.norm(p - newpt)`, a norm over all evaluation points)."""
         self._point_derivative_ready(newpt)
+        return self._var_grad(newpt, noiseFunc)
+
+    def _var_grad(self, newpt, noiseFunc):
         ctx = _dev.context()
         nd = eb = db = None
         if noiseFunc is not None:
@@ -389,6 +400,21 @@ class GP:
         if self._fitc is not None:
             return self._fitc.var_grad(self.kernel._spec(), _dev.points(ctx, newpt), nd, eb, db)
         return _dev.var_grad(ctx, self.kernel._spec(), self._L, self._X, _dev.points(ctx, newpt), nd, eb, db)
+
+    def varianceGradient(self, newpt, noiseFunc=None):
+        """out[k*d+l, j] = d var(newpt_j) / d pts[k, l], (N*d, M): evaluateVarianceDerivative -- same layout, same handling of
+        `noiseFunc`, dense and FITC models -- for every kernel with a point derivative.  Squared exponential and 1-D Mehler:
+        exactly what evaluateVarianceDerivative returns, i.e. the REFERENCE's convention, including the squared
+        exponential's doubled signalSize (kernels.py:177).  Isotropic Matern (nu = 3/2, 5/2; KernelIsoMatern.pointDerivative),
+        which the reference does not differentiate: the true gradient.  KernelMehlerND with d > 1 raises AttributeError."""
+        self._point_derivative_ready(newpt, referenceOnly=False)
+        return self._var_grad(newpt, noiseFunc)
+
+    def varianceGradientWRTnewpt(self, newpt):
+        """d var(newpt_i) / d newpt_i, flattened (M*d,): evaluateVarianceDerivWRTnewpt for every kernel with a point derivative,
+        with the conventions of varianceGradient (reference's for squared exponential / 1-D Mehler, true for Matern)."""
+        self._point_derivative_ready(newpt, referenceOnly=False)
+        return self._var_grad_newpt(newpt)
 
     def generateSamples(self, x, noise=1e-10):
         raise NotImplementedError("generateSamples (SVD sampling, gp.py:343-371) is outside the GPU hot path")

@@ -9,6 +9,8 @@ Mirrors `Kernel` (kernels.py:30-70), `KernelIsoMatern` (:72-97), `KernelSquaredE
 Differences from the reference, on purpose:
   * Matern nu=5/2 is implemented (the reference leaves `out` unbound for nu != 3/2, kernels.py:85-91);
     any other nu raises NotImplementedError instead of UnboundLocalError.
+  * `KernelIsoMatern.pointDerivative` (the true derivative w.r.t. a point) exists; the reference's Matern has no
+    `derivative`, and that name stays absent here.
   * `KernelSquaredExponential.derivativeWrtHypParams` works (the reference indexes with a float,
     kernels.py:140-141, and raises IndexError on current NumPy).
   * A NaN from the Mehler kernel raises FloatingPointError instead of print + exit() (kernels.py:288-292).
@@ -77,6 +79,30 @@ class KernelIsoMatern(Kernel):
     def derivativeWrtHypParams(self, x1, x2):
         assert x1.shape == x2.shape, "__evaluate() received non-equal shaped point sets"
         raise AttributeError("derivativeWrtHypParams not implemented for KernelIsoMatern")
+
+    def pointDerivative(self, x1, x2):
+        """out[j, i] = dK(x1[j], x2) / d x1[j, i] for a single point x2 (1, d): the TRUE derivative, with the shapes of
+        KernelSquaredExponential.derivative.  The reference's KernelIsoMatern has no `derivative` (and this class keeps
+        none: GP.evaluateVarianceDerivative stays gated on that name), so there is no convention to mimic.  With
+        t = sqrt(2 nu) |x1[j] - x2| / rho:
+            nu = 3/2:  -signalSize (3 / rho^2) e^-t (x1[j] - x2)
+            nu = 5/2:  -signalSize (5 / (3 rho^2)) (1 + t) e^-t (x1[j] - x2)
+        smooth at x1[j] = x2, where it is 0 (nothing divides by the distance).  Host arithmetic on a handful of points;
+        the device routines (gpx_var_grad, gpx_ivar_grad, ...) carry the same formulas."""
+        assert len(x2.shape) > 1 and len(x1.shape) > 1, "Must supply nd arrays to evaluation function"
+        assert x2.shape[0] == 1 and x2.shape[1] == self.dimension, "x2 not in correct shape"
+        assert x1.shape[0] > 0 and x1.shape[1] == self.dimension, "x1 not in correct shape"
+        kind = self._spec().kind          # (raises for any other nu)
+        rho, sig = self.hyperParam['rho'], self.hyperParam['signalSize']
+        diff = np.asarray(x1, dtype=float) - np.asarray(x2, dtype=float)
+        r = np.sqrt(np.sum(diff ** 2.0, axis=1))
+        if kind == _dev.K_MATERN32:
+            t = np.sqrt(3.0) * r / rho
+            g = -sig * (3.0 / rho ** 2.0) * np.exp(-t)
+        else:
+            t = np.sqrt(5.0) * r / rho
+            g = -sig * (5.0 / (3.0 * rho ** 2.0)) * (1.0 + t) * np.exp(-t)
+        return g[:, None] * diff
 
 
 class KernelSquaredExponential(Kernel):

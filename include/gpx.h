@@ -256,8 +256,12 @@ int gpx_lml_grad_linv(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp
 
 
 /* ---- point-location gradients of the posterior variance ----------------------------------------------
- * For the two kernels the reference differentiates: squared exponential (kernels.py:146-181, including its doubled
- * signalSize, :177) and 1-D Mehler (GPX_K_MEHLER with d == 1; kernels.py:295-324); any other kind is an argument error.
+ * For the two kernels the reference differentiates, in ITS convention: squared exponential (kernels.py:146-181, including its
+ * doubled signalSize, :177) and 1-D Mehler (GPX_K_MEHLER with d == 1; kernels.py:295-324); and for GPX_K_MATERN32 /
+ * GPX_K_MATERN52, which the reference does not differentiate, with the TRUE derivative (t = sqrt(2 nu) |u - p| / rho):
+ *     d k(u, p) / d u = -s (3 / rho^2) e^-t (u - p)   resp.   -s (5 / (3 rho^2)) (1 + t) e^-t (u - p),
+ * smooth at u = p.  Any other kind (Mehler with d > 1) is an argument error.  All entry points of this section and the two
+ * gpx_fitc_var_grad* take the same kinds, with every optional argument.
  * noise_deriv (host N x d, nullable) = d noise(x_j) / d x_jl of a heteroscedastic noise model (space.noiseFunc.deriv,
  * gp.py:314-317): it enters the derivative of the covariance at coincident training points.  Nothing N x N reaches the host. */
 /* grad[a*d + l] = d IVAR / d X[a][l] = (1/M) sum_m d var(z_m) / d X[a][l]
@@ -268,7 +272,7 @@ int gpx_ivar_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, co
 int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                     const gpx_mat* Z, const double* noise_deriv, const gpx_mat* W, double* grad);
 /* ... for the design points from r0 (a multiple of 128) on only: the batch loop pins the earlier ones by equal bounds
- * (experimentalDesign.py:719-724).  Squared exponential, homoscedastic; grad: (N - r0) x d.  2 (N - r0) N M flops instead of 2 N^2 M. */
+ * (experimentalDesign.py:719-724).  Squared exponential or Matern, homoscedastic; grad: (N - r0) x d.  2 (N - r0) N M flops instead of 2 N^2 M. */
 int gpx_ivar_grad_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                        const gpx_mat* Z, const gpx_mat* W, int64_t r0, double* grad);
 /* out[(j*d + l) * M + m] = d var(z_m) / d X[j][l]  (GP.evaluateVarianceDerivative, gp.py:282-341; host, (N*d) x M).

@@ -3,7 +3,10 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq] [--kernel se,matern52]
+
+--kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
+matern52; default se) -- the other entries keep their own kernels.
 """
 import json
 import os
@@ -19,6 +22,7 @@ PEAK_TF, PEAK_GBS = 78.6, 8000.0
 ctx = dev.context()
 quick = "--quick" in sys.argv
 only = set(sys.argv[sys.argv.index("--only") + 1].split(",")) if "--only" in sys.argv else None
+kernels = sys.argv[sys.argv.index("--kernel") + 1].split(",") if "--kernel" in sys.argv else ["se"]
 
 
 def want(section):
@@ -51,26 +55,38 @@ def report(name, replaces, size, t, flops=None, nbytes=None, note=""):
 rng = np.random.default_rng(8192)
 d = 8
 sp = dev.KernelSpec(dev.K_SE, d, list(0.4 + 0.05 * np.arange(d)) + [1.0])
+
+
+def kernel_choice(name):
+    """(KernelSpec, kernel-class factory) of a --kernel name at d = 8."""
+    from gpExp.kernels import KernelSquaredExponential, KernelIsoMatern
+    if name == "se":
+        return sp, lambda: KernelSquaredExponential(list(0.4 + 0.05 * np.arange(d)), 1.0, d)
+    nu = {"matern32": 1.5, "matern52": 2.5}[name]
+    k = KernelIsoMatern(0.7, 1.0, d, nu=nu)
+    return k._spec(), lambda: KernelIsoMatern(0.7, 1.0, d, nu=nu)
+
+
 # ---- f1: gradients of the posterior variance w.r.t. point locations (gp.py:261-341, experimentalDesign.py:168-179)
-if want("f1"):
+for kname in (kernels if want("f1") else []):
+    ksp, make_kernel = kernel_choice(kname)
     N, M = (2048, 8192) if quick else (8192, 32768)
     Xh, Zh = rng.uniform(-1, 1, (N, d)), rng.uniform(-1, 1, (M, d))
     X, Z = dev.points(ctx, Xh), dev.points(ctx, Zh)
-    L = dev.potrf(ctx, dev.kfill(ctx, sp, X, nugget=0.1))
-    _, t = best(lambda: dev.ivar_grad(ctx, sp, L, X, Z))
-    report("gpx_ivar_grad", "costFunctionGP_IVAR.derivative v1 (experimentalDesign.py:168-179)", dict(N=N, M=M, d=d), t,
+    L = dev.potrf(ctx, dev.kfill(ctx, ksp, X, nugget=0.1))
+    _, t = best(lambda: dev.ivar_grad(ctx, ksp, L, X, Z))
+    report("gpx_ivar_grad", "costFunctionGP_IVAR.derivative v1 (experimentalDesign.py:168-179)", dict(N=N, M=M, d=d, kernel=kname), t,
            flops=3.0 * N * N * M, note="ONE count, in SURVEY 8d's units (a triangular solve of an N x M block = N^2 M): beta = K^-1 K(X,Z) "
            "is two solves (2 N^2 M), S = beta beta^T as a lower SYRK is N^2 M more; tr(dK/dx S) needs S")
-    _, t = best(lambda: dev.var_grad_newpt(ctx, sp, L, X, Z))
-    report("gpx_var_grad_newpt", "GP.evaluateVarianceDerivWRTnewpt (gp.py:261-280)", dict(N=N, M=M, d=d), t, flops=2.0 * N * N * M)
+    _, t = best(lambda: dev.var_grad_newpt(ctx, ksp, L, X, Z))
+    report("gpx_var_grad_newpt", "GP.evaluateVarianceDerivWRTnewpt (gp.py:261-280)", dict(N=N, M=M, d=d, kernel=kname), t, flops=2.0 * N * N * M)
     # one optimiser iteration of a continuous design (SLSQP, experimentalDesign.py:471-489): cost, then gradient, same design
-    from gpExp.kernels import KernelSquaredExponential
     from gpExp.gp import GP
     from gpExp.approximation import Space
     from gpExp.experimentalDesign import costFunctionGP_IVAR
     space = Space(d, lambda size: rng.uniform(-1, 1, size), lambda p: np.ones(len(p)))
     def iteration(reuse):
-        g = GP(KernelSquaredExponential(list(0.4 + 0.05 * np.arange(d)), 1.0, d), 0.1)
+        g = GP(make_kernel(), 0.1)
         g.reuseFactor = reuse
         cf = costFunctionGP_IVAR(g, N, space, mcPoints=Zh)
         cf.evaluate(Xh); cf.derivative(Xh)                      # warm: pools, block inverses
@@ -80,7 +96,7 @@ if want("f1"):
             return cf.derivative(Xq)
         return best(both, reps=1)[1]
     def batch_move(reuse, nb_=512):
-        g = GP(KernelSquaredExponential(list(0.4 + 0.05 * np.arange(d)), 1.0, d), 0.1)
+        g = GP(make_kernel(), 0.1)
         g.reuseFactor = reuse
         cf = costFunctionGP_IVAR(g, N, space, mcPoints=Zh)
         cf.evaluate(Xh)
@@ -90,7 +106,7 @@ if want("f1"):
             ts.append(best(lambda: cf.evaluate(Xq), reps=1)[1])
         return min(ts)
     def batch_gradient(pinned, nb_=512):
-        g = GP(KernelSquaredExponential(list(0.4 + 0.05 * np.arange(d)), 1.0, d), 0.1)
+        g = GP(make_kernel(), 0.1)
         cf = costFunctionGP_IVAR(g, N, space, mcPoints=Zh)
         cf.pinnedPoints = pinned
         cf.evaluate(Xh); cf.derivative(Xh)
@@ -99,44 +115,45 @@ if want("f1"):
         return best(lambda: cf.derivative(Xq), reps=2)[1]
     t_gall, t_gfree = batch_gradient(0), batch_gradient(N - 512)
     report("design gradient of the last 512 points", "costFunctionGP_IVAR.derivative inside the batch loop (experimentalDesign.py:"
-           "694-751: earlier batches pinned by equal bounds, :719-724)", dict(N=N, M=M, free=512, d=d), t_gfree,
+           "694-751: earlier batches pinned by equal bounds, :719-724)", dict(N=N, M=M, free=512, d=d, kernel=kname), t_gfree,
            flops=2.0 * 512 * N * M + 512.0 * 512 * M + 512.0 * N * N,
            note="beta_T = L_TT^-T W_T, S_T = (beta_T W^T) L^-1 from the kept solve, row kernel for the free points: %.1f ms for "
                 "all points (kept forward solve), %.1f ms for the free ones" % (1e3 * t_gall, 1e3 * t_gfree))
     t_full, t_inc = batch_move(False), batch_move(True)
     report("design cost after moving the last 512 points", "costFunctionGP_IVAR.evaluate inside the batch loop "
-           "(experimentalDesign.py:694-751: earlier batches pinned)", dict(N=N, M=M, moved=512, d=d), t_inc,
+           "(experimentalDesign.py:694-751: earlier batches pinned)", dict(N=N, M=M, moved=512, d=d, kernel=kname), t_inc,
            flops=2.0 * 512 * (N - 512) * M + 512.0 * 512 * M + 512.0 * N * N,
            note="refit of the moved rows (rows N^2) + W2 = L22^-1 (K(X2, Z) - L21 W1) on the kept solve; %.1f ms when every evaluation "
                 "refits and solves from scratch (reuseFactor = False), %.1f ms incrementally" % (1e3 * t_full, 1e3 * t_inc))
     t_sep, t_shared = iteration(False), iteration(True)
     report("design iteration: cost + gradient", "costFunctionGP_IVAR.evaluate + .derivative at one design (experimentalDesign.py:100-117, "
-           "168-179, 471-489)", dict(N=N, M=M, d=d), t_shared, flops=3.0 * N * N * M + N ** 3 / 3.0,
+           "168-179, 471-489)", dict(N=N, M=M, d=d, kernel=kname), t_shared, flops=3.0 * N * N * M + N ** 3 / 3.0,
            note="count = what one iteration needs: ONE fit (N^3/3), the forward solve once (N^2 M), backward solve and SYRK "
                 "(2 N^2 M); %.1f ms when the gradient call refits and solves forward again (reuseFactor = False: two fits, "
                 "4 N^2 M), %.1f ms with the kept factor and the kept forward solve" % (1e3 * t_sep, 1e3 * t_shared))
     Nv, Mv = (1024, 1024) if quick else (2048, 4096)
     Xv, Zv = dev.points(ctx, Xh[:Nv]), dev.points(ctx, Zh[:Mv])
-    Lv = dev.potrf(ctx, dev.kfill(ctx, sp, Xv, nugget=0.1))
-    _, t = best(lambda: dev.var_grad(ctx, sp, Lv, Xv, Zv), reps=2)
-    report("gpx_var_grad", "GP.evaluateVarianceDerivative (gp.py:282-341)", dict(N=Nv, M=Mv, d=d), t, flops=2.0 * (d + 1) * Nv * Nv * Mv,
+    Lv = dev.potrf(ctx, dev.kfill(ctx, ksp, Xv, nugget=0.1))
+    _, t = best(lambda: dev.var_grad(ctx, ksp, Lv, Xv, Zv), reps=2)
+    report("gpx_var_grad", "GP.evaluateVarianceDerivative (gp.py:282-341)", dict(N=Nv, M=Mv, d=d, kernel=kname), t, flops=2.0 * (d + 1) * Nv * Nv * Mv,
            nbytes=8.0 * Nv * d * Mv,
            note="the (N d) x M result goes to the HOST by contract (that is what the reference returns): %.2f GB over PCIe dominate; "
                 "one N x N matrix dK_l is refilled per coordinate (not d of them)" % (8.0 * Nv * d * Mv / 1e9))
     del L, Lv
 # ---- a13-a15 / 8c: design kernels at C3 / C5 sizes
-if want("design"):
+for kname in (kernels if want("design") else []):
+    ksp = kernel_choice(kname)[0]
     N3, M3, nmc = (4096, 16384, 1024) if quick else (16384, 65536, 4096)
     rng = np.random.default_rng(16384)
     X3h, C3h, Z3h = rng.uniform(-1, 1, (N3, d)), rng.uniform(-1, 1, (M3, d)), rng.uniform(-1, 1, (nmc, d))
     X3, C3, Z3 = dev.points(ctx, X3h), dev.points(ctx, C3h), dev.points(ctx, Z3h)
-    K3 = dev.potrf(ctx, dev.kfill(ctx, sp, X3, nugget=0.1))
-    _, t = best(lambda: dev.greedy_ivar_step(ctx, sp, K3, X3, C3, Z3, 0.1))
+    K3 = dev.potrf(ctx, dev.kfill(ctx, ksp, X3, nugget=0.1))
+    _, t = best(lambda: dev.greedy_ivar_step(ctx, ksp, K3, X3, C3, Z3, 0.1))
     report("gpx_greedy_ivar_step", "costFunctionGP_IVAR.evaluate per candidate (experimentalDesign.py:79-117; SURVEY 8c composition)",
-           dict(N=N3, candidates=M3, nMC=nmc, d=d), t, flops=2.0 * nmc * M3 * N3 + 1.0 * N3 * N3 * (M3 + nmc),
+           dict(N=N3, candidates=M3, nMC=nmc, d=d, kernel=kname), t, flops=2.0 * nmc * M3 * N3 + 1.0 * N3 * N3 * (M3 + nmc),
            note="rank-one scoring of every candidate: two N x (M + nMC) triangular solves + the nMC x M x N product")
-    _, t = best(lambda: dev.greedy_var(ctx, sp, C3, 16))
-    report("gpx_greedy_var", "performGreedyVarExperimentalDesign (experimentalDesign.py:787-845)", dict(candidates=M3, picks=16, d=d), t,
+    _, t = best(lambda: dev.greedy_var(ctx, ksp, C3, 16))
+    report("gpx_greedy_var", "performGreedyVarExperimentalDesign (experimentalDesign.py:787-845)", dict(candidates=M3, picks=16, d=d, kernel=kname), t,
            nbytes=8.0 * M3 * 16 * 16 / 2 + 8.0 * M3 * d * 16, note="incremental Cholesky rows; latency-bound (one launch chain per pick)")
     del K3
 if want("mi"):
