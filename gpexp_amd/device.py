@@ -600,6 +600,31 @@ def lml_grad(ctx, spec, L, X, alpha, slabs=None):
     return lml_grad_from_sums(spec, sums)
 
 
+def loo(ctx, L, y, want_pred=True):
+    """Leave-one-out predictions from the factor (gpx_loo; the reference has no counterpart): (mean (N,), var (N,), L_LOO) --
+    mean_i / var_i the predictive distribution of the observation y_i given all the others, L_LOO the sum of the log predictive
+    probabilities.  Needs the factor only, so every kernel is accepted.  `want_pred=False`: (None, None, L_LOO)."""
+    y = as_f64(np.ravel(y))
+    mean = np.empty_like(y) if want_pred else None
+    var = np.empty_like(y) if want_pred else None
+    lp = C.c_double()
+    check(ctx.lib.gpx_loo(ctx.h, L.h, dptr(y), dptr(mean), dptr(var), C.byref(lp)))
+    return mean, var, lp.value
+
+
+def loo_grad(ctx, spec, L, X, nugget, y, slab_rows=0):
+    """(L_LOO, its TRUE derivatives [lengths..., signalSize, noise variance]) (gpx_loo_grad).  `nugget`: what went into L, as
+    kfill takes it.  `slab_rows`: rows of W = P dK formed at once (a multiple of 128); 0 = the whole matrix when P, dK and W fit,
+    otherwise the largest slab that does.  When not even P fits the error is gpx_dev_alloc's "hipMalloc(...) failed", the one
+    lml_grad recognises."""
+    y = as_f64(np.ravel(y))
+    nug, nlen = _nugget_args(nugget, X.shape[0])
+    out = np.empty(spec.nsums)
+    lp = C.c_double()
+    check(ctx.lib.gpx_loo_grad(ctx.h, *spec.args(), L.h, X.h, dptr(nug), nlen, dptr(y), int(slab_rows), C.byref(lp), dptr(out)))
+    return lp.value, out
+
+
 class MiState:
     """One rank's state of a row-sharded greedy MI run (gpx_mi_*): rows [lo, hi) of the inverse are kept current."""
 

@@ -460,6 +460,54 @@ class GP:
             return out, outD
         return out
 
+    # ---- leave-one-out cross-validation (Rasmussen & Williams 5.4.2; absent in the reference) --------------------------
+    def _loo_factor(self, pts, noiseIn):
+        """Factor of K(pts) + nugget under the current hyper-parameters for the leave-one-out calls -> (X, L, nugget).  As
+        loglikeParams: the trained state is not touched, and right after `train` on the same points the kept factor is
+        reused.  Under a multi-process session every rank runs the same single-GPU call (a block-cyclic factor is made dense
+        first)."""
+        if self.FITC is not None:
+            raise NotImplementedError("leave-one-out cross-validation needs the dense factor; FITC models are not supported")
+        nugget = self.noise if noiseIn is None else noiseIn
+        X, L, _ = self._factor(pts, nugget, remember=False)
+        if self.dropped > 0:
+            raise ValueError("leave-one-out cross-validation is undefined here: the factorisation dropped %d point(s) whose "
+                             "conditional variance is at round-off level (duplicated points at zero noise)" % self.dropped)
+        if getattr(L, "is_cyclic", False):
+            L = L.dense()
+        return X, L, nugget
+
+    def looPredict(self, pts, evals, noiseIn=None):
+        """Leave-one-out predictions under the current hyper-parameters, without refits: (mean (N,), var (N,)) with
+        mean_i, var_i the predictive distribution of the OBSERVATION evals_i given all the other points (the noise of point i is
+        included): mean_i = y_i - alpha_i / P_ii, var_i = 1 / P_ii, P = K^-1, alpha = P y (gpx_loo).  Standardised residuals
+        (evals - mean) / sqrt(var) check a fit before a design trusts it.  Every kernel; does not touch the trained state."""
+        evals = np.asarray(evals, dtype=float)
+        assert len(evals.shape) == 1, "evaluations must be an (N,) array"
+        _, L, _ = self._loo_factor(pts, noiseIn)
+        y = evals - self.gpPriorMean(pts)
+        mean, var, _ = _dev.loo(_dev.context(), L, y)
+        return mean + self.gpPriorMean(pts), var
+
+    def looLogLike(self, pts, evals, returnDeriv=0, noiseIn=None):
+        """Leave-one-out log predictive probability sum_i log p(y_i | y_-i)  [, {key: d/d key}] -- a model-selection objective
+        beside the marginal likelihood, more robust when the kernel family is wrong.
+
+        The dict has the keys of loglikeParams (`kernel.hyperParam` keys + 'noise'); its entries are the TRUE derivatives.
+        In particular 'noise' is the derivative with respect to the noise VARIANCE (a common shift of every nugget), WITHOUT
+        the reference's factor 2 * noise that loglikeParams carries (gp.py:463-464).  Gradient: squared exponential and
+        isotropic Matern kernels (gpx_loo_grad).  Does not touch the trained state."""
+        evals = np.asarray(evals, dtype=float)
+        assert len(evals.shape) == 1, "evaluations must be an (N,) array"
+        X, L, nugget = self._loo_factor(pts, noiseIn)
+        y = evals - self.gpPriorMean(pts)
+        ctx = _dev.context()
+        if returnDeriv == 1:
+            out, grad = _dev.loo_grad(ctx, self.kernel._spec(), L, X, nugget, y)
+            keys = list(self.kernel.hyperParam.keys()) + ['noise']
+            return out, dict(zip(keys, grad))
+        return _dev.loo(ctx, L, y, want_pred=False)[2]
+
     def getHypParamNames(self):
         return self.kernel.hyperParam.keys()
 
@@ -473,13 +521,19 @@ class GP:
 
     # ---- hyper-parameter fit: host driver around loglikeParams -----------------------------------
     def findOptParamsLogLike(self, pts, evals, paramsStart=None, paramLowerBounds=None, paramUpperBounds=None,
-                             useNoise=None, maxiter=40, useLastParams=True, analyticGradient=False):
+                             useNoise=None, maxiter=40, useLastParams=True, analyticGradient=False, objective="lml"):
         """Maximise the marginal likelihood over the kernel hyper-parameters (+ noise unless `useNoise` is given);
         bounds default to [max(v/10, 1e-3), min(10 v, 10)], noise to [1e-12, 1] from 1e-5 (gp.py:498-590).
+
+        `objective="loo"` maximises the leave-one-out log predictive probability (looLogLike) instead; with
+        `analyticGradient=True` L-BFGS-B gets its gradient from gpx_loo_grad, whose 'noise' entry already is the derivative
+        w.r.t. the noise variance.  Any other string raises ValueError.
 
         `analyticGradient=True` (opt-in; squared-exponential kernel) hands L-BFGS-B the gradient from
         gpx_lml_grad instead of letting it difference the objective (gp.py:635, approx_grad=True): one factorisation per
         iterate instead of nparams+1.  The default reproduces the reference's numerical-gradient search."""
+        if objective not in ("lml", "loo"):
+            raise ValueError("findOptParamsLogLike: objective must be 'lml' or 'loo', not %r" % (objective,))
         if paramsStart is None:
             paramsStart = copy.deepcopy(self.kernel.hyperParam)
         if paramLowerBounds is None:
@@ -498,7 +552,13 @@ class GP:
 
         def objFunc(in0, gradIn):
             self.updateKernelParams(dict(zip(keys, in0)))
-            if gradIn.size > 0:
+            if objective == "loo":
+                if gradIn.size > 0:
+                    margLogLike, derivs = self.looLogLike(pts, evals, returnDeriv=1)
+                    gradIn[:] = -np.array([derivs[k] for k in keys])
+                else:
+                    margLogLike = self.looLogLike(pts, evals, returnDeriv=0)
+            elif gradIn.size > 0:
                 margLogLike, derivs = self.loglikeParams(pts, evals, returnDeriv=1)
                 if analyticGradient and 'noise' in derivs and 'noise' in keys:
                     # loglikeParams scales the noise entry by 2*noise (gp.py:463-464, a derivative w.r.t. sqrt(noise));

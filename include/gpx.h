@@ -254,6 +254,30 @@ int gpx_lml_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
 int gpx_lml_grad_linv(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                       const double* alpha, double* sums);
 
+/* ---- leave-one-out cross-validation (Rasmussen & Williams 5.4.2) ---------------------------------------------------
+ * The reference has NO counterpart: validating a fit there means N refits through GP.train.  Zero prior mean, K including the
+ * nugget D = diag(noise); with P = K^-1, alpha = P y, p_i = P_ii:
+ *     mu_i = y_i - alpha_i / p_i,   var_i = 1 / p_i     the predictive distribution of the OBSERVATION y_i given all the others
+ *                                                       (the noise of point i is included)
+ *     L_LOO = sum_i [ -1/2 log var_i - (y_i - mu_i)^2 / (2 var_i) - 1/2 log 2 pi ]
+ *     dL_LOO / d theta = sum_i ( alpha_i a_i - 1/2 (1 + alpha_i^2 / p_i) q_i ) / p_i,   W = P dK/d theta,
+ *                        a_i = (W alpha)_i,   q_i = sum_l W_il P_il  (= [P dK P]_ii)
+ * with dK as in gpx_lml_grad (coordinate differences first, then scaled; K0 = the covariance without the nugget):
+ *     SE length cl_k:  K0 e_k^2 / cl_k, e_k = (x_k - x'_k) / cl_k;     Matern rho:  (rho dk/d rho) / rho;
+ *     signalSize s:  K0 / s  (no product: P K0 = I - P D);              noise, a common shift of every nugget:  I.
+ * One N x N x N product per LENGTH-type parameter only (d for SE, 1 for Matern).  All reductions run in a fixed order: two calls
+ * agree bit for bit. */
+/* mean / var (host N, each nullable), *logp = L_LOO.  Needs the factor only, so every kernel is accepted: L^-1 by the halving
+ * recursion, p_i = column sums of squares of it (N^3 / 3 flops, no K^-1 is formed). */
+int gpx_loo(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* mean, double* var, double* logp);
+/* *logp = L_LOO and grad[nlen + 2] = its TRUE derivatives in gpx_lml_grad's order [lengths..., signalSize, noise] (the noise entry
+ * is the derivative w.r.t. the noise VARIANCE; no factor 2 * noise).  nugget as gpx_kfill takes it (nugget_len in {0, 1, N}) --
+ * the one that went into L.  slab_rows: rows of W = P dK formed at once, a multiple of 128; 0 = the whole matrix when it fits,
+ * otherwise the largest slab that does.  Squared exponential and isotropic Matern only, as gpx_lml_grad.
+ * 2 N^3 / 3 + 2 nlen N^3 flops; memory: P + dK + the slab of W. */
+int gpx_loo_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                 const double* nugget, int64_t nugget_len, const double* y, int64_t slab_rows, double* logp, double* grad);
+
 
 /* ---- point-location gradients of the posterior variance ----------------------------------------------
  * For the two kernels the reference differentiates, in ITS convention: squared exponential (kernels.py:146-181, including its

@@ -3,10 +3,11 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq] [--kernel se,matern52]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo] [--kernel se,matern52] [--out FILE]
 
 --kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
 matern52; default se) -- the other entries keep their own kernels.
+--out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl).
 """
 import json
 import os
@@ -50,6 +51,7 @@ def report(name, replaces, size, t, flops=None, nbytes=None, note=""):
     if note:
         line["note"] = note
     print(json.dumps(line), flush=True)
+    return line
 
 
 rng = np.random.default_rng(8192)
@@ -314,3 +316,40 @@ if want("acq"):
            flops=1.0 * Na * Na * Mb + Na ** 3 / 3.0,
            note="2 picks timed, per pick: one factorisation + the forward solve over all candidates; gpx_acq_batch per pick is "
                 "%.1f x below it" % (t / 2 / t_pick))
+
+# ---- loo: leave-one-out cross-validation and its hyper-parameter gradient (gpx_loo / gpx_loo_grad; none in the reference)
+if want("loo"):
+    from gpExp.kernels import KernelSquaredExponential, KernelIsoMatern
+    Nl = 4096 if quick else 16384
+    rl = np.random.default_rng(Nl)
+    Xl = rl.uniform(-1, 1, (Nl, 8))
+    yl = np.sin(3.0 * Xl[:, 0]) + 0.5 * np.cos(2.0 * Xl.sum(1)) + 0.1 * rl.standard_normal(Nl)
+    Xd = dev.points(ctx, Xl)
+    lines = []
+    for kname, kern in (("Matern-5/2", KernelIsoMatern(1.5, 1.0, 8, nu=2.5)),
+                        ("ARD-SE", KernelSquaredExponential(list(0.5 + 0.05 * np.arange(8)), 1.0, 8))):
+        ksp = kern._spec()
+        size = dict(N=Nl, d=8, kernel=kname, nlen=ksp.nlen)
+        Ll = dev.potrf(ctx, dev.kfill(ctx, ksp, Xd, nugget=0.01))
+        dev.loo(ctx, Ll, yl)
+        _, t = best(lambda: dev.loo(ctx, Ll, yl))
+        lines.append(report("gpx_loo", "N refits through GP.train (the reference has no leave-one-out call)", size, t,
+                            flops=Nl ** 3 / 3.0, note="L^-1 by the halving recursion + column sums of squares + potrs"))
+        dev.loo_grad(ctx, ksp, Ll, Xd, 0.01, yl)
+        _, tg = best(lambda: dev.loo_grad(ctx, ksp, Ll, Xd, 0.01, yl))
+        # what the gradient is composed of, through entry points that predate it: one inverse + nlen square NN products
+        _, tp = best(lambda: dev.potri(ctx, Ll).free())
+        A, B, Cm = (dev.DeviceMatrix.zeros(ctx, Nl, Nl) for _ in range(3))
+        dev.dbg_gemm(ctx, A, B, Cm, False, False)
+        _, tm = best(lambda: dev.dbg_gemm(ctx, A, B, Cm, False, False))
+        for m in (A, B, Cm):
+            m.free()
+        base = tp + ksp.nlen * tm
+        lines.append(report("gpx_loo_grad", "none in the reference", size, tg, flops=2.0 * Nl ** 3 / 3.0 + 2.0 * ksp.nlen * Nl ** 3,
+                            note="composition baseline in this process: potri %.2f ms + %d x NN product %.2f ms = %.2f ms; gpx_loo_grad / "
+                                 "baseline = %.3f" % (1e3 * tp, ksp.nlen, 1e3 * tm, 1e3 * base, tg / base)))
+        Ll.free()
+    if "--out" in sys.argv:
+        with open(sys.argv[sys.argv.index("--out") + 1], "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
