@@ -172,6 +172,7 @@ _SIGS = {
                                            C.POINTER(c_i64), c_i64, C.POINTER(c_i64)]),
     "gpx_dbg_guard_violations": (c_i64, [c_vp]),
     "gpx_dbg_guard_selftest": (C.c_int, [c_vp]),
+    "gpx_dbg_pool_stats": (C.c_int, [c_vp, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "gpx_dbg_spin": (C.c_int, [c_vp, C.c_int]),
     "gpx_dbg_spin_us": (C.c_int, [c_vp, c_i64]),
     "gpx_dbg_stamp": (C.c_int, [c_vp, C.c_int]),

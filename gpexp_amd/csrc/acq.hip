@@ -21,42 +21,15 @@
 //     Matern32  dk/dz   = -sig (3 / rho^2) e^-t (z - x)             t = sqrt(3) |z - x| / rho
 //     Matern52  dk/dz   = -sig (5 / (3 rho^2)) (1 + t) e^-t (z - x)  t = sqrt(5) |z - x| / rho
 // all smooth at z = x.  Where var == 0 exactly, a and b are NaN, and so is the gradient row.
-#include "gpx_internal.h"
+#include "gpx_device.h"
 #include <math.h>
 
 namespace {
 
 constexpr int ACQ_EPI = 128;   // candidates per epilogue block = one arg-min partial; chunk starts are multiples of it
 
-struct ArgMin {
-  double c;
-  int64_t i;   // -1: no non-NaN cost seen
-};
-
-// first minimum: the smaller cost, on a tie the smaller index; NaN costs never enter.  Associative and commutative, so the
-// winner does not depend on the reduction tree or on the chunking.
-__device__ __forceinline__ ArgMin argmin_merge(ArgMin a, ArgMin b) {
-  if (a.i < 0) return b;
-  if (b.i < 0) return a;
-  return (b.c < a.c || (b.c == a.c && b.i < a.i)) ? b : a;
-}
-
-__device__ __forceinline__ ArgMin argmin_block(ArgMin v, double* sc, int64_t* si) {
-  const int t = threadIdx.x;
-  sc[t] = v.c;
-  si[t] = v.i;
-  __syncthreads();
-  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      const ArgMin o = argmin_merge(ArgMin{sc[t], si[t]}, ArgMin{sc[t + w], si[t + w]});
-      sc[t] = o.c;
-      si[t] = o.i;
-    }
-    __syncthreads();
-  }
-  return ArgMin{sc[0], si[0]};
-}
-
+// arg-min partials: VI{cost, index} under argmin_merge (gpx_device.h) -- the first minimum among the non-NaN costs, i = -1: no
+// non-NaN cost seen
 // cost of one candidate from its posterior mean and SIGNED variance -- the one formula of gpx_acq's epilogue and of the batch
 // selection's per-pick kernel.  a = dA/dmu, b = dA/dvar (NaN where var == 0 exactly).
 __device__ __forceinline__ double acq_cost(int acq, double param, double mu, double var, double* a_out, double* b_out) {
@@ -97,7 +70,7 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double p
   __shared__ double sc[ACQ_EPI];
   __shared__ int64_t si[ACQ_EPI];
   const int64_t j = (int64_t)blockIdx.x * ACQ_EPI + threadIdx.x;
-  ArgMin v{0.0, -1};
+  VI v{0.0, -1};
   if (j < mc) {
     double a, b;
     const double c = acq_cost(acq, param, mean[j], kd[j] - ssq[j], &a, &b);
@@ -106,11 +79,11 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double p
       coef[2 * j] = a;
       coef[2 * j + 1] = b;
     }
-    if (c == c) v = ArgMin{c, j0 + j};
+    if (c == c) v = VI{c, j0 + j};
   }
-  const ArgMin r = argmin_block(v, sc, si);
+  const VI r = block_arg_reduce(v, sc, si, blockDim.x, argmin_merge);
   if (threadIdx.x == 0) {
-    part_c[j0 / ACQ_EPI + blockIdx.x] = r.c;
+    part_c[j0 / ACQ_EPI + blockIdx.x] = r.v;
     part_i[j0 / ACQ_EPI + blockIdx.x] = r.i;
   }
 }
@@ -120,19 +93,19 @@ __global__ __launch_bounds__(256) void acq_argmin_kernel(const double* __restric
                                                          int64_t np_, double* __restrict__ out_c, int64_t* __restrict__ out_i) {
   __shared__ double sc[256];
   __shared__ int64_t si[256];
-  ArgMin v{0.0, -1};
-  for (int64_t p = threadIdx.x; p < np_; p += 256) v = argmin_merge(v, ArgMin{part_c[p], part_i[p]});
-  const ArgMin r = argmin_block(v, sc, si);
+  VI v{0.0, -1};
+  for (int64_t p = threadIdx.x; p < np_; p += 256) v = argmin_merge(v, VI{part_c[p], part_i[p]});
+  const VI r = block_arg_reduce(v, sc, si, blockDim.x, argmin_merge);
   if (threadIdx.x == 0) {
-    out_c[0] = r.i < 0 ? __builtin_nan("") : r.c;
+    out_c[0] = r.i < 0 ? __builtin_nan("") : r.v;
     out_i[0] = r.i;
   }
 }
 
 // grad[m][l] = dA_m / dz_m[l] for the candidates of one chunk: one workgroup per candidate, one pass over the training points,
 // fixed-order tree reduction per coordinate.  betaT: row m = beta[:, m] (row stride ldt), coef[2m], coef[2m+1] = (a, b).
-// Per pair the radial factor f(r) multiplies (x_j - z) -- the derivative is linear in the coordinate difference for the three
-// kernels -- and the kernel's constant is applied once at the end:
+// Per pair the radial factor f(r) (radial_pair, gpx_device.h) multiplies (x_j - z) -- the derivative is linear in the coordinate
+// difference for the three kernels -- and the kernel's constant is applied once at the end:
 //     SE   f = k(z, x_j),              const_l = 1 / cl_l^2 = scale_l^2
 //     M32  f = e^-t,                   const   = sig scale^2
 //     M52  f = (1 + t) e^-t,           const   = sig scale^2 / 3
@@ -153,24 +126,8 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double*
   }
   const double* __restrict__ bt = betaT + mm * ldt;
   for (int64_t j = t; j < n; j += 256) {
-    const double* xj = X + j * d;
-    double diff[DMAX], r2 = 0.0;
-#pragma unroll
-    for (int l = 0; l < DMAX; ++l) {
-      diff[l] = 0.0;
-      if (l < d) {
-        diff[l] = xj[l] - zs[l];
-        const double e = diff[l] * kp.scale[l];
-        r2 = fma(e, e, r2);
-      }
-    }
-    double f;
-    if (KIND == GPX_K_SE) {
-      f = kp.sig * exp(-0.5 * r2);
-    } else {
-      const double tt = sqrt(r2);
-      f = KIND == GPX_K_MATERN32 ? exp(-tt) : (1.0 + tt) * exp(-tt);
-    }
+    double diff[DMAX];
+    const double f = radial_pair<KIND, DMAX>(kp, X + j * d, zs, diff);   // diff = x_j - z
     const double w = fma(ca, alpha[j], cb * bt[j]) * f;
 #pragma unroll
     for (int l = 0; l < DMAX; ++l) s1[l] = fma(w, diff[l], s1[l]);
@@ -181,12 +138,7 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double*
       double c = kp.scale[l] * kp.scale[l];
       if (KIND == GPX_K_MATERN32) c *= kp.sig;
       if (KIND == GPX_K_MATERN52) c *= kp.sig / 3.0;
-      red[t] = c * s1[l];
-      __syncthreads();
-      for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-      }
+      block_sum_256(red, c * s1[l]);
       if (t == 0) out[mm * d + l] = red[0];
       __syncthreads();
     }
@@ -195,19 +147,11 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double*
 
 int launch_acq_grad(gpx_ctx* ctx, const KParams& kp, const double* X, int64_t n, const double* Zc, int64_t mc,
                     const double* betaT, int64_t ldt, const double* alpha, const double* coef, double* out) {
-#define GPX_CALL_K(K_, DM_)                                                                                               \
+#define GPX_CALL(K_, DM_)                                                                                                 \
   hipLaunchKernelGGL((acq_grad_kernel<K_, DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X, n, Zc, betaT, ldt, \
                      alpha, coef, out)
-#define GPX_CALL_SE(DM_) GPX_CALL_K(GPX_K_SE, DM_)
-#define GPX_CALL_M32(DM_) GPX_CALL_K(GPX_K_MATERN32, DM_)
-#define GPX_CALL_M52(DM_) GPX_CALL_K(GPX_K_MATERN52, DM_)
-  if (kp.kind == GPX_K_SE) GPX_SE_DISPATCH(kp.d, GPX_CALL_SE);
-  else if (kp.kind == GPX_K_MATERN32) GPX_SE_DISPATCH(kp.d, GPX_CALL_M32);
-  else GPX_SE_DISPATCH(kp.d, GPX_CALL_M52);
-#undef GPX_CALL_M52
-#undef GPX_CALL_M32
-#undef GPX_CALL_SE
-#undef GPX_CALL_K
+  GPX_RADIAL_DISPATCH(kp.kind, kp.d, GPX_CALL);
+#undef GPX_CALL
   GPX_HIP(hipGetLastError());
   return 0;
 }
@@ -226,27 +170,28 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
   const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
   const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
   const int64_t bytesT = (grad && np >= 4096) ? mc_alloc * chol_binv_order(np) * 8 : 0;
-  void *pB = nullptr, *pW = nullptr, *pal = nullptr, *pmean = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
-  void *pcost = nullptr, *pcoef = nullptr, *pgrad = nullptr, *ppc = nullptr, *ppi = nullptr, *pbc = nullptr, *pbi = nullptr;
-  void* pT = nullptr;
+  double *pB = nullptr, *pW = nullptr, *pT = nullptr, *pal = nullptr, *pmean = nullptr, *pout = nullptr, *ppart = nullptr;
+  double *pkd = nullptr, *pcost = nullptr, *pcoef = nullptr, *pgrad = nullptr, *ppc = nullptr, *pbc = nullptr;
+  int64_t *ppi = nullptr, *pbi = nullptr;
+  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
   int r = 0;
   do {
-    if ((r = gpx_dev_alloc(ctx, bytesB, &pB)) != 0) break;
-    if ((oop || grad) && (r = gpx_dev_alloc(ctx, bytesB, &pW)) != 0) break;
-    if (bytesT && (r = gpx_dev_alloc(ctx, bytesT, &pT)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, np * 8, &pal)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pmean)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pout)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pkd)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, M * 8, &pcost)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppi)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, 8, &pbc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, 8, &pbi)) != 0) break;
+    if ((r = sc.get(bytesB, &pB)) != 0) break;
+    if ((oop || grad) && (r = sc.get(bytesB, &pW)) != 0) break;
+    if (bytesT && (r = sc.get(bytesT, &pT)) != 0) break;
+    if ((r = sc.get(np * 8, &pal)) != 0) break;
+    if ((r = sc.get(bytes_out, &pmean)) != 0) break;
+    if ((r = sc.get(bytes_out, &pout)) != 0) break;
+    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
+    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
+    if ((r = sc.get(M * 8, &pcost)) != 0) break;
+    if ((r = sc.get(nparts * 8, &ppc)) != 0) break;
+    if ((r = sc.get(nparts * 8, &ppi)) != 0) break;
+    if ((r = sc.get(8, &pbc)) != 0) break;
+    if ((r = sc.get(8, &pbi)) != 0) break;
     if (grad) {
-      if ((r = gpx_dev_alloc(ctx, 2 * bytes_out, &pcoef)) != 0) break;
-      if ((r = gpx_dev_alloc(ctx, M * d * 8, &pgrad)) != 0) break;
+      if ((r = sc.get(2 * bytes_out, &pcoef)) != 0) break;
+      if ((r = sc.get(M * d * 8, &pgrad)) != 0) break;
     }
     if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
@@ -256,26 +201,25 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     for (int64_t j0 = 0; j0 < M && r == 0; j0 += mcmax) {
       const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
       const int64_t mcp = gpx_round_up(mc, GPX_TILE);
-      double* B = (double*)pB;
+      double* B = pB;
       const double* Zc = Z->p + j0 * d;
       const int64_t ldb = gpx_skew_ld(mcp);
       // posterior_impl's sequence, operation for operation: the values equal GP.evaluate's
       if ((r = launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb)) != 0) break;
-      if ((r = launch_colreduce(ctx, B, ldb, n, mcp, (const double*)pal, (double*)pmean, (double*)ppart)) != 0) break;
+      if ((r = launch_colreduce(ctx, B, ldb, n, mcp, pal, pmean, ppart)) != 0) break;
       double* Wsol = B;
       if (oop) {
-        if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, (double*)pW, ldb, mcp)) != 0) break;
-        Wsol = (double*)pW;
+        if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, pW, ldb, mcp)) != 0) break;
+        Wsol = pW;
       } else if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp)) != 0) {
         break;
       }
-      if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, (double*)pout, (double*)ppart)) != 0) break;
-      if ((r = launch_kdiag(ctx, kp, Zc, mc, (double*)pkd)) != 0) break;
+      if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, pout, ppart)) != 0) break;
+      if ((r = launch_kdiag(ctx, kp, Zc, mc, pkd)) != 0) break;
       {
         ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 5.0 * (double)mc);
         hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
-                           param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, (double*)pcost,
-                           (double*)pcoef, (double*)ppc, (int64_t*)ppi);
+                           param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, pcost, pcoef, ppc, ppi);
         if (hipGetLastError() != hipSuccess) {
           r = -2;
           break;
@@ -283,23 +227,22 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
       }
       if (!grad) continue;
       // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
-      double* Bt = Wsol == B ? (double*)pW : B;
+      double* Bt = Wsol == B ? pW : B;
       if ((r = launch_transpose(ctx, Wsol, np, mcp, ldb, Bt, np)) != 0) break;
-      if (pT) r = chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, (double*)pT);
+      if (pT) r = chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, pT);
       else r = chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np);
       if (r != 0) break;
       {
         ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
                      8.0 * ((double)n * (double)mc + (double)n * d));
-        r = launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, (const double*)pal, (const double*)pcoef,
-                            (double*)pgrad + j0 * d);
+        r = launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, pal, pcoef, pgrad + j0 * d);
       }
     }
     if (r != 0) break;
     if (best || best_cost) {
       ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
       hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                         (double*)pbc, (int64_t*)pbi);
+                         pbc, pbi);
       if (hipGetLastError() != hipSuccess) {
         r = -2;
         break;
@@ -319,23 +262,10 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
       break;
     }
   } while (0);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (pB) gpx_dev_release(ctx, pB, bytesB);
-  if (pW) gpx_dev_release(ctx, pW, bytesB);
-  if (pT) gpx_dev_release(ctx, pT, bytesT);
-  if (pal) gpx_dev_release(ctx, pal, np * 8);
-  if (pmean) gpx_dev_release(ctx, pmean, bytes_out);
-  if (pout) gpx_dev_release(ctx, pout, bytes_out);
-  if (pkd) gpx_dev_release(ctx, pkd, bytes_out);
-  if (ppart) gpx_dev_release(ctx, ppart, bytes_part);
-  if (pcost) gpx_dev_release(ctx, pcost, M * 8);
-  if (ppc) gpx_dev_release(ctx, ppc, nparts * 8);
-  if (ppi) gpx_dev_release(ctx, ppi, nparts * 8);
-  if (pbc) gpx_dev_release(ctx, pbc, 8);
-  if (pbi) gpx_dev_release(ctx, pbi, 8);
-  if (pcoef) gpx_dev_release(ctx, pcoef, 2 * bytes_out);
-  if (pgrad) gpx_dev_release(ctx, pgrad, M * d * 8);
-  if (r == -2) gpx_set_error("acq: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  if (r == -2) {
+    (void)hipStreamSynchronize(ctx->stream);   // the error text is that of the stream's work, as before
+    gpx_set_error("acq: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  }
   return r;
 }
 
@@ -405,7 +335,7 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
   __shared__ double shc[ACQ_EPI];
   __shared__ int64_t shi[ACQ_EPI];
   const int64_t j = (int64_t)blockIdx.x * ACQ_EPI + threadIdx.x;
-  ArgMin best{0.0, -1};
+  VI best{0.0, -1};
   if (j < M) {
     double m = mu[j], var = v[j];
     if (upd) {
@@ -426,11 +356,11 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
     double c = acq_cost(acq, sc[SC_PARAM], m, var, &a, &b);
     if (mask[j]) c = __builtin_nan("");
     cost[j] = c;
-    if (c == c) best = ArgMin{c, j};
+    if (c == c) best = VI{c, j};
   }
-  const ArgMin r = argmin_block(best, shc, shi);
+  const VI r = block_arg_reduce(best, shc, shi, blockDim.x, argmin_merge);
   if (threadIdx.x == 0) {
-    part_c[blockIdx.x] = r.c;
+    part_c[blockIdx.x] = r.v;
     part_i[blockIdx.x] = r.i;
   }
 }
@@ -449,31 +379,33 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
   const int64_t bytes_part = colreduce_partial_elems(np, Mp) * 8 + 8;
   const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
   const int64_t bytes_w = (np > q ? np : q) * 8;
-  void *pW = nullptr, *pB = nullptr, *pU = nullptr, *pal = nullptr, *pmu = nullptr, *pv = nullptr, *pkd = nullptr, *pss = nullptr;
-  void *ppart = nullptr, *pcost = nullptr, *ppc = nullptr, *ppi = nullptr, *pbc = nullptr, *pbi = nullptr, *psc = nullptr;
-  void *puc = nullptr, *pw = nullptr, *pmask = nullptr;
+  double *pW = nullptr, *pB = nullptr, *pU = nullptr, *pal = nullptr, *pmu = nullptr, *pv = nullptr, *pkd = nullptr, *pss = nullptr;
+  double *ppart = nullptr, *pcost = nullptr, *ppc = nullptr, *pbc = nullptr, *psc = nullptr, *puc = nullptr, *pw = nullptr;
+  int64_t *ppi = nullptr, *pbi = nullptr;
+  int* pmask = nullptr;
+  Scratch sc(ctx);
   const dim3 gEpi((unsigned)nparts), gM((unsigned)((M + 255) / 256));
   const dim3 gPick((unsigned)(((np > q ? np : q) + 255) / 256));
   int r = 0;
   do {
-    if ((r = gpx_dev_alloc(ctx, bytesW, &pW)) != 0) break;
-    if (oop && (r = gpx_dev_alloc(ctx, bytesB, &pB)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytesU, &pU)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, np * 8, &pal)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytesM, &pmu)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytesM, &pv)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytesM, &pkd)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytesM, &pss)) != 0) break;    // |W_C[:, j]|^2 at the set-up, then h of every pick
-    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, M * 8, &pcost)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, nparts * 8, &ppi)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, 8, &pbc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, 8, &pbi)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, SC_N * 8, &psc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, q * 8, &puc)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_w, &pw)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, Mp * 4, &pmask)) != 0) break;
+    if ((r = sc.get(bytesW, &pW)) != 0) break;
+    if (oop && (r = sc.get(bytesB, &pB)) != 0) break;
+    if ((r = sc.get(bytesU, &pU)) != 0) break;
+    if ((r = sc.get(np * 8, &pal)) != 0) break;
+    if ((r = sc.get(bytesM, &pmu)) != 0) break;
+    if ((r = sc.get(bytesM, &pv)) != 0) break;
+    if ((r = sc.get(bytesM, &pkd)) != 0) break;
+    if ((r = sc.get(bytesM, &pss)) != 0) break;    // |W_C[:, j]|^2 at the set-up, then h of every pick
+    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
+    if ((r = sc.get(M * 8, &pcost)) != 0) break;
+    if ((r = sc.get(nparts * 8, &ppc)) != 0) break;
+    if ((r = sc.get(nparts * 8, &ppi)) != 0) break;
+    if ((r = sc.get(8, &pbc)) != 0) break;
+    if ((r = sc.get(8, &pbi)) != 0) break;
+    if ((r = sc.get(SC_N * 8, &psc)) != 0) break;
+    if ((r = sc.get(q * 8, &puc)) != 0) break;
+    if ((r = sc.get(bytes_w, &pw)) != 0) break;
+    if ((r = sc.get(Mp * 4, &pmask)) != 0) break;
     double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
     if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -482,21 +414,21 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
       r = -2;
       break;
     }
-    double *Wc = (double*)pW, *U = (double*)pU, *mu = (double*)pmu, *v = (double*)pv, *hd = (double*)pss;
+    double *Wc = pW, *U = pU, *mu = pmu, *v = pv, *hd = pss;
     // ---- set-up: gpx_acq's posterior pass, operation for operation, with W kept ----
     for (int64_t j0 = 0; j0 < Mp && r == 0; j0 += mcw) {
       const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
       const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
-      double* B = oop ? (double*)pB : Wc + j0;
+      double* B = oop ? pB : Wc + j0;
       const int64_t ldc = oop ? gpx_skew_ld(mcp) : ld;
       if ((r = launch_kfill(ctx, kp, X->p, n, Cm->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldc)) != 0) break;
-      if ((r = launch_colreduce(ctx, B, ldc, n, mcp, (const double*)pal, mu + j0, (double*)ppart)) != 0) break;
+      if ((r = launch_colreduce(ctx, B, ldc, n, mcp, pal, mu + j0, ppart)) != 0) break;
       if (oop) r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldc, Wc + j0, ld, mcp);
       else r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldc, np, mcp);
     }
     if (r != 0) break;
-    if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, (double*)ppart)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Cm->p, M, (double*)pkd)) != 0) break;
+    if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, ppart)) != 0) break;
+    if ((r = launch_kdiag(ctx, kp, Cm->p, M, pkd)) != 0) break;
     hipLaunchKernelGGL(acq_batch_v_kernel, gM, dim3(256), 0, ctx->stream, (const double*)pkd, (const double*)hd, M, v);
     if (hipGetLastError() != hipSuccess) {
       r = -2;
@@ -509,9 +441,9 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
         ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
         hipLaunchKernelGGL(acq_batch_kernel, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M, t > 0 ? 1 : 0,
                            s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
-                           (const int*)pmask, (double*)pcost, (double*)ppc, (int64_t*)ppi);
+                           (const int*)pmask, pcost, ppc, ppi);
         hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                           (double*)pbc, (int64_t*)pbi);
+                           pbc, pbi);
       }
       double c = 0.0;
       if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -532,36 +464,20 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
       if (t + 1 == q && !out_lie) break;
       hipLaunchKernelGGL(acq_pick_kernel, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
                          (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
-                         (double*)psc, (double*)puc, (double*)pw, (int*)pmask);
+                         psc, puc, pw, pmask);
       if (hipGetLastError() != hipSuccess ||
-          (out_lie && hipMemcpyAsync(out_lie + t, (double*)psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
+          (out_lie && hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
         r = -2;
         break;
       }
       if (t + 1 == q) break;
-      if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, (const double*)pw, hd, (double*)ppart)) != 0) break;
+      if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, pw, hd, ppart)) != 0) break;
     }
   } while (0);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (pW) gpx_dev_release(ctx, pW, bytesW);
-  if (pB) gpx_dev_release(ctx, pB, bytesB);
-  if (pU) gpx_dev_release(ctx, pU, bytesU);
-  if (pal) gpx_dev_release(ctx, pal, np * 8);
-  if (pmu) gpx_dev_release(ctx, pmu, bytesM);
-  if (pv) gpx_dev_release(ctx, pv, bytesM);
-  if (pkd) gpx_dev_release(ctx, pkd, bytesM);
-  if (pss) gpx_dev_release(ctx, pss, bytesM);
-  if (ppart) gpx_dev_release(ctx, ppart, bytes_part);
-  if (pcost) gpx_dev_release(ctx, pcost, M * 8);
-  if (ppc) gpx_dev_release(ctx, ppc, nparts * 8);
-  if (ppi) gpx_dev_release(ctx, ppi, nparts * 8);
-  if (pbc) gpx_dev_release(ctx, pbc, 8);
-  if (pbi) gpx_dev_release(ctx, pbi, 8);
-  if (psc) gpx_dev_release(ctx, psc, SC_N * 8);
-  if (puc) gpx_dev_release(ctx, puc, q * 8);
-  if (pw) gpx_dev_release(ctx, pw, bytes_w);
-  if (pmask) gpx_dev_release(ctx, pmask, Mp * 4);
-  if (r == -2) gpx_set_error("acq batch: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  if (r == -2) {
+    (void)hipStreamSynchronize(ctx->stream);
+    gpx_set_error("acq batch: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  }
   return r;
 }
 

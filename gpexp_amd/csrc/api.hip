@@ -61,6 +61,7 @@ int gpx_dev_alloc(gpx_ctx* ctx, int64_t bytes, void** out) {
   } else {
     *out = base;
   }
+  ctx->out_bytes += key;
   return 0;
 }
 
@@ -90,6 +91,7 @@ void gpx_dev_release(gpx_ctx* ctx, void* p, int64_t bytes) {
   }
   ctx->pool.insert({key, base});
   ctx->pool_bytes += key;
+  ctx->out_bytes -= key;
 }
 
 // ---- profiling -------------------------------------------------------------------------------------
@@ -383,6 +385,7 @@ int gpx_create(int device, gpx_ctx** out) {
   c->guard_violations = 0;
   c->device = device;
   c->pool_bytes = 0;
+  c->out_bytes = 0;
   c->comm = nullptr;
   c->rank = 0;
   c->world = 1;
@@ -515,6 +518,15 @@ int gpx_dbg_spin_until(gpx_ctx* ctx, int slot, int64_t us) {
 }
 
 int64_t gpx_dbg_guard_violations(gpx_ctx* ctx) { return ctx ? (ctx->guard ? ctx->guard_violations : -1) : -1; }
+
+// bytes cached in the pool / handed out and not yet returned, both counted in pool keys (the rounded size a block is filed under):
+// a call that returns every block under the size it took it with leaves outstanding_bytes where it found it
+int gpx_dbg_pool_stats(gpx_ctx* ctx, int64_t* pooled_bytes, int64_t* outstanding_bytes) {
+  GPX_ARG(ctx != nullptr, "ctx is NULL");
+  if (pooled_bytes) *pooled_bytes = ctx->pool_bytes;
+  if (outstanding_bytes) *outstanding_bytes = ctx->out_bytes;
+  return 0;
+}
 
 // writes 16 bytes past a scratch block on purpose and returns 1 if the guard check caught it (the count is restored)
 int gpx_dbg_guard_selftest(gpx_ctx* ctx) {
@@ -831,23 +843,16 @@ int gpx_kfill_into(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
   GPX_ARG(symmetric || nugget_len == 0, "nugget only applies to the symmetric form");
   GPX_ARG(nugget_len == 0 || nugget != nullptr, "nugget is NULL");
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Bp));
+  Scratch sc(ctx);
   double* d_nug = nullptr;
-  int64_t nug_bytes = 0;
   double nscal = 0.0;
   if (nugget_len == 1) nscal = nugget[0];
   if (nugget_len > 1) {
-    nug_bytes = nugget_len * 8;
-    void* p;
-    GPX_TRY(gpx_dev_alloc(ctx, nug_bytes, &p));
-    d_nug = (double*)p;
-    GPX_HIP(hipMemcpyAsync(d_nug, nugget, (size_t)nug_bytes, hipMemcpyHostToDevice, ctx->stream));
+    GPX_TRY(sc.get(nugget_len * 8, &d_nug));
+    GPX_HIP(hipMemcpyAsync(d_nug, nugget, (size_t)nugget_len * 8, hipMemcpyHostToDevice, ctx->stream));
   }
   int r = launch_kfill(ctx, kp, X->p, X->rows, Bp->p, Bp->rows, symmetric, d_nug, nugget_len, nscal, K->p,
                        K->prows, K->pcols, K->ld);
-  if (d_nug) {
-    (void)hipStreamSynchronize(ctx->stream);
-    gpx_dev_release(ctx, d_nug, nug_bytes);
-  }
   K->binv_ib = 0;  // block inverses (chol_potrs) belong to the previous contents
   K->factored = 0;
   return r;
@@ -873,15 +878,14 @@ int gpx_kdiag(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const 
   GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
   GPX_ARG(Z->cols == d && Z->pcols == d, "Z must be an unpadded (M x d) point set");
   if (Z->rows == 0) return 0;
-  void* p;
-  GPX_TRY(gpx_dev_alloc(ctx, Z->rows * 8, &p));
-  int r = launch_kdiag(ctx, kp, Z->p, Z->rows, (double*)p);
+  Scratch sc(ctx);   // (its scope exit completes the copy)
+  double* p;
+  GPX_TRY(sc.get(Z->rows * 8, &p));
+  int r = launch_kdiag(ctx, kp, Z->p, Z->rows, p);
   if (r == 0) {
     hipError_t e = hipMemcpyAsync(out, p, (size_t)Z->rows * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e != hipSuccess) r = -2;
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  gpx_dev_release(ctx, p, Z->rows * 8);
   return r;
 }
 
@@ -1018,8 +1022,8 @@ int gpx_refit_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
   GPX_TRY(gpx_mat_new(ctx, n, n, 1, &K));
   const int64_t np = K->prows;
   int r = 0;
+  Scratch sc(ctx);
   double* d_nug = nullptr;
-  int64_t nug_bytes = 0;
   do {
     K->aux_bytes = np * GPX_TILE * 8;
     void* pa;
@@ -1051,11 +1055,8 @@ int gpx_refit_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
     double nscal = 0.0;
     if (nugget_len == 1) nscal = nugget[0];
     if (nugget_len > 1) {
-      nug_bytes = nugget_len * 8;
-      void* pn;
-      if ((r = gpx_dev_alloc(ctx, nug_bytes, &pn)) != 0) break;
-      d_nug = (double*)pn;
-      if (hipMemcpyAsync(d_nug, nugget, (size_t)nug_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      if ((r = sc.get(nugget_len * 8, &d_nug)) != 0) break;
+      if (hipMemcpyAsync(d_nug, nugget, (size_t)nugget_len * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
         r = -2; gpx_set_error("refit_rows: nugget upload failed"); break;
       }
     }
@@ -1074,20 +1075,19 @@ int gpx_refit_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
         const bool wide = keep >= 4096 && n2 <= 2048 && Lold->prows >= 2048;
         if (wide) {
           const int64_t ib = chol_binv_order(Lold->prows), nbat = keep / kc, rem = keep - nbat * kc;
-          void *pT = nullptr, *pP = nullptr;
+          double *pT = nullptr, *pP = nullptr;
           const int64_t tcap = std::max<int64_t>(4 * n2 * ib, 2 * n2 * keep);   // (the solve runs its few-row products as slices)
-          const int64_t tb = tcap * 8, pb = nbat * n2 * n2 * 8;
-          if ((r = gpx_dev_alloc(ctx, tb, &pT)) != 0) break;
-          if ((r = gpx_dev_alloc(ctx, pb, &pP)) != 0) { gpx_dev_release(ctx, pT, tb); break; }
-          r = chol_trsm_right_leading(ctx, const_cast<gpx_mat*>(Lold), keep, A21, K->ld, n2, (double*)pT, tcap);
-          if (r == 0)
-            r = launch_gemm_batched(ctx, A21, K->ld, kc, A21, K->ld, kc, (double*)pP, n2, n2 * n2, n2, n2, kc, true, false, nbat);
-          if (r == 0) r = launch_sub_partials(ctx, (const double*)pP, nbat, n2, A21 + keep, K->ld);
-          if (r == 0 && rem > 0)
-            r = launch_gemm(ctx, A21 + nbat * kc, K->ld, A21 + nbat * kc, K->ld, A21 + keep, K->ld, n2, n2, rem, true, true, true);
-          (void)hipStreamSynchronize(ctx->stream);
-          gpx_dev_release(ctx, pT, tb);
-          gpx_dev_release(ctx, pP, pb);
+          {
+            Scratch wide_sc(ctx);   // back to the pool before the factorisation of the new rows asks it for its own scratch
+            if ((r = wide_sc.get(tcap * 8, &pT)) != 0) break;
+            if ((r = wide_sc.get(nbat * n2 * n2 * 8, &pP)) != 0) break;
+            r = chol_trsm_right_leading(ctx, const_cast<gpx_mat*>(Lold), keep, A21, K->ld, n2, pT, tcap);
+            if (r == 0)
+              r = launch_gemm_batched(ctx, A21, K->ld, kc, A21, K->ld, kc, pP, n2, n2 * n2, n2, n2, kc, true, false, nbat);
+            if (r == 0) r = launch_sub_partials(ctx, (const double*)pP, nbat, n2, A21 + keep, K->ld);
+            if (r == 0 && rem > 0)
+              r = launch_gemm(ctx, A21 + nbat * kc, K->ld, A21 + nbat * kc, K->ld, A21 + keep, K->ld, n2, n2, rem, true, true, true);
+          }
           if (r != 0) break;
         } else {
           // (against the OLD factor: the copy may still be in flight)
@@ -1112,7 +1112,6 @@ int gpx_refit_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
   //  an error between the fork and the join leaves the copy of the kept rows in flight on the side stream: it writes K
   // and reads Lold -- both may be freed right after this returns
   if (ctx->ev_side && ctx->streams[4] != ctx->stream) (void)hipStreamSynchronize(ctx->streams[4]);
-  if (d_nug) gpx_dev_release(ctx, d_nug, nug_bytes);
   if (r != 0) {
     gpx_mat_free(ctx, K);
     return r;
@@ -1132,23 +1131,17 @@ int gpx_potrs(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* alpha) {
   GPX_TRY(need_factor(L));
   const int64_t n = L->rows, np = L->prows;
   const int64_t sb = chol_potrs_scratch_bytes(np);
-  void *p, *ps;
-  GPX_TRY(gpx_dev_alloc(ctx, np * 8, &p));
-  int r = gpx_dev_alloc(ctx, sb, &ps);
-  if (r != 0) {
-    gpx_dev_release(ctx, p, np * 8);
-    return r;
-  }
-  double* dv = (double*)p;
+  Scratch sc(ctx);   // (its scope exit completes the copy of alpha)
+  double *dv, *ps;
+  GPX_TRY(sc.get(np * 8, &dv));
+  GPX_TRY(sc.get(sb, &ps));
+  int r = 0;
   do {
     if (hipMemsetAsync(dv, 0, (size_t)np * 8, ctx->stream) != hipSuccess) { r = -2; break; }
     if (hipMemcpyAsync(dv, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
-    if ((r = chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, (double*)ps)) != 0) break;  // caches the block inverses in L
+    if ((r = chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, ps)) != 0) break;  // caches the block inverses in L
     if (hipMemcpyAsync(alpha, dv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
   } while (0);
-  (void)hipStreamSynchronize(ctx->stream);
-  gpx_dev_release(ctx, dv, np * 8);
-  gpx_dev_release(ctx, ps, sb);
   if (r == -2) gpx_set_error("potrs: HIP copy failed");
   return r;
 }
@@ -1233,19 +1226,17 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
   if (M == 0) return 0;
   const int64_t mcmax = eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  void *pB = nullptr, *pW = nullptr, *pal = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
+  double *pB = nullptr, *pW = nullptr, *pal = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
   // from 2048 training points the solve goes through the explicit block inverses, out of place (chol_trsm_left_oop)
   const bool oop = var && np >= 2048;
   const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
   const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
   const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
   int r = 0;
-  void* pvar = nullptr;  // all M variances, device (when the caller did not bring its own)
+  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
   do {
-    if (var && !var_dev) {
-      if ((r = gpx_dev_alloc(ctx, M * 8, &pvar)) != 0) break;
-      var_dev = (double*)pvar;
-    }
+    // all M variances, device (when the caller did not bring its own)
+    if (var && !var_dev && (r = sc.get(M * 8, &var_dev)) != 0) break;
     // keepW: the solved W = L^-1 K(X, Z) stays, as a matrix of its own, for the cost's gradient at the same design
     // (gpx_ivar_grad_w) -- when all of Z is one chunk; it then IS the buffer the solution lands in
     gpx_mat* Wm = nullptr;
@@ -1255,17 +1246,18 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
       Wm = nullptr;
     }
     if (Wm) *keepW = Wm;
+    // (the kept matrix's buffer serves as pB or pW; it belongs to the gpx_mat and never goes through the scratch owner)
     if (Wm && !oop) pB = Wm->p;
-    else if ((r = gpx_dev_alloc(ctx, bytesB, &pB)) != 0) break;
+    else if ((r = sc.get(bytesB, &pB)) != 0) break;
     if (oop) {
       if (Wm) pW = Wm->p;
-      else if ((r = gpx_dev_alloc(ctx, bytesB, &pW)) != 0) break;
+      else if ((r = sc.get(bytesB, &pW)) != 0) break;
     }
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pout)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pkd)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
+    if ((r = sc.get(bytes_out, &pout)) != 0) break;
+    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
+    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
     if (mean) {
-      if ((r = gpx_dev_alloc(ctx, np * 8, &pal)) != 0) break;
+      if ((r = sc.get(np * 8, &pal)) != 0) break;
       if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
           hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
         r = -2;
@@ -1275,12 +1267,12 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
     for (int64_t j0 = 0; j0 < M && r == 0; j0 += mcmax) {
       const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
       const int64_t mcp = gpx_round_up(mc, GPX_TILE);
-      double* B = (double*)pB;
+      double* B = pB;
       const double* Zc = Z->p + j0 * d;
       const int64_t ldb = gpx_skew_ld(mcp);
       if ((r = launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb)) != 0) break;
       if (mean) {
-        if ((r = launch_colreduce(ctx, B, ldb, n, mcp, (const double*)pal, (double*)pout, (double*)ppart)) != 0) break;
+        if ((r = launch_colreduce(ctx, B, ldb, n, mcp, pal, pout, ppart)) != 0) break;
         if (hipMemcpyAsync(mean + j0, pout, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
           r = -2;
           break;
@@ -1289,13 +1281,13 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
       if (var) {
         const double* Wsol = B;
         if (oop) {
-          if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, (double*)pW, ldb, mcp)) != 0) break;
-          Wsol = (const double*)pW;
+          if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, pW, ldb, mcp)) != 0) break;
+          Wsol = pW;
         } else if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp)) != 0) {
           break;
         }
-        if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, (double*)pout, (double*)ppart)) != 0) break;
-        if ((r = launch_kdiag(ctx, kp, Zc, mc, (double*)pkd)) != 0) break;
+        if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, pout, ppart)) != 0) break;
+        if ((r = launch_kdiag(ctx, kp, Zc, mc, pkd)) != 0) break;
         hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
                            (const double*)pout, mc, var_dev + j0);
       }
@@ -1304,21 +1296,13 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
         hipMemcpyAsync(var_host, var_dev, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       r = -2;
   } while (0);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (pvar) gpx_dev_release(ctx, pvar, M * 8);
-  {
-    gpx_mat* Wm = keepW ? *keepW : nullptr;
-    if (pB && !(Wm && pB == (void*)Wm->p)) gpx_dev_release(ctx, pB, bytesB);
-    if (pW && !(Wm && pW == (void*)Wm->p)) gpx_dev_release(ctx, pW, bytesB);
-    if (Wm && r != 0) {
-      gpx_mat_free(ctx, Wm);
+  if (r != 0) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (keepW && *keepW) {
+      gpx_mat_free(ctx, *keepW);
       *keepW = nullptr;
     }
   }
-  gpx_dev_release(ctx, pout, bytes_out);
-  gpx_dev_release(ctx, pkd, bytes_out);
-  gpx_dev_release(ctx, ppart, bytes_part);
-  if (pal) gpx_dev_release(ctx, pal, np * 8);
   if (r == -2) gpx_set_error("posterior: HIP copy failed: %s", hipGetErrorString(hipGetLastError()));
   return r;
 }
@@ -1370,15 +1354,14 @@ static int ivar_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp,
   GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
   GPX_ARG(Z->rows > 0, "IVAR needs at least one integration point");
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
-  void* pv;
-  GPX_TRY(gpx_dev_alloc(ctx, Z->rows * 8, &pv));
-  int r = posterior_impl(ctx, kp, L, X, nullptr, Z, nullptr, nullptr, (double*)pv, W);
+  Scratch sc(ctx);   // (its scope exit completes the copy of the cost)
+  double* pv;
+  GPX_TRY(sc.get(Z->rows * 8, &pv));
+  int r = posterior_impl(ctx, kp, L, X, nullptr, Z, nullptr, nullptr, pv, W);
   if (r == 0) {
-    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, (double*)pv, Z->rows, ctx->d_scal);
+    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, Z->rows, ctx->d_scal);
     if (hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  gpx_dev_release(ctx, pv, Z->rows * 8);
   if (r == -2) gpx_set_error("ivar: HIP copy failed");
   if (r != 0 && W && *W) {
     gpx_mat_free(ctx, *W);
@@ -1407,30 +1390,26 @@ int gpx_ivar_update(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   const int64_t n2 = n - keep, n2p = np - keep, ldw = W->ld;
   const int64_t bytes_out = mcp * 8, bytes_part = colreduce_partial_elems(np, mcp) * 8 + 8;
-  void *pout = nullptr, *pkd = nullptr, *ppart = nullptr, *pv = nullptr;
+  Scratch sc(ctx);   // (its scope exit completes the copy of the cost)
+  double *pout = nullptr, *pkd = nullptr, *ppart = nullptr, *pv = nullptr;
   int r = 0;
   do {
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pout)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_out, &pkd)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, bytes_part, &ppart)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, M * 8, &pv)) != 0) break;
+    if ((r = sc.get(bytes_out, &pout)) != 0) break;
+    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
+    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
+    if ((r = sc.get(M * 8, &pv)) != 0) break;
     double* W2 = W->p + keep * ldw;
     if ((r = launch_kfill(ctx, kp, X->p + keep * d, n2, Z->p, M, 0, nullptr, 0, 0.0, W2, n2p, mcp, ldw)) != 0) break;
     if ((r = launch_gemm(ctx, L->p + keep * L->ld, L->ld, W->p, ldw, W2, ldw, n2p, mcp, keep, false, true, false)) != 0) break;
     if ((r = chol_trsm_left(ctx, L->p + keep * (L->ld + 1), L->ld, L->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, W2, ldw, n2p,
                             mcp)) != 0) break;
-    if ((r = launch_colreduce(ctx, W->p, ldw, n, mcp, nullptr, (double*)pout, (double*)ppart)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Z->p, M, (double*)pkd)) != 0) break;
+    if ((r = launch_colreduce(ctx, W->p, ldw, n, mcp, nullptr, pout, ppart)) != 0) break;
+    if ((r = launch_kdiag(ctx, kp, Z->p, M, pkd)) != 0) break;
     hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                       (const double*)pout, M, (double*)pv);
-    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, (double*)pv, M, ctx->d_scal);
+                       (const double*)pout, M, pv);
+    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, M, ctx->d_scal);
     if (hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
   } while (0);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (pout) gpx_dev_release(ctx, pout, bytes_out);
-  if (pkd) gpx_dev_release(ctx, pkd, bytes_out);
-  if (ppart) gpx_dev_release(ctx, ppart, bytes_part);
-  if (pv) gpx_dev_release(ctx, pv, M * 8);
   if (r == -2) gpx_set_error("ivar_update: HIP copy failed");
   return r;
 }
@@ -1464,17 +1443,12 @@ int gpx_fit_ivar(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, gpx
 // out[j] = sum_{i < rows} B[i][j]^2 for the logical columns of B (host out[B->cols]); deterministic
 int gpx_col_sumsq(gpx_ctx* ctx, const gpx_mat* B, int64_t rows, double* out) {
   GPX_ARG(ctx && B && out && rows >= 0 && rows <= B->prows, "bad arguments");
-  void *po, *pp;
-  const int64_t bytes_part = colreduce_partial_elems(B->prows, B->pcols) * 8 + 8;
-  GPX_TRY(gpx_dev_alloc(ctx, B->pcols * 8, &po));
-  int r = gpx_dev_alloc(ctx, bytes_part, &pp);
-  if (r == 0) {
-    r = launch_colreduce(ctx, B->p, B->ld, rows, B->pcols, nullptr, (double*)po, (double*)pp);
-    if (r == 0 && hipMemcpyAsync(out, po, (size_t)B->cols * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
-    (void)hipStreamSynchronize(ctx->stream);
-    gpx_dev_release(ctx, pp, bytes_part);
-  }
-  gpx_dev_release(ctx, po, B->pcols * 8);
+  Scratch sc(ctx);   // (its scope exit completes the copy)
+  double *po, *pp;
+  GPX_TRY(sc.get(B->pcols * 8, &po));
+  GPX_TRY(sc.get(colreduce_partial_elems(B->prows, B->pcols) * 8 + 8, &pp));
+  int r = launch_colreduce(ctx, B->p, B->ld, rows, B->pcols, nullptr, po, pp);
+  if (r == 0 && hipMemcpyAsync(out, po, (size_t)B->cols * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
   if (r == -2) gpx_set_error("col_sumsq: HIP copy failed");
   return r;
 }
@@ -1483,20 +1457,17 @@ int gpx_col_sumsq(gpx_ctx* ctx, const gpx_mat* B, int64_t rows, double* out) {
 int gpx_matvec(gpx_ctx* ctx, const gpx_mat* A, const double* v, double* out) {
   GPX_ARG(ctx && A && v && out, "NULL argument");
   GPX_ARG(A->pcols % 2 == 0 && A->ld % 2 == 0, "matvec needs an even padded width");
-  void *pv, *po;
-  GPX_TRY(gpx_dev_alloc(ctx, A->pcols * 8, &pv));
-  int r = gpx_dev_alloc(ctx, (A->rows > 0 ? A->rows : 1) * 8, &po);
-  if (r == 0) {
-    do {
-      if (hipMemsetAsync(pv, 0, (size_t)A->pcols * 8, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(pv, v, (size_t)A->cols * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
-      if ((r = launch_rowreduce(ctx, A->p, A->ld, A->rows, A->pcols, (const double*)pv, (double*)po)) != 0) break;
-      if (hipMemcpyAsync(out, po, (size_t)A->rows * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    } while (0);
-    (void)hipStreamSynchronize(ctx->stream);
-    gpx_dev_release(ctx, po, (A->rows > 0 ? A->rows : 1) * 8);
-  }
-  gpx_dev_release(ctx, pv, A->pcols * 8);
+  Scratch sc(ctx);   // (its scope exit completes the copy)
+  double *pv, *po;
+  GPX_TRY(sc.get(A->pcols * 8, &pv));
+  GPX_TRY(sc.get((A->rows > 0 ? A->rows : 1) * 8, &po));
+  int r = 0;
+  do {
+    if (hipMemsetAsync(pv, 0, (size_t)A->pcols * 8, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(pv, v, (size_t)A->cols * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
+    if ((r = launch_rowreduce(ctx, A->p, A->ld, A->rows, A->pcols, pv, po)) != 0) break;
+    if (hipMemcpyAsync(out, po, (size_t)A->rows * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
+  } while (0);
   if (r == -2) gpx_set_error("matvec: HIP copy failed");
   return r;
 }
@@ -1557,14 +1528,11 @@ int gpx_dbg_gemm_ksplit(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_ma
   GPX_ARG(ctx && A && B && C && mode >= 0 && mode <= 3 && parts > 0, "bad argument");
   const int64_t m = C->prows, n = C->pcols, k = A->pcols;
   GPX_ARG(A->prows == m && B->prows == n && B->pcols == k, "operand shapes");
-  void* P;
-  const int64_t pb = (int64_t)parts * m * n * 8;
-  GPX_TRY(gpx_dev_alloc(ctx, pb, &P));
-  int r = mode <= 1 ? launch_gemm_ksplit(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, mode == 1, parts, (double*)P)
-                    : launch_gemm_ksplit_small(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, mode == 3, parts, (double*)P);
-  (void)hipStreamSynchronize(ctx->stream);
-  gpx_dev_release(ctx, P, pb);
-  return r;
+  Scratch sc(ctx);
+  double* P;
+  GPX_TRY(sc.get((int64_t)parts * m * n * 8, &P));
+  return mode <= 1 ? launch_gemm_ksplit(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, mode == 1, parts, P)
+                   : launch_gemm_ksplit_small(ctx, A->p, A->ld, B->p, B->ld, C->p, C->ld, m, n, k, mode == 3, parts, P);
 }
 
 int gpx_dbg_gemm(gpx_ctx* ctx, const gpx_mat* A, const gpx_mat* B, gpx_mat* C, int bt, int accumulate, int lower) {

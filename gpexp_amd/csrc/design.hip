@@ -9,7 +9,7 @@
 //                        cov(Z,C|X) = K(Z,C) - W_Z^T W_C as one MFMA GEMM instead of M refits.
 //  gpx_posterior_cov     GP.evaluate(compvar=2) (gp.py:146-152).
 //  gpx_potri             explicit K^-1 for the lazy GP.precisionMatrix attribute (gp.py:181).
-#include "gpx_internal.h"
+#include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -26,7 +26,8 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
   for (int r = ty; r < 32; r += 8) out[(j0 + r) * ldo + i0 + tx] = tile[tx][r];
 }
 
-// upper triangle <- transpose of the lower one (32 x 32 tiles, grid = tiles x tiles; tiles above the diagonal exit)
+// upper triangle <- transpose of the lower one (32 x 32 tiles, grid = tiles x tiles; tiles above the diagonal exit).  grad.hip's
+// mirror_lower_tri_kernel does the same from a linear index over the lower tiles only: another kernel, another launch shape.
 __global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ P, int64_t ld) {
   if (blockIdx.x > blockIdx.y) return;
   __shared__ double tile[32][33];
@@ -69,15 +70,7 @@ __global__ __launch_bounds__(256) void greedy_row_kernel(KParams kp, const doubl
 }
 
 // first-maximum arg-max of d[c]*w[c] (np.argmax tie rule: lowest index), two stages, deterministic
-struct VI {
-  double v;
-  int64_t i;
-};
-__device__ __forceinline__ VI vi_max(VI a, VI b) {
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
-
+// (VI, vi_max / vi_min and the block tree: gpx_device.h)
 __global__ __launch_bounds__(256) void argmax_stage1(const double* __restrict__ d, const double* __restrict__ w,
                                                      int64_t M, double* __restrict__ pv, int64_t* __restrict__ pi) {
   __shared__ double sv[256];
@@ -91,21 +84,10 @@ __global__ __launch_bounds__(256) void argmax_stage1(const double* __restrict__ 
     x.i = c;
     best = vi_max(best, x);
   }
-  sv[threadIdx.x] = best.v;
-  si[threadIdx.x] = best.i;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (threadIdx.x < h) {
-      VI a{sv[threadIdx.x], si[threadIdx.x]}, b{sv[threadIdx.x + h], si[threadIdx.x + h]};
-      VI m = vi_max(a, b);
-      sv[threadIdx.x] = m.v;
-      si[threadIdx.x] = m.i;
-    }
-    __syncthreads();
-  }
+  best = block_arg_reduce(best, sv, si, 256, vi_max);
   if (threadIdx.x == 0) {
-    pv[blockIdx.x] = sv[0];
-    pi[blockIdx.x] = si[0];
+    pv[blockIdx.x] = best.v;
+    pi[blockIdx.x] = best.i;
   }
 }
 
@@ -117,18 +99,8 @@ __global__ __launch_bounds__(256) void argmax_stage2(const double* __restrict__ 
   best.v = -INFINITY;
   best.i = INT64_MAX;
   for (int b = threadIdx.x; b < nb; b += 256) best = vi_max(best, VI{pv[b], pi[b]});
-  sv[threadIdx.x] = best.v;
-  si[threadIdx.x] = best.i;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (threadIdx.x < h) {
-      VI m = vi_max(VI{sv[threadIdx.x], si[threadIdx.x]}, VI{sv[threadIdx.x + h], si[threadIdx.x + h]});
-      sv[threadIdx.x] = m.v;
-      si[threadIdx.x] = m.i;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sel[slot] = si[0] == INT64_MAX ? 0 : si[0];  // all-NaN scores: index 0 like np.argmax
+  best = block_arg_reduce(best, sv, si, 256, vi_max);
+  if (threadIdx.x == 0) sel[slot] = best.i == INT64_MAX ? 0 : best.i;  // all-NaN scores: index 0 like np.argmax
 }
 
 __global__ __launch_bounds__(256) void keval_kernel(KParams kp, const double* __restrict__ A, int64_t sa,
@@ -146,21 +118,6 @@ __global__ __launch_bounds__(256) void ivar_cost_kernel(const double* __restrict
   if (j >= M) return;
   cost[j] = fabs((s0 - q[j] / (kcc[j] - ssc[j] + noise)) * inv_nmc);
 }
-
-struct Scratch {  // pooled device buffers released together
-  gpx_ctx* ctx;
-  std::vector<std::pair<void*, int64_t>> bufs;
-  explicit Scratch(gpx_ctx* c) : ctx(c) {}
-  int get(int64_t bytes, void** out) {
-    int r = gpx_dev_alloc(ctx, bytes, out);
-    if (r == 0) bufs.push_back({*out, bytes});
-    return r;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
-  }
-};
 
 int check_points(const gpx_mat* P, int d) {
   GPX_ARG(P && P->cols == d && P->pcols == d, "point sets must be unpadded (n x d)");
@@ -192,11 +149,6 @@ __global__ __launch_bounds__(256) void givar_cost_kernel(const double* __restric
   cost[j] = (c == c) ? c : INFINITY;
 }
 
-__device__ __forceinline__ VI vi_min(VI a, VI b) {
-  if (b.v < a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
-
 __global__ __launch_bounds__(256) void argmin_stage1(const double* __restrict__ c, int64_t M, double* __restrict__ pv,
                                                      int64_t* __restrict__ pi) {
   __shared__ double sv[256];
@@ -210,21 +162,10 @@ __global__ __launch_bounds__(256) void argmin_stage1(const double* __restrict__ 
     x.i = j;
     best = vi_min(best, x);
   }
-  sv[threadIdx.x] = best.v;
-  si[threadIdx.x] = best.i;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (threadIdx.x < h) {
-      VI a{sv[threadIdx.x], si[threadIdx.x]}, b{sv[threadIdx.x + h], si[threadIdx.x + h]};
-      VI m = vi_min(a, b);
-      sv[threadIdx.x] = m.v;
-      si[threadIdx.x] = m.i;
-    }
-    __syncthreads();
-  }
+  best = block_arg_reduce(best, sv, si, 256, vi_min);
   if (threadIdx.x == 0) {
-    pv[blockIdx.x] = sv[0];
-    pi[blockIdx.x] = si[0];
+    pv[blockIdx.x] = best.v;
+    pi[blockIdx.x] = best.i;
   }
 }
 
@@ -239,21 +180,10 @@ __global__ __launch_bounds__(256) void argmin_stage2(const double* __restrict__ 
     VI x{pv[b], pi[b]};
     best = vi_min(best, x);
   }
-  sv[threadIdx.x] = best.v;
-  si[threadIdx.x] = best.i;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (threadIdx.x < h) {
-      VI a{sv[threadIdx.x], si[threadIdx.x]}, b{sv[threadIdx.x + h], si[threadIdx.x + h]};
-      VI m = vi_min(a, b);
-      sv[threadIdx.x] = m.v;
-      si[threadIdx.x] = m.i;
-    }
-    __syncthreads();
-  }
+  best = block_arg_reduce(best, sv, si, 256, vi_min);
   if (threadIdx.x == 0) {
-    *out_v = sv[0];
-    *out_i = si[0];
+    *out_v = best.v;
+    *out_i = best.i;
   }
 }
 
@@ -293,12 +223,7 @@ __global__ __launch_bounds__(256) void givar_rr_kernel(double* __restrict__ buf,
   const double* r = buf + 2 + d;
   double acc = 0.0;
   for (int64_t i = threadIdx.x; i < zp; i += 256) acc = fma(r[i], r[i], acc);
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-    __syncthreads();
-  }
+  block_sum_256(sh, acc);
   if (threadIdx.x == 0) buf[1] = sh[0];
 }
 
@@ -669,7 +594,8 @@ int gpx_givar_begin(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   }
   int r = 0;
   void* p;
-  void *pWz = nullptr, *pWzt = nullptr, *pss = nullptr, *pkd = nullptr;
+  Scratch sc(ctx);   // the work buffers of the set-up; everything in `st` is resident state and stays with it
+  double *pWz = nullptr, *pWzt = nullptr, *pss = nullptr, *pkd = nullptr;
   const int64_t wide = zp > Mp ? zp : Mp;
   do {
     if ((r = gpx_dev_alloc(ctx, np * Mp * 8, &p)) != 0) break; st->Wc = (double*)p;
@@ -684,39 +610,35 @@ int gpx_givar_begin(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
     if ((r = gpx_dev_alloc(ctx, st->pack * 8, &p)) != 0) break; st->buf = (double*)p;
     if ((r = gpx_dev_alloc(ctx, 1024 * 8, &p)) != 0) break; st->red = (double*)p;
     if ((r = gpx_dev_alloc(ctx, 1024 * 8, &p)) != 0) break; st->redi = (int64_t*)p;
-    if ((r = gpx_dev_alloc(ctx, np * zp * 8, &pWz)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, np * zp * 8, &pWzt)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, wide * 8, &pss)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, wide * 8, &pkd)) != 0) break;
+    if ((r = sc.get(np * zp * 8, &pWz)) != 0) break;
+    if ((r = sc.get(np * zp * 8, &pWzt)) != 0) break;
+    if ((r = sc.get(wide * 8, &pss)) != 0) break;
+    if ((r = sc.get(wide * 8, &pkd)) != 0) break;
     // ---- integration points: W_Z = L^-1 K(X, Z), var_z, S0 -- the launches of gpx_greedy_ivar_step, in its order ----
-    if ((r = launch_kfill(ctx, kp, X->p, n, Z->p, nmc, 0, nullptr, 0, 0.0, (double*)pWz, np, zp, zp)) != 0) break;
-    if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, (double*)pWz, zp, np, zp)) != 0) break;
-    if ((r = launch_colreduce(ctx, (double*)pWz, zp, n, zp, nullptr, (double*)pss, st->part)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Z->p, nmc, (double*)pkd)) != 0) break;
+    if ((r = launch_kfill(ctx, kp, X->p, n, Z->p, nmc, 0, nullptr, 0, 0.0, pWz, np, zp, zp)) != 0) break;
+    if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, pWz, zp, np, zp)) != 0) break;
+    if ((r = launch_colreduce(ctx, pWz, zp, n, zp, nullptr, pss, st->part)) != 0) break;
+    if ((r = launch_kdiag(ctx, kp, Z->p, nmc, pkd)) != 0) break;
     std::vector<double> hs((size_t)nmc), hk((size_t)nmc);
     if (hipMemcpyAsync(hs.data(), pss, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
     if (hipMemcpyAsync(hk.data(), pkd, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    if ((r = launch_transpose(ctx, (double*)pWz, np, zp, zp, (double*)pWzt, np)) != 0) break;
+    if ((r = launch_transpose(ctx, pWz, np, zp, zp, pWzt, np)) != 0) break;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { r = -2; break; }
     for (int64_t j = 0; j < nmc; ++j) hk[(size_t)j] -= hs[(size_t)j];
     st->s0 = pairwise_sum(hk, nmc);
     // ---- candidates: W_C, v, G = K(Z, C) - W_Z^T W_C, q ----
     if ((r = launch_kfill(ctx, kp, X->p, n, Cm->p, M, 0, nullptr, 0, 0.0, st->Wc, np, Mp, Mp)) != 0) break;
     if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, st->Wc, Mp, np, Mp)) != 0) break;
-    if ((r = launch_colreduce(ctx, st->Wc, Mp, n, Mp, nullptr, (double*)pss, st->part)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Cm->p, M, (double*)pkd)) != 0) break;
+    if ((r = launch_colreduce(ctx, st->Wc, Mp, n, Mp, nullptr, pss, st->part)) != 0) break;
+    if ((r = launch_kdiag(ctx, kp, Cm->p, M, pkd)) != 0) break;
     hipLaunchKernelGGL(givar_v_kernel, dim3((unsigned)(Mp / 256 + 1)), dim3(256), 0, ctx->stream, (const double*)pkd,
                        (const double*)pss, M, Mp, st->v);
     if ((r = launch_kfill(ctx, kp, Z->p, nmc, Cm->p, M, 0, nullptr, 0, 0.0, st->G, zp, Mp, Mp)) != 0) break;
-    if ((r = launch_gemm(ctx, (double*)pWzt, np, st->Wc, Mp, st->G, Mp, zp, Mp, np, false, true, false)) != 0) break;
+    if ((r = launch_gemm(ctx, pWzt, np, st->Wc, Mp, st->G, Mp, zp, Mp, np, false, true, false)) != 0) break;
     if ((r = launch_colreduce(ctx, st->G, Mp, nmc, Mp, nullptr, st->q, st->part)) != 0) break;
     if (hipMemsetAsync(st->U, 0, (size_t)(nsel * Mp * 8), ctx->stream) != hipSuccess) { r = -2; break; }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { r = -2; break; }
   } while (0);
-  if (pWz) gpx_dev_release(ctx, pWz, np * zp * 8);
-  if (pWzt) gpx_dev_release(ctx, pWzt, np * zp * 8);
-  if (pss) gpx_dev_release(ctx, pss, wide * 8);
-  if (pkd) gpx_dev_release(ctx, pkd, wide * 8);
   if (r != 0) {
     gpx_givar_end(ctx, st);
     if (r == -2) gpx_set_error("givar_begin: HIP call failed");

@@ -129,25 +129,6 @@ int64_t eval_chunk(int64_t np) {
   return mc;
 }
 
-struct Tmp {  // scratch buffers released on scope exit (after a stream sync)
-  gpx_ctx* ctx;
-  std::vector<std::pair<void*, int64_t>> bufs;
-  explicit Tmp(gpx_ctx* c) : ctx(c) {}
-  int get(int64_t bytes, double** out) {
-    void* p;
-    int r = gpx_dev_alloc(ctx, bytes, &p);
-    if (r == 0) {
-      bufs.push_back({p, bytes});
-      *out = (double*)p;
-    }
-    return r;
-  }
-  ~Tmp() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
-  }
-};
-
 // Bt[m][i] *= s[i] (row-major m x cols, row stride ld)
 __global__ __launch_bounds__(256) void scale_cols_kernel(double* __restrict__ Bt, int64_t ld, const double* __restrict__ s,
                                                          int64_t cols) {
@@ -220,7 +201,7 @@ int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
   f->n = X->rows;
   f->nu = S->rows;
   f->noise = noise;
-  Tmp tmp(ctx);
+  Scratch tmp(ctx);
   do {
     // Lu = chol(K(S,S) + noise I)
     if ((r = gpx_mat_new(ctx, f->nu, f->nu, 1, &f->Lu)) != 0) break;
@@ -304,7 +285,7 @@ int gpx_fitc_shape(const gpx_fitc* f, int64_t* n, int64_t* nu) {
 // coeff = P y (host arrays of length n); quad = y^T P y
 int gpx_fitc_solve(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* coeff, double* quad) {
   GPX_ARG(ctx && f && y && coeff, "NULL argument");
-  Tmp tmp(ctx);
+  Scratch tmp(ctx);
   double *dy, *du, *dt, *part;
   GPX_TRY(tmp.get(f->np * 8, &dy));
   GPX_TRY(tmp.get(f->nup * 8, &du));
@@ -361,7 +342,7 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, X, Z));
   const int64_t mcmax = eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  Tmp tmp(ctx);
+  Scratch tmp(ctx);
   const int64_t ldb = gpx_skew_ld(np), ldu = gpx_skew_ld(nup);
   double *B, *U, *dc = nullptr, *o1, *o2, *kd;
   GPX_TRY(tmp.get(mc_alloc * ldb * 8, &B));
@@ -405,7 +386,7 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
 int gpx_fitc_dense(gpx_ctx* ctx, const gpx_fitc* f, double* cov, double* prec) {
   GPX_ARG(ctx && f, "NULL argument");
   const int64_t n = f->n, np = f->np, nup = f->nup;
-  Tmp tmp(ctx);
+  Scratch tmp(ctx);
   double *T, *C;
   const int64_t ldt = gpx_skew_ld(nup), ldc = gpx_skew_ld(np);
   GPX_TRY(tmp.get(np * ldt * 8, &T));

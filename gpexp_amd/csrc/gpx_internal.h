@@ -86,29 +86,6 @@ struct KParams {
 };
 int gpx_make_kparams(int kind, int d, const double* hyp, int nhyp, KParams* out);
 
-// ---- covariance value for a pair of points given in global memory (generic d; design.hip, acq.hip) ----
-static __device__ __forceinline__ double kpair(const KParams& kp, const double* __restrict__ a, const double* __restrict__ b) {
-  double acc = 0.0;
-  if (kp.kind == GPX_K_MEHLER) {
-    double pa = 0.0, pb = 0.0, cr = 0.0;
-    for (int k = 0; k < kp.d; ++k) {
-      const double x = a[k], y = b[k];
-      pa = fma(kp.c1[k] * x, x, pa);
-      pb = fma(kp.c1[k] * y, y, pb);
-      cr = fma(kp.c2[k] * x, y, cr);
-    }
-    return kp.sig * exp(-(pa + pb - cr));
-  }
-  for (int k = 0; k < kp.d; ++k) {
-    const double e = (a[k] - b[k]) * kp.scale[k];  // difference first, as the reference (kernels.py:121-122)
-    acc = fma(e, e, acc);
-  }
-  if (kp.kind == GPX_K_SE) return kp.sig * exp(-0.5 * acc);
-  const double t = sqrt(acc);
-  if (kp.kind == GPX_K_MATERN32) return kp.sig * (1.0 + t) * exp(-t);
-  return kp.sig * (1.0 + t + acc * (1.0 / 3.0)) * exp(-t);
-}
-
 // ---- objects --------------------------------------------------------------------------------------
 struct gpx_mat {
   double* p;
@@ -166,6 +143,7 @@ struct gpx_ctx {
   // cached device allocations (exact-size reuse)
   std::multimap<int64_t, void*> pool;
   int64_t pool_bytes;
+  int64_t out_bytes;   // handed out and not yet returned, in pool keys (gpx_dbg_pool_stats)
   // deferred release (gpx_mat_free): a freed matrix's buffers go back to the pool AT ONCE, tagged with a fence -- one event per
   // stream of the context, recorded at the time of the free; whoever takes such a block out of the pool waits for the fence
   // first (normally long complete).  Replaces a device-wide synchronisation per free.
@@ -219,6 +197,45 @@ int gpx_dev_alloc(gpx_ctx* ctx, int64_t bytes, void** out);
 void gpx_dev_release(gpx_ctx* ctx, void* p, int64_t bytes);
 int gpx_mat_new(gpx_ctx* ctx, int64_t rows, int64_t cols, int pad, gpx_mat** out);
 
+// The one owner of pooled scratch.  The pool is keyed by size and gpx_dev_release files a block under the byte count it is
+// TOLD, so the count is recorded once, where the block is taken, and every block goes back under it on scope exit -- error
+// paths included -- after the work queued on it has finished.  That wait is for the context's selected stream; Scratch::Device
+// waits for the whole device (grad.hip, whose passes use several of the context's streams).  An owner that took nothing does
+// not wait at all: that holds for EVERY user -- an early return before the first get() no longer synchronises the stream (what
+// such a path frees goes through gpx_mat_free, which is fenced) -- and keeps gpx_kfill_into without a nugget vector asynchronous.
+// Buffers that outlive the call (resident state, the fields of a gpx_mat) are never registered here.
+class Scratch {
+ public:
+  enum Sync { Stream, Device };
+  explicit Scratch(gpx_ctx* c, Sync s = Stream) : ctx(c), sync(s) {}
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  template <typename T>
+  int get(int64_t bytes, T** out) {
+    void* p = nullptr;
+    int r = gpx_dev_alloc(ctx, bytes, &p);
+    if (r == 0) {
+      adopt(p, bytes);
+      *out = (T*)p;
+    }
+    return r;
+  }
+  // a block the caller took from gpx_dev_alloc itself, with the byte count it asked for (loo.hip's shrinking slab, which must
+  // leave gpx_dev_alloc's own out-of-memory text in place while it retries)
+  void adopt(void* p, int64_t bytes) { bufs.push_back({p, bytes}); }
+  ~Scratch() {
+    if (bufs.empty()) return;
+    if (sync == Device) (void)hipDeviceSynchronize();
+    else (void)hipStreamSynchronize(ctx->stream);
+    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
+  }
+
+ private:
+  gpx_ctx* ctx;
+  Sync sync;
+  std::vector<std::pair<void*, int64_t>> bufs;
+};
+
 // RAII-ish profiling bracket: records events around launches of one class when profiling is on
 struct ProfScope {
   gpx_ctx* ctx;
@@ -228,15 +245,23 @@ struct ProfScope {
 };
 int gpx_prof_flush(gpx_ctx* ctx);
 
-// d rounded up to the instantiated register-array sizes of the per-point kernels templated on the dimension (grad.hip, acq.hip)
-#define GPX_SE_DISPATCH(d_, CALL) \
-  do {                            \
-    if ((d_) <= 1) { CALL(1); }   \
-    else if ((d_) <= 2) { CALL(2); } \
-    else if ((d_) <= 4) { CALL(4); } \
-    else if ((d_) <= 8) { CALL(8); } \
-    else if ((d_) <= 16) { CALL(16); } \
-    else { CALL(32); }            \
+// d rounded up to the instantiated register-array sizes of the per-point kernels templated on the dimension (grad.hip, acq.hip):
+// CALL(KIND, DMAX) for a kernel whose derivative is a radial factor times the coordinate difference (SE, Matern 3/2, Matern 5/2;
+// radial_pair in gpx_device.h)
+#define GPX_SE_DISPATCH(K_, d_, CALL)  \
+  do {                                 \
+    if ((d_) <= 1) { CALL(K_, 1); }    \
+    else if ((d_) <= 2) { CALL(K_, 2); } \
+    else if ((d_) <= 4) { CALL(K_, 4); } \
+    else if ((d_) <= 8) { CALL(K_, 8); } \
+    else if ((d_) <= 16) { CALL(K_, 16); } \
+    else { CALL(K_, 32); }             \
+  } while (0)
+#define GPX_RADIAL_DISPATCH(kind_, d_, CALL)                                    \
+  do {                                                                          \
+    if ((kind_) == GPX_K_SE) GPX_SE_DISPATCH(GPX_K_SE, d_, CALL);               \
+    else if ((kind_) == GPX_K_MATERN32) GPX_SE_DISPATCH(GPX_K_MATERN32, d_, CALL); \
+    else GPX_SE_DISPATCH(GPX_K_MATERN52, d_, CALL);                             \
   } while (0)
 
 // evaluation points per chunk of the posterior-shaped passes (gpx_posterior, gpx_acq): the N x chunk cross matrix under ~16 GiB,

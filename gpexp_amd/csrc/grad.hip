@@ -13,7 +13,9 @@
 // -- and the TRUE derivative for Matern (as acq.hip; t = kp.scale |u - p|, kp.scale = sqrt(3) / rho or sqrt(5) / rho):
 //     Matern32  -s (3 / rho^2) e^-t (u_l - p_l)
 //     Matern52  -s (5 / (3 rho^2)) (1 + t) e^-t (u_l - p_l)
-// both smooth at u = p, where they vanish: nothing divides by |u - p|.
+// both smooth at u = p, where they vanish: nothing divides by |u - p|.  The pair covariance (kpair), the radial pair of the
+// SE / Matern kernels (radial_pair) and the workgroup tree sum (block_sum_256) are the shared ones of gpx_device.h; the
+// kind-by-dimension dispatch (GPX_RADIAL_DISPATCH) and the scratch owner (Scratch) those of gpx_internal.h.
 // beta = K^-1 K(X, Z) (N x M, two triangular solves against the factor), nd[j][l] = d noise(x_j) / d x_jl (optional).
 // With c_jl[i] = dk(x_j, x_i)[l] + [x_i == x_j] nd[j][l]   (gp.py:310, 316: `indUse` marks coincident training points)
 // and  T_j[m][l] = -dk(z_m, x_j)[l]                        (gp.py:312)
@@ -21,51 +23,28 @@
 // The sum over i is one MFMA GEMM per coordinate (A_l = [c_jl[i]] is N x N, C_l = A_l beta); its column mean -- the IVAR
 // gradient -- collapses to one GEMM S = beta beta^T and a fused row kernel:
 //     d IVAR / d x_jl = 1/M ( -2 sum_m beta[j][m] T_j[m][l] + 2 sum_i c_jl[i] S[j][i] - c_jl[j] S[j][j] ).
-#include "gpx_internal.h"
+#include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
 
 namespace {
 
-// k(a, b) and, through `dk`, the reference's point derivative (SE any d; Mehler d == 1)
-__device__ __forceinline__ double kval(const KParams& kp, const double* __restrict__ a, const double* __restrict__ b) {
-  if (kp.kind == GPX_K_MEHLER) {
-    double pa = 0.0, pb = 0.0, cr = 0.0;
-    for (int k = 0; k < kp.d; ++k) {
-      pa = fma(kp.c1[k] * a[k], a[k], pa);
-      pb = fma(kp.c1[k] * b[k], b[k], pb);
-      cr = fma(kp.c2[k] * a[k], b[k], cr);
-    }
-    return kp.sig * exp(-(pa + pb - cr));
-  }
-  double r2 = 0.0;
-  for (int k = 0; k < kp.d; ++k) {
-    const double e = (a[k] - b[k]) * kp.scale[k];  // difference first (kernels.py:121-122)
-    r2 = fma(e, e, r2);
-  }
-  return kp.sig * exp(-0.5 * r2);
-}
-
+// the reference's point derivative through `dk` of k(a, b) = kpair (SE any d; Mehler d == 1)
 // d k(u, p) / d u_l given kv = k(u, p)
 __device__ __forceinline__ double dk(const KParams& kp, double ul, double pl, int l, double kv) {
   if (kp.kind == GPX_K_MEHLER) return -(2.0 * kp.c1[l] * ul - kp.c2[l] * pl) * kv;
   return -kp.sig * (ul - pl) * kp.scale[l] * kp.scale[l] * kv;
 }
 
-// d k(u, p) / d u_l for a pair of points (the element-wise kernels below).  SE, Mehler: dk of kval, as before.  Matern: the
-// radial factor times the difference -- it is not a multiple of k(u, p), so it does not go through kval / dk.
+// d k(u, p) / d u_l for a pair of points (the element-wise kernels below).  SE, Mehler: dk of kpair.  Matern: the radial
+// factor times the difference -- it is not a multiple of k(u, p), so it does not go through kpair / dk.
 __device__ __forceinline__ double dkpair(const KParams& kp, const double* __restrict__ u, const double* __restrict__ p, int l) {
   if (kp.kind == GPX_K_MATERN32 || kp.kind == GPX_K_MATERN52) {
-    double r2 = 0.0;
-    for (int k = 0; k < kp.d; ++k) {
-      const double e = (u[k] - p[k]) * kp.scale[k];
-      r2 = fma(e, e, r2);
-    }
-    const double t = sqrt(r2);
+    const double t = sqrt(scaled_dist2(kp, u, p));
     const double f = kp.kind == GPX_K_MATERN32 ? exp(-t) : (1.0 + t) * exp(-t) * (1.0 / 3.0);
     return -kp.sig * kp.scale[l] * kp.scale[l] * f * (u[l] - p[l]);
   }
-  return dk(kp, u[l], p[l], l, kval(kp, u, p));
+  return dk(kp, u[l], p[l], l, kpair(kp, u, p));
 }
 
 // coincident training points: np.linalg.norm(pp - p) < 1e-10 (gp.py:308)
@@ -79,7 +58,7 @@ __device__ __forceinline__ bool same_point(const double* __restrict__ a, const d
 // grad[a][l] = 1/M ( 2 sum_m Bm[a][m] dk(z_m, x_a)[l] + 2 sum_i c_al[i] S[a][i] - c_al[a] S[a][a] )
 // S (n x n, row stride ld, n a multiple of 32): the strictly upper triangle <- the transpose of the lower one.  One 32 x 32
 // tile pair per workgroup (blockIdx.x enumerates the tiles on / below the diagonal); a diagonal tile mirrors inside itself.
-__global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ S, int64_t ld, int nt) {
+__global__ __launch_bounds__(256) void mirror_lower_tri_kernel(double* __restrict__ S, int64_t ld, int nt) {
   __shared__ double tile[32][33];
   // tile (ti, tj), tj <= ti, from the linear index: ti (ti + 1) / 2 + tj
   int ti = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
@@ -116,7 +95,7 @@ __global__ __launch_bounds__(256) void ivar_grad_row_kernel(KParams kp, const do
   // evaluation points: -2 beta T = 2 beta dk(z, x_a)
   for (int64_t j = t; j < m; j += 256) {
     const double* z = Z + j * d;
-    const double w = 2.0 * Bm[a * ldb + j] * kval(kp, z, xa);
+    const double w = 2.0 * Bm[a * ldb + j] * kpair(kp, z, xa);
 #pragma unroll
     for (int l = 0; l < GPX_MAXD; ++l)
       if (l < d) acc[l] += dk(kp, z[l], xa[l], l, w);
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(256) void ivar_grad_row_kernel(KParams kp, const do
   for (int64_t i = t; i < n; i += 256) {
     const double* xi = X + i * d;
     const double sai = (i == a ? 1.0 : 2.0) * S[a * lds_ + i];
-    const double w = sai * kval(kp, xa, xi);
+    const double w = sai * kpair(kp, xa, xi);
     const bool dup = nd != nullptr && (i == a || same_point(xa, xi, d));
 #pragma unroll
     for (int l = 0; l < GPX_MAXD; ++l)
@@ -140,12 +119,7 @@ __global__ __launch_bounds__(256) void ivar_grad_row_kernel(KParams kp, const do
 #pragma unroll
     for (int q = 0; q < GPX_MAXD; ++q)
       if (q == l) v = acc[q];
-    red[t] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (t < w) red[t] += red[t + w];
-      __syncthreads();
-    }
+    block_sum_256(red, v);
     if (t == 0) grad[a * d + l] = inv_m * red[0];
     __syncthreads();
   }
@@ -157,28 +131,10 @@ __global__ __launch_bounds__(256) void ivar_grad_row_kernel(KParams kp, const do
 // above (kept for the Mehler kernel) unroll to GPX_MAXD = 32 predicated ones: 10.7 ms of gpx_ivar_grad's 120 at N = 8192,
 // M = 32768, d = 8 (3.4e8 pairs) against 1.3 ms of fp64 issue.  DMAX = d rounded up to a power of two.
 // The Matern derivatives have the same shape -- a radial factor times the difference (acq.hip) -- with one sqrt more per pair:
-//     KIND      radial_pair returns      radial_finish multiplies s_l by
+//     KIND      radial_pair (gpx_device.h)  radial_finish multiplies s_l by
 //     SE        s e^(-r2/2) = k(u, p)    -s scale_l^2
 //     Matern32  e^-t                     -s scale^2
 //     Matern52  (1 + t) e^-t             -s scale^2 / 3                   r2 = sum_l ((u_l - p_l) scale_l)^2, t = sqrt(r2)
-template <int KIND, int DMAX>
-__device__ __forceinline__ double radial_pair(const KParams& kp, const double* __restrict__ u, const double (&p)[DMAX],
-                                          double (&diff)[DMAX]) {
-  double r2 = 0.0;
-#pragma unroll
-  for (int l = 0; l < DMAX; ++l) {
-    diff[l] = 0.0;
-    if (l < kp.d) {
-      diff[l] = u[l] - p[l];
-      const double e = diff[l] * kp.scale[l];
-      r2 = fma(e, e, r2);
-    }
-  }
-  if (KIND == GPX_K_SE) return kp.sig * exp(-0.5 * r2);
-  const double t = sqrt(r2);
-  return KIND == GPX_K_MATERN32 ? exp(-t) : (1.0 + t) * exp(-t);
-}
-
 // c_l * s_l for every coordinate, reduced over the workgroup in the fixed tree order, written to out[0 .. d)
 template <int KIND, int DMAX>
 __device__ __forceinline__ void radial_finish(const KParams& kp, const double (&s1)[DMAX], double extra_w, const double* extra,
@@ -190,12 +146,7 @@ __device__ __forceinline__ void radial_finish(const KParams& kp, const double (&
       double v = -kp.sig * kp.scale[l] * kp.scale[l] * s1[l];
       if (KIND == GPX_K_MATERN52) v *= 1.0 / 3.0;
       if (extra) v += extra_w * extra[l];
-      red[t] = v;
-      __syncthreads();
-      for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-      }
+      block_sum_256(red, v);
       if (t == 0) out[l] = scale_out * red[0];
       __syncthreads();
     }
@@ -329,7 +280,7 @@ __global__ __launch_bounds__(256) void var_grad_newpt_kernel(KParams kp, const d
   for (int l = 0; l < GPX_MAXD; ++l) acc[l] = 0.0;
   for (int64_t j = t; j < n; j += 256) {
     const double* xj = X + j * d;
-    const double w = -2.0 * beta[j * ldb + mm] * kval(kp, zs, xj);
+    const double w = -2.0 * beta[j * ldb + mm] * kpair(kp, zs, xj);
 #pragma unroll
     for (int l = 0; l < GPX_MAXD; ++l)
       if (l < d) acc[l] += dk(kp, zs[l], xj[l], l, w);
@@ -339,40 +290,11 @@ __global__ __launch_bounds__(256) void var_grad_newpt_kernel(KParams kp, const d
 #pragma unroll
     for (int q = 0; q < GPX_MAXD; ++q)
       if (q == l) v = acc[q];
-    red[t] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (t < w) red[t] += red[t + w];
-      __syncthreads();
-    }
+    block_sum_256(red, v);
     if (t == 0) out[(col0 + mm) * d + l] = red[0];
     __syncthreads();
   }
 }
-
-struct Scratch {
-  gpx_ctx* ctx;
-  std::vector<std::pair<void*, int64_t>> bufs;
-  explicit Scratch(gpx_ctx* c) : ctx(c) {}
-  int get(int64_t bytes, void** out) {
-    int r = gpx_dev_alloc(ctx, bytes, out);
-    if (r == 0) bufs.push_back({*out, bytes});
-    return r;
-  }
-  ~Scratch() {
-    (void)hipDeviceSynchronize();
-    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
-  }
-};
-
-// CALL(KIND, DMAX) for a kernel whose derivative is a radial factor times the difference (SE, Matern 3/2, Matern 5/2), d rounded
-// up as GPX_SE_DISPATCH does it
-#define GPX_RADIAL_DISPATCH(kind_, d_, CALL)                               \
-  do {                                                                     \
-    if ((kind_) == GPX_K_SE) GPX_SE_DISPATCH(d_, CALL##_SE);               \
-    else if ((kind_) == GPX_K_MATERN32) GPX_SE_DISPATCH(d_, CALL##_M32);   \
-    else GPX_SE_DISPATCH(d_, CALL##_M52);                                  \
-  } while (0)
 
 int check_args(int kind, int d, const gpx_mat* L, const gpx_mat* X, const gpx_mat* Z, const gpx_fitc* fitc = nullptr) {
   GPX_ARG((L || fitc) && X && Z, "NULL argument");
@@ -465,19 +387,14 @@ int solve_beta(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat*
 int solve_scratch(gpx_ctx* ctx, Scratch& sc, int64_t np, int64_t mcp, double** T) {
   *T = nullptr;
   if (np < 4096) return 0;
-  void* p;
-  GPX_TRY(sc.get(mcp * chol_binv_order(np) * 8, &p));
-  *T = (double*)p;
-  return 0;
+  return sc.get(mcp * chol_binv_order(np) * 8, T);
 }
 
 int upload(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t count, double** dev) {
   *dev = nullptr;
   if (!host) return 0;
-  void* p;
-  GPX_TRY(sc.get(count * 8, &p));
-  GPX_HIP(hipMemcpyAsync(p, host, (size_t)count * 8, hipMemcpyHostToDevice, ctx->stream));
-  *dev = (double*)p;
+  GPX_TRY(sc.get(count * 8, dev));
+  GPX_HIP(hipMemcpyAsync(*dev, host, (size_t)count * 8, hipMemcpyHostToDevice, ctx->stream));
   return 0;
 }
 
@@ -509,7 +426,7 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   const int64_t n = L->rows, np = L->prows, m = Z->rows;
   const int64_t mp = gpx_round_up(m, GPX_TILE);
-  Scratch sc(ctx);
+  Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pW, *pWt, *pS, *pg;
   GPX_TRY(sc.get(np * mp * 8, &pW));
   GPX_TRY(sc.get(mp * np * 8, &pWt));
@@ -539,7 +456,7 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   }
   {
     const int nt = (int)(np / 32);
-    hipLaunchKernelGGL(mirror_lower_kernel, dim3((unsigned)((int64_t)nt * (nt + 1) / 2)), dim3(256), 0, ctx->stream, (double*)pS, np, nt);
+    hipLaunchKernelGGL(mirror_lower_tri_kernel, dim3((unsigned)((int64_t)nt * (nt + 1) / 2)), dim3(256), 0, ctx->stream, (double*)pS, np, nt);
     GPX_HIP(hipGetLastError());
   }
   {
@@ -549,13 +466,7 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   hipLaunchKernelGGL((ivar_grad_row_radial_kernel<K_, DM_>), dim3((unsigned)n), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, \
                      m, (const double*)W, mp, (const double*)pS, np, (const double*)d_nd, 1.0 / (double)m, (double*)pg,       \
                      (int64_t)0)
-#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
-#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
-#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
       GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
-#undef GPX_CALL_M52
-#undef GPX_CALL_M32
-#undef GPX_CALL_SE
 #undef GPX_CALL
     } else {
       hipLaunchKernelGGL(ivar_grad_row_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, m,
@@ -588,7 +499,7 @@ int gpx_ivar_grad_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhy
   GPX_ARG(W->rows == n && W->cols == m && W->prows == np && W->pcols == mp, "ivar_grad_rows: the kept solve has another shape");
   GPX_ARG(r0 > 0 && r0 < n && r0 % GPX_TILE == 0, "ivar_grad_rows: r0 must be a positive multiple of 128 below the number of points");
   const int64_t bp = np - r0, b = n - r0, ldw = W->ld;
-  Scratch sc(ctx);
+  Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pA, *pB, *pG, *pP = nullptr, *pT = nullptr, *pg;
   GPX_TRY(sc.get(mp * bp * 8, &pA));
   GPX_TRY(sc.get(bp * mp * 8, &pB));
@@ -621,13 +532,7 @@ int gpx_ivar_grad_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhy
 #define GPX_CALL(K_, DM_)                                                                                                     \
   hipLaunchKernelGGL((ivar_grad_row_radial_kernel<K_, DM_>), dim3((unsigned)b), dim3(256), 0, ctx->stream, kp, X->p, n, Z->p, \
                      m, (const double*)B, mp, (const double*)G, np, (const double*)nullptr, 1.0 / (double)m, (double*)pg, r0)
-#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
-#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
-#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
     GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
-#undef GPX_CALL_M52
-#undef GPX_CALL_M32
-#undef GPX_CALL_SE
 #undef GPX_CALL
   }
   GPX_HIP(hipGetLastError());
@@ -649,7 +554,7 @@ static int var_grad_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
   GPX_ARG(np <= 65535, "var_grad: at most 65535 training points");
   const int64_t mcmax = grad_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  Scratch sc(ctx);
+  Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pW, *pWt, *pA, *pO;
   GPX_TRY(sc.get(np * mc_alloc * 8, &pW));
   GPX_TRY(sc.get(np * mc_alloc * 8, &pWt));   // transpose scratch, then C_l
@@ -727,7 +632,7 @@ static int var_grad_newpt_impl(gpx_ctx* ctx, int kind, int d, const double* hyp,
   const int64_t n = fitc ? fitc_n(fitc) : L->rows, np = fitc ? fitc_np(fitc) : L->prows, M = Z->rows;
   const int64_t mcmax = grad_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  Scratch sc(ctx);
+  Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pW, *pWt, *pO;
   GPX_TRY(sc.get(np * mc_alloc * 8, &pW));
   GPX_TRY(sc.get(np * mc_alloc * 8, &pWt));
@@ -746,13 +651,7 @@ static int var_grad_newpt_impl(gpx_ctx* ctx, int kind, int d, const double* hyp,
 #define GPX_CALL(K_, DM_)                                                                                                    \
   hipLaunchKernelGGL((var_grad_newpt_radial_kernel<K_, DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X->p, n,    \
                      Z->p, (const double*)beta, np, j0, (double*)pO)
-#define GPX_CALL_SE(DM_) GPX_CALL(GPX_K_SE, DM_)
-#define GPX_CALL_M32(DM_) GPX_CALL(GPX_K_MATERN32, DM_)
-#define GPX_CALL_M52(DM_) GPX_CALL(GPX_K_MATERN52, DM_)
       GPX_RADIAL_DISPATCH(kind, d, GPX_CALL);
-#undef GPX_CALL_M52
-#undef GPX_CALL_M32
-#undef GPX_CALL_SE
 #undef GPX_CALL
     } else {
       GPX_TRY(solve_beta(ctx, kp, L, X, Z->p + j0 * d, mc, mcp, nullptr, (double*)pW, (double*)pWt, T, 0, &beta, nullptr, fitc,

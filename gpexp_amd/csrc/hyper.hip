@@ -9,7 +9,7 @@
 //                 numerator var(c|A) carried as an incremental Cholesky row (pivot + noise), denominator
 //                 var(c | S\c) = 1/[(K_SS + noise I)^-1]_cc - noise with S = all \ A, the inverse being
 //                 down-dated by a rank-one kernel whenever a point moves from S to A.
-#include "gpx_internal.h"
+#include "gpx_device.h"
 #include <math.h>
 #include <vector>
 
@@ -131,12 +131,7 @@ __global__ __launch_bounds__(256) void lmlgrad_final_kernel(const double* __rest
   const int q = blockIdx.x;
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < nblocks; b += 256) s += partial[b * nq + q];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+  block_sum_256(red, s);
   if (threadIdx.x == 0) out[q] = red[0];
 }
 
@@ -231,29 +226,6 @@ __global__ __launch_bounds__(256) void unit_rows_kernel(double* __restrict__ Z, 
 }
 
 // ---- MI greedy -------------------------------------------------------------------------------------------
-__device__ __forceinline__ double kpair_se_like(const KParams& kp, const double* __restrict__ a,
-                                                const double* __restrict__ b) {
-  if (kp.kind == GPX_K_MEHLER) {
-    double pa = 0.0, pb = 0.0, cr = 0.0;
-    for (int k = 0; k < kp.d; ++k) {
-      const double x = a[k], y = b[k];
-      pa = fma(kp.c1[k] * x, x, pa);
-      pb = fma(kp.c1[k] * y, y, pb);
-      cr = fma(kp.c2[k] * x, y, cr);
-    }
-    return kp.sig * exp(-(pa + pb - cr));
-  }
-  double acc = 0.0;
-  for (int k = 0; k < kp.d; ++k) {
-    const double e = (a[k] - b[k]) * kp.scale[k];  // difference first, as the reference (kernels.py:121-122)
-    acc = fma(e, e, acc);
-  }
-  if (kp.kind == GPX_K_SE) return kp.sig * exp(-0.5 * acc);
-  const double t = sqrt(acc);
-  if (kp.kind == GPX_K_MATERN32) return kp.sig * (1.0 + t) * exp(-t);
-  return kp.sig * (1.0 + t + acc * (1.0 / 3.0)) * exp(-t);
-}
-
 // conditioning on sel[cur] with noisy observations: pivot = d_s + noise
 __global__ __launch_bounds__(256) void mi_row_kernel(KParams kp, const double* __restrict__ Cp, int64_t M,
                                                      const int64_t* __restrict__ sel, int cur, double noise,
@@ -264,7 +236,7 @@ __global__ __launch_bounds__(256) void mi_row_kernel(KParams kp, const double* _
   const int64_t s = sel[cur];
   double dot = 0.0;
   for (int t = 0; t < cur; ++t) dot = fma(W[(int64_t)t * ldw + s], W[(int64_t)t * ldw + c], dot);
-  const double w = (kpair_se_like(kp, Cp + s * kp.d, Cp + c * kp.d) - dot) / sqrt(d_in[s] + noise);
+  const double w = (kpair(kp, Cp + s * kp.d, Cp + c * kp.d) - dot) / sqrt(d_in[s] + noise);
   W[(int64_t)cur * ldw + c] = w;
   d_out[c] = fma(-w, w, d_in[c]);
 }
@@ -314,14 +286,6 @@ __global__ __launch_bounds__(256) void mi_ratio_kernel(const double* __restrict_
   ratio[c] = alive[c] ? dnum[c] / (1.0 / P[c * ld + c] - noise) : -INFINITY;
 }
 
-struct VI {
-  double v;
-  int64_t i;
-};
-__device__ __forceinline__ VI vi_max(VI a, VI b) {
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
 // single-block first-max arg-max; also stores the winning value
 __global__ __launch_bounds__(1024) void argmax_block_kernel(const double* __restrict__ x, int64_t M,
                                                             int64_t* __restrict__ sel, int slot,
@@ -330,20 +294,10 @@ __global__ __launch_bounds__(1024) void argmax_block_kernel(const double* __rest
   __shared__ int64_t si[1024];
   VI best{-INFINITY, INT64_MAX};
   for (int64_t c = threadIdx.x; c < M; c += 1024) best = vi_max(best, VI{x[c], c});
-  sv[threadIdx.x] = best.v;
-  si[threadIdx.x] = best.i;
-  __syncthreads();
-  for (int h = 512; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      VI m = vi_max(VI{sv[threadIdx.x], si[threadIdx.x]}, VI{sv[threadIdx.x + h], si[threadIdx.x + h]});
-      sv[threadIdx.x] = m.v;
-      si[threadIdx.x] = m.i;
-    }
-    __syncthreads();
-  }
+  best = block_arg_reduce(best, sv, si, 1024, vi_max);
   if (threadIdx.x == 0) {
-    sel[slot] = si[0] == INT64_MAX ? 0 : si[0];
-    if (val) val[slot] = sv[0];
+    sel[slot] = best.i == INT64_MAX ? 0 : best.i;
+    if (val) val[slot] = best.v;
   }
 }
 
@@ -351,21 +305,6 @@ __global__ __launch_bounds__(256) void fill_int_kernel(int* __restrict__ a, int6
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) a[i] = v;
 }
-
-struct Scratch {
-  gpx_ctx* ctx;
-  std::vector<std::pair<void*, int64_t>> bufs;
-  explicit Scratch(gpx_ctx* c) : ctx(c) {}
-  int get(int64_t bytes, void** out) {
-    int r = gpx_dev_alloc(ctx, bytes, out);
-    if (r == 0) bufs.push_back({*out, bytes});
-    return r;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
-  }
-};
 
 }  // namespace
 

@@ -159,21 +159,6 @@ __global__ __launch_bounds__(256) void loo_ones_kernel(int64_t n, double* __rest
   if (i < n) v[i] = 1.0;
 }
 
-struct Scratch {
-  gpx_ctx* ctx;
-  std::vector<std::pair<void*, int64_t>> bufs;
-  explicit Scratch(gpx_ctx* c) : ctx(c) {}
-  int get(int64_t bytes, void** out) {
-    int r = gpx_dev_alloc(ctx, bytes, out);
-    if (r == 0) bufs.push_back({*out, bytes});
-    return r;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto& b : bufs) gpx_dev_release(ctx, b.first, b.second);
-  }
-};
-
 // a failed allocation keeps gpx_dev_alloc's own message ("hipMalloc(... bytes) failed: out of memory"), which the Python side
 // recognises; every other HIP failure is named here
 #define LOO_HIP(call)                                                                               \
@@ -335,7 +320,7 @@ int gpx_loo_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
           }
           if (!pW) { r = -2; break; }  // gpx_dev_alloc's message stands
         }
-        sc.bufs.push_back({pW, slab * np * 8});
+        sc.adopt(pW, slab * np * 8);
       } else if ((r = sc.get(slab * np * 8, &pW)) != 0) {
         break;
       }

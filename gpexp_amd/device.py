@@ -41,6 +41,12 @@ class Context:
         """Pooled blocks found overwritten outside their bounds (GPX_ALLOC_GUARD=1), -1 when the mode is off."""
         return int(self.lib.gpx_dbg_guard_violations(self.h))
 
+    def pool_stats(self):
+        """(bytes cached in the pool, bytes handed out and not returned), both in pool keys (gpx_dbg_pool_stats)."""
+        pooled, out = c_i64(), c_i64()
+        check(self.lib.gpx_dbg_pool_stats(self.h, C.byref(pooled), C.byref(out)))
+        return pooled.value, out.value
+
     def trim(self):
         check(self.lib.gpx_trim(self.h))
 

@@ -37,6 +37,10 @@ int gpx_dbg_spin(gpx_ctx* ctx, int ms);
  * block with NaNs when it is handed out (a read of memory nobody wrote then shows in the results).  Returns the number of
  * blocks found overwritten so far (each also reported on stderr), or -1 when the mode is off. */
 int64_t gpx_dbg_guard_violations(gpx_ctx* ctx);
+/* the pooled allocator's books, in pool keys (the rounded byte count a block is filed under): bytes cached in the pool, and
+ * bytes handed out and not returned.  A call that gives every block back under the size it took it with -- and frees what it
+ * returned -- leaves outstanding_bytes where it found it.  Either pointer may be NULL. */
+int gpx_dbg_pool_stats(gpx_ctx* ctx, int64_t* pooled_bytes, int64_t* outstanding_bytes);
 /* guard mode only: overruns a scratch block by 16 bytes on purpose; 1 if the check caught it, 0 if not, < 0 on error */
 int gpx_dbg_guard_selftest(gpx_ctx* ctx);
 /* host logic of gpx_comm_panel_bcast: the ncclSend / ncclRecv schedule of rank `me` in a W-rank communicator, rows of 6 int64
