@@ -174,110 +174,69 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
   double *pkd = nullptr, *pcost = nullptr, *pcoef = nullptr, *pgrad = nullptr, *ppc = nullptr, *pbc = nullptr;
   int64_t *ppi = nullptr, *pbi = nullptr;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  int r = 0;
-  do {
-    if ((r = sc.get(bytesB, &pB)) != 0) break;
-    if ((oop || grad) && (r = sc.get(bytesB, &pW)) != 0) break;
-    if (bytesT && (r = sc.get(bytesT, &pT)) != 0) break;
-    if ((r = sc.get(np * 8, &pal)) != 0) break;
-    if ((r = sc.get(bytes_out, &pmean)) != 0) break;
-    if ((r = sc.get(bytes_out, &pout)) != 0) break;
-    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
-    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
-    if ((r = sc.get(M * 8, &pcost)) != 0) break;
-    if ((r = sc.get(nparts * 8, &ppc)) != 0) break;
-    if ((r = sc.get(nparts * 8, &ppi)) != 0) break;
-    if ((r = sc.get(8, &pbc)) != 0) break;
-    if ((r = sc.get(8, &pbi)) != 0) break;
-    if (grad) {
-      if ((r = sc.get(2 * bytes_out, &pcoef)) != 0) break;
-      if ((r = sc.get(M * d * 8, &pgrad)) != 0) break;
-    }
-    if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      r = -2;
-      break;
-    }
-    for (int64_t j0 = 0; j0 < M && r == 0; j0 += mcmax) {
-      const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-      const int64_t mcp = gpx_round_up(mc, GPX_TILE);
-      double* B = pB;
-      const double* Zc = Z->p + j0 * d;
-      const int64_t ldb = gpx_skew_ld(mcp);
-      // posterior_impl's sequence, operation for operation: the values equal GP.evaluate's
-      if ((r = launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb)) != 0) break;
-      if ((r = launch_colreduce(ctx, B, ldb, n, mcp, pal, pmean, ppart)) != 0) break;
-      double* Wsol = B;
-      if (oop) {
-        if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, pW, ldb, mcp)) != 0) break;
-        Wsol = pW;
-      } else if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp)) != 0) {
-        break;
-      }
-      if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, pout, ppart)) != 0) break;
-      if ((r = launch_kdiag(ctx, kp, Zc, mc, pkd)) != 0) break;
-      {
-        ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 5.0 * (double)mc);
-        hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
-                           param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, pcost, pcoef, ppc, ppi);
-        if (hipGetLastError() != hipSuccess) {
-          r = -2;
-          break;
-        }
-      }
-      if (!grad) continue;
-      // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
-      double* Bt = Wsol == B ? pW : B;
-      if ((r = launch_transpose(ctx, Wsol, np, mcp, ldb, Bt, np)) != 0) break;
-      if (pT) r = chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, pT);
-      else r = chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np);
-      if (r != 0) break;
-      {
-        ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
-                     8.0 * ((double)n * (double)mc + (double)n * d));
-        r = launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, pal, pcoef, pgrad + j0 * d);
-      }
-    }
-    if (r != 0) break;
-    if (best || best_cost) {
-      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
-      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                         pbc, pbi);
-      if (hipGetLastError() != hipSuccess) {
-        r = -2;
-        break;
-      }
-      if ((best && hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-          (best_cost && hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
-        r = -2;
-        break;
-      }
-    }
-    if (cost_host && hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-      r = -2;
-      break;
-    }
-    if (grad_host && hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-      r = -2;
-      break;
-    }
-  } while (0);
-  if (r == -2) {
-    (void)hipStreamSynchronize(ctx->stream);   // the error text is that of the stream's work, as before
-    gpx_set_error("acq: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  GPX_TRY(sc.get(bytesB, &pB));
+  if (oop || grad) GPX_TRY(sc.get(bytesB, &pW));
+  if (bytesT) GPX_TRY(sc.get(bytesT, &pT));
+  GPX_TRY(sc.get(np * 8, &pal));
+  GPX_TRY(sc.get(bytes_out, &pmean));
+  GPX_TRY(sc.get(bytes_out, &pout));
+  GPX_TRY(sc.get(bytes_out, &pkd));
+  GPX_TRY(sc.get(bytes_part, &ppart));
+  GPX_TRY(sc.get(M * 8, &pcost));
+  GPX_TRY(sc.get(nparts * 8, &ppc));
+  GPX_TRY(sc.get(nparts * 8, &ppi));
+  GPX_TRY(sc.get(8, &pbc));
+  GPX_TRY(sc.get(8, &pbi));
+  if (grad) {
+    GPX_TRY(sc.get(2 * bytes_out, &pcoef));
+    GPX_TRY(sc.get(M * d * 8, &pgrad));
   }
-  return r;
+  GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
+    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+    const int64_t mcp = gpx_round_up(mc, GPX_TILE);
+    double* B = pB;
+    const double* Zc = Z->p + j0 * d;
+    const int64_t ldb = gpx_skew_ld(mcp);
+    // gpx_posterior's own per-chunk step: the values equal GP.evaluate's
+    GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Zc, mc, B, oop ? pW : nullptr, pal, pmean, nullptr, pout, pkd, ppart));
+    double* Wsol = oop ? pW : B;
+    {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 5.0 * (double)mc);
+      hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
+                         param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, pcost, pcoef, ppc, ppi);
+      GPX_HIP(hipGetLastError());
+    }
+    if (!grad) continue;
+    // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
+    double* Bt = Wsol == B ? pW : B;
+    GPX_TRY(launch_transpose(ctx, Wsol, np, mcp, ldb, Bt, np));
+    if (pT) GPX_TRY(chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, pT));
+    else GPX_TRY(chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np));
+    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
+                 8.0 * ((double)n * (double)mc + (double)n * d));
+    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, pal, pcoef, pgrad + j0 * d));
+  }
+  if (best || best_cost) {
+    ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
+    hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                       pbc, pbi);
+    GPX_HIP(hipGetLastError());
+    if (best) GPX_HIP(hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (grad_host) GPX_HIP(hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
+// the acquisition entries' own checks in front of the shared prologue
 int acq_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
              const gpx_mat* Z, int acq, KParams* kp) {
   GPX_ARG(ctx && L && X && Z && alpha, "NULL argument");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, kp));
-  GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
-  GPX_ARG(X->rows == L->rows, "X does not match the factor");
-  return gpx_kparams_sets(ctx, kp, X, Z);
+  return gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", kp);
 }
 
 // ---- q-point batch selection with resident state (gpx_acq_batch) ------------------------------------------------------------
@@ -386,99 +345,79 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
   Scratch sc(ctx);
   const dim3 gEpi((unsigned)nparts), gM((unsigned)((M + 255) / 256));
   const dim3 gPick((unsigned)(((np > q ? np : q) + 255) / 256));
-  int r = 0;
-  do {
-    if ((r = sc.get(bytesW, &pW)) != 0) break;
-    if (oop && (r = sc.get(bytesB, &pB)) != 0) break;
-    if ((r = sc.get(bytesU, &pU)) != 0) break;
-    if ((r = sc.get(np * 8, &pal)) != 0) break;
-    if ((r = sc.get(bytesM, &pmu)) != 0) break;
-    if ((r = sc.get(bytesM, &pv)) != 0) break;
-    if ((r = sc.get(bytesM, &pkd)) != 0) break;
-    if ((r = sc.get(bytesM, &pss)) != 0) break;    // |W_C[:, j]|^2 at the set-up, then h of every pick
-    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
-    if ((r = sc.get(M * 8, &pcost)) != 0) break;
-    if ((r = sc.get(nparts * 8, &ppc)) != 0) break;
-    if ((r = sc.get(nparts * 8, &ppi)) != 0) break;
-    if ((r = sc.get(8, &pbc)) != 0) break;
-    if ((r = sc.get(8, &pbi)) != 0) break;
-    if ((r = sc.get(SC_N * 8, &psc)) != 0) break;
-    if ((r = sc.get(q * 8, &puc)) != 0) break;
-    if ((r = sc.get(bytes_w, &pw)) != 0) break;
-    if ((r = sc.get(Mp * 4, &pmask)) != 0) break;
-    double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
-    if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      r = -2;
-      break;
-    }
-    double *Wc = pW, *U = pU, *mu = pmu, *v = pv, *hd = pss;
-    // ---- set-up: gpx_acq's posterior pass, operation for operation, with W kept ----
-    for (int64_t j0 = 0; j0 < Mp && r == 0; j0 += mcw) {
-      const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
-      const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
-      double* B = oop ? pB : Wc + j0;
-      const int64_t ldc = oop ? gpx_skew_ld(mcp) : ld;
-      if ((r = launch_kfill(ctx, kp, X->p, n, Cm->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldc)) != 0) break;
-      if ((r = launch_colreduce(ctx, B, ldc, n, mcp, pal, mu + j0, ppart)) != 0) break;
-      if (oop) r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldc, Wc + j0, ld, mcp);
-      else r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldc, np, mcp);
-    }
-    if (r != 0) break;
-    if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, ppart)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Cm->p, M, pkd)) != 0) break;
-    hipLaunchKernelGGL(acq_batch_v_kernel, gM, dim3(256), 0, ctx->stream, (const double*)pkd, (const double*)hd, M, v);
-    if (hipGetLastError() != hipSuccess) {
-      r = -2;
-      break;
-    }
-    // ---- the picks ----
-    int64_t s = -1;
-    for (int64_t t = 0; t < q; ++t) {
-      {
-        ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
-        hipLaunchKernelGGL(acq_batch_kernel, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M, t > 0 ? 1 : 0,
-                           s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
-                           (const int*)pmask, pcost, ppc, ppi);
-        hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                           pbc, pbi);
-      }
-      double c = 0.0;
-      if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          (all_costs &&
-           hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        r = -2;
-        break;
-      }
-      if (s < 0 || s >= M) {
-        gpx_set_error("acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
-        r = -1;
-        break;
-      }
-      out_idx[t] = s;
-      if (out_cost) out_cost[t] = c;
-      if (t + 1 == q && !out_lie) break;
-      hipLaunchKernelGGL(acq_pick_kernel, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
-                         (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
-                         psc, puc, pw, pmask);
-      if (hipGetLastError() != hipSuccess ||
-          (out_lie && hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) {
-        r = -2;
-        break;
-      }
-      if (t + 1 == q) break;
-      if ((r = launch_colreduce(ctx, Wc, ld, n, Mp, pw, hd, ppart)) != 0) break;
-    }
-  } while (0);
-  if (r == -2) {
-    (void)hipStreamSynchronize(ctx->stream);
-    gpx_set_error("acq batch: HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  GPX_TRY(sc.get(bytesW, &pW));
+  if (oop) GPX_TRY(sc.get(bytesB, &pB));
+  GPX_TRY(sc.get(bytesU, &pU));
+  GPX_TRY(sc.get(np * 8, &pal));
+  GPX_TRY(sc.get(bytesM, &pmu));
+  GPX_TRY(sc.get(bytesM, &pv));
+  GPX_TRY(sc.get(bytesM, &pkd));
+  GPX_TRY(sc.get(bytesM, &pss));    // |W_C[:, j]|^2 at the set-up, then h of every pick
+  GPX_TRY(sc.get(bytes_part, &ppart));
+  GPX_TRY(sc.get(M * 8, &pcost));
+  GPX_TRY(sc.get(nparts * 8, &ppc));
+  GPX_TRY(sc.get(nparts * 8, &ppi));
+  GPX_TRY(sc.get(8, &pbc));
+  GPX_TRY(sc.get(8, &pbi));
+  GPX_TRY(sc.get(SC_N * 8, &psc));
+  GPX_TRY(sc.get(q * 8, &puc));
+  GPX_TRY(sc.get(bytes_w, &pw));
+  GPX_TRY(sc.get(Mp * 4, &pmask));
+  double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
+  GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream));
+  double *Wc = pW, *U = pU, *mu = pmu, *v = pv, *hd = pss;
+  // ---- set-up: the posterior pass with W kept.  Not gpx_posterior_chunk: the solve lands in the resident W_C with ITS row
+  // stride, and the squares are reduced once over all of W_C ----
+  for (int64_t j0 = 0; j0 < Mp; j0 += mcw) {
+    const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
+    const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
+    double* B = oop ? pB : Wc + j0;
+    const int64_t ldc = oop ? gpx_skew_ld(mcp) : ld;
+    GPX_TRY(launch_kfill(ctx, kp, X->p, n, Cm->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldc));
+    GPX_TRY(launch_colreduce(ctx, B, ldc, n, mcp, pal, mu + j0, ppart));
+    if (oop) GPX_TRY(chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldc, Wc + j0, ld, mcp));
+    else GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldc, np, mcp));
   }
-  return r;
+  GPX_TRY(launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, ppart));
+  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, pkd));
+  hipLaunchKernelGGL(acq_batch_v_kernel, gM, dim3(256), 0, ctx->stream, (const double*)pkd, (const double*)hd, M, v);
+  GPX_HIP(hipGetLastError());
+  // ---- the picks ----
+  int64_t s = -1;
+  for (int64_t t = 0; t < q; ++t) {
+    {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
+      hipLaunchKernelGGL(acq_batch_kernel, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M, t > 0 ? 1 : 0,
+                         s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
+                         (const int*)pmask, pcost, ppc, ppi);
+      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                         pbc, pbi);
+    }
+    double c = 0.0;
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (all_costs) GPX_HIP(hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipStreamSynchronize(ctx->stream));
+    if (s < 0 || s >= M) {
+      gpx_set_error("acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
+      return -1;
+    }
+    out_idx[t] = s;
+    if (out_cost) out_cost[t] = c;
+    if (t + 1 == q && !out_lie) break;
+    hipLaunchKernelGGL(acq_pick_kernel, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
+                       (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
+                       psc, puc, pw, pmask);
+    GPX_HIP(hipGetLastError());
+    if (out_lie) GPX_HIP(hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (t + 1 == q) break;
+    GPX_TRY(launch_colreduce(ctx, Wc, ld, n, Mp, pw, hd, ppart));
+  }
+  return 0;
 }
 
 }  // namespace

@@ -861,14 +861,10 @@ int gpx_kfill_into(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
 int gpx_kfill(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* Z,
               const double* nugget, int64_t nugget_len, gpx_mat** outK) {
   GPX_ARG(ctx && X && outK, "NULL argument");
-  gpx_mat* K = nullptr;
-  GPX_TRY(gpx_mat_new(ctx, X->rows, Z ? Z->rows : X->rows, 1, &K));
-  int r = gpx_kfill_into(ctx, kind, d, hyp, nhyp, X, Z, nugget, nugget_len, K);
-  if (r != 0) {
-    gpx_mat_free(ctx, K);
-    return r;
-  }
-  *outK = K;
+  MatHold K(ctx);
+  GPX_TRY(gpx_mat_new(ctx, X->rows, Z ? Z->rows : X->rows, 1, K.put()));
+  GPX_TRY(gpx_kfill_into(ctx, kind, d, hyp, nhyp, X, Z, nugget, nugget_len, K.get()));
+  *outK = K.release();
   return 0;
 }
 
@@ -881,12 +877,9 @@ int gpx_kdiag(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const 
   Scratch sc(ctx);   // (its scope exit completes the copy)
   double* p;
   GPX_TRY(sc.get(Z->rows * 8, &p));
-  int r = launch_kdiag(ctx, kp, Z->p, Z->rows, p);
-  if (r == 0) {
-    hipError_t e = hipMemcpyAsync(out, p, (size_t)Z->rows * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) r = -2;
-  }
-  return r;
+  GPX_TRY(launch_kdiag(ctx, kp, Z->p, Z->rows, p));
+  GPX_HIP(hipMemcpyAsync(out, p, (size_t)Z->rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 // ---- factorisation and solves ----------------------------------------------------------------------
@@ -983,7 +976,41 @@ int gpx_potrf(gpx_ctx* ctx, gpx_mat* K) {
   return potrf_end(ctx, K, &J);
 }
 
-static int need_factor(const gpx_mat* L);
+static int need_factor(const gpx_mat* L) {
+  GPX_ARG(L != nullptr, "factor is NULL");
+  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
+  return 0;
+}
+
+}  // extern "C"
+
+int gpx_entry_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                   const gpx_mat* Z, const gpx_mat* C, const char* points_msg, KParams* kp) {
+  GPX_TRY(need_factor(L));
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, kp));
+  for (const gpx_mat* P : {X, Z, C})
+    if (P) GPX_ARG(P->cols == d && P->pcols == d, points_msg);
+  GPX_ARG(X->rows == L->rows, "X does not match the factor");
+  return Z ? gpx_kparams_sets(ctx, kp, X, Z, C) : 0;
+}
+
+int gpx_posterior_chunk(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,
+                        double* B, double* Wout, const double* alpha_dev, double* mean_dev, double* mean_host, double* ssq,
+                        double* kd, double* part) {
+  const int64_t n = L->rows, np = L->prows, mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
+  GPX_TRY(launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb));
+  if (alpha_dev) {
+    GPX_TRY(launch_colreduce(ctx, B, ldb, n, mcp, alpha_dev, mean_dev, part));
+    if (mean_host) GPX_HIP(hipMemcpyAsync(mean_host, mean_dev, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (!ssq) return 0;
+  if (Wout) GPX_TRY(chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, Wout, ldb, mcp));
+  else GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp));
+  GPX_TRY(launch_colreduce(ctx, Wout ? Wout : B, ldb, n, mcp, nullptr, ssq, part));
+  return launch_kdiag(ctx, kp, Zc, mc, kd);
+}
+
+extern "C" {
 
 int gpx_potrf_policy(gpx_ctx* ctx, double piv_min, int skip) {
   GPX_ARG(ctx != nullptr && piv_min >= 0.0, "bad pivot policy");
@@ -997,6 +1024,89 @@ int gpx_potrf_dropped(gpx_ctx* ctx, int* count) {
   GPX_HIP(hipMemcpyAsync(count, ctx->d_info + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   GPX_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+// the assembly and factorisation behind gpx_refit_rows, into the fresh matrix K; every stream it used is drained by the caller
+static int refit_rows_into(gpx_ctx* ctx, const KParams& kp, const gpx_mat* X, const double* nugget, int64_t nugget_len,
+                           const gpx_mat* Lold, int64_t keep, gpx_mat* K) {
+  const int64_t n = X->rows, np = K->prows;
+  Scratch sc(ctx);
+  double* d_nug = nullptr;
+  K->aux_bytes = np * GPX_TILE * 8;
+  void* pa;
+  GPX_TRY(gpx_dev_alloc(ctx, K->aux_bytes, &pa));
+  K->aux = (double*)pa;
+  // the kept rows are COPIED (device state is immutable once built: shallow copies of a GP share handles), but nothing below
+  // reads the copy -- the strip solve works against the old factor, the new rows are factored on their own -- so it runs on the
+  // low-priority side stream underneath (HBM-bound beside MFMA-bound work: 0.59 ms off the 4.7 at N = 16384) and is joined
+  // before the result is handed out
+  hipStream_t Mst = ctx->stream, Cst = ctx->streams[4];
+  bool side = keep > 0 && Mst == ctx->streams[0] && Cst != Mst;
+  if (side && !ctx->ev_side && hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming) != hipSuccess) side = false;
+  if (keep > 0) {
+    // (the lower triangle only, to the 512-column boundary above the diagonal -- every diagonal tile whole: nothing reads a
+    // factor's blocks above those; a full factorisation leaves the assembled K there, this one whatever the pool handed out)
+    if (side) {
+      GPX_HIP(hipEventRecord(ctx->ev_side, Mst));
+      GPX_HIP(hipStreamWaitEvent(Cst, ctx->ev_side, 0));
+    }
+    StreamScope copy_stream(ctx, side ? Cst : Mst);
+    GPX_TRY(gpx_copy2d_lower(ctx, Lold->p, Lold->ld, K->p, K->ld, keep));
+    if (hipMemcpyAsync(K->aux, Lold->aux, (size_t)keep * GPX_TILE * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+      gpx_set_error("refit_rows: copy of the leaf inverses failed");
+      return -2;
+    }
+    if (side) GPX_HIP(hipEventRecord(ctx->ev_side, Cst));
+  }
+  double nscal = 0.0;
+  if (nugget_len == 1) nscal = nugget[0];
+  if (nugget_len > 1) {
+    GPX_TRY(sc.get(nugget_len * 8, &d_nug));
+    if (hipMemcpyAsync(d_nug, nugget, (size_t)nugget_len * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      gpx_set_error("refit_rows: nugget upload failed");
+      return -2;
+    }
+  }
+  GPX_HIP(hipMemsetAsync(ctx->d_info, 0, 2 * sizeof(int), ctx->stream));
+  const int64_t n2 = np - keep;
+  if (n2 > 0) {
+    double* A21 = K->p + keep * K->ld;
+    GPX_TRY(launch_kfill_rows(ctx, kp, X->p, n, keep, d_nug, nugget_len, nscal, A21, n2, np, K->ld));
+    if (keep > 0) {
+      // The strip solve A21 <- A21 L11^-T has few rows (one batch of design points): through the leaf recursion its products
+      // have K = 128..512 on a handful of tiles (20 TF/s at N = 16384, 512 changed rows).  Large factors: through the old
+      // factor's explicit 1024-order block inverses (every product K >= 1024, 64-tiles), and the small trailing SYRK -- K = keep
+      // on n2^2 / 64^2 tiles, a serial k loop in a few dozen workgroups -- split over K into 1024-wide batches whose partial
+      // products are then subtracted in a fixed order.
+      const int64_t kc = 1024;
+      const bool wide = keep >= 4096 && n2 <= 2048 && Lold->prows >= 2048;
+      if (wide) {
+        const int64_t ib = chol_binv_order(Lold->prows), nbat = keep / kc, rem = keep - nbat * kc;
+        double *pT = nullptr, *pP = nullptr;
+        const int64_t tcap = std::max<int64_t>(4 * n2 * ib, 2 * n2 * keep);   // (the solve runs its few-row products as slices)
+        Scratch wide_sc(ctx);   // back to the pool before the factorisation of the new rows asks it for its own scratch
+        GPX_TRY(wide_sc.get(tcap * 8, &pT));
+        GPX_TRY(wide_sc.get(nbat * n2 * n2 * 8, &pP));
+        GPX_TRY(chol_trsm_right_leading(ctx, const_cast<gpx_mat*>(Lold), keep, A21, K->ld, n2, pT, tcap));
+        GPX_TRY(launch_gemm_batched(ctx, A21, K->ld, kc, A21, K->ld, kc, pP, n2, n2 * n2, n2, n2, kc, true, false, nbat));
+        GPX_TRY(launch_sub_partials(ctx, (const double*)pP, nbat, n2, A21 + keep, K->ld));
+        if (rem > 0)
+          GPX_TRY(launch_gemm(ctx, A21 + nbat * kc, K->ld, A21 + nbat * kc, K->ld, A21 + keep, K->ld, n2, n2, rem, true, true, true));
+      } else {
+        // (against the OLD factor: the copy may still be in flight)
+        GPX_TRY(chol_trsm_right(ctx, Lold->p, Lold->ld, Lold->aux, A21, K->ld, n2, keep));
+        GPX_TRY(launch_gemm(ctx, A21, K->ld, A21, K->ld, A21 + keep, K->ld, n2, n2, keep, true, true, true));
+      }
+    }
+    GPX_TRY(chol_potrf_nozero(ctx, A21 + keep, K->ld, n2, K->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, keep, n));
+  }
+  int info = 0;
+  if (side) GPX_HIP(hipStreamWaitEvent(Mst, ctx->ev_side, 0));
+  GPX_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  K->factored = (info == 0);
+  if (info != 0) gpx_set_error("refit_rows: matrix is not positive definite (pivot %d <= 0)", info);
+  return info;
 }
 
 // f2: refit when only the trailing points of the design changed.  The leading `keep` rows/columns of
@@ -1018,111 +1128,16 @@ int gpx_refit_rows(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
     GPX_ARG(keep <= Lold->rows && keep <= n, "keep exceeds the old factor or the new point set");
   }
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X));
-  gpx_mat* K = nullptr;
-  GPX_TRY(gpx_mat_new(ctx, n, n, 1, &K));
-  const int64_t np = K->prows;
-  int r = 0;
-  Scratch sc(ctx);
-  double* d_nug = nullptr;
-  do {
-    K->aux_bytes = np * GPX_TILE * 8;
-    void* pa;
-    if ((r = gpx_dev_alloc(ctx, K->aux_bytes, &pa)) != 0) break;
-    K->aux = (double*)pa;
-    // the kept rows are COPIED (device state is immutable once built: shallow copies of a GP share handles), but nothing below
-    // reads the copy -- the strip solve works against the old factor, the new rows are factored on their own -- so it runs on the
-    // low-priority side stream underneath (HBM-bound beside MFMA-bound work: 0.59 ms off the 4.7 at N = 16384) and is joined
-    // before the result is handed out
-    hipStream_t Mst = ctx->stream, Cst = ctx->streams[4];
-    bool side = keep > 0 && Mst == ctx->streams[0] && Cst != Mst;
-    if (side && !ctx->ev_side && hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming) != hipSuccess) side = false;
-    if (keep > 0) {
-      // (the lower triangle only, to the 512-column boundary above the diagonal -- every diagonal tile whole: nothing reads a
-      // factor's blocks above those; a full factorisation leaves the assembled K there, this one whatever the pool handed out)
-      if (side) {
-        if (hipEventRecord(ctx->ev_side, Mst) != hipSuccess || hipStreamWaitEvent(Cst, ctx->ev_side, 0) != hipSuccess) { r = -2; break; }
-        ctx->stream = Cst;
-      }
-      r = gpx_copy2d_lower(ctx, Lold->p, Lold->ld, K->p, K->ld, keep);
-      if (r == 0 && hipMemcpyAsync(K->aux, Lold->aux, (size_t)keep * GPX_TILE * 8, hipMemcpyDeviceToDevice, ctx->stream) !=
-          hipSuccess) { r = -2; gpx_set_error("refit_rows: copy of the leaf inverses failed"); }
-      if (side) {
-        if (r == 0 && hipEventRecord(ctx->ev_side, Cst) != hipSuccess) r = -2;
-        ctx->stream = Mst;
-      }
-      if (r != 0) break;
-    }
-    double nscal = 0.0;
-    if (nugget_len == 1) nscal = nugget[0];
-    if (nugget_len > 1) {
-      if ((r = sc.get(nugget_len * 8, &d_nug)) != 0) break;
-      if (hipMemcpyAsync(d_nug, nugget, (size_t)nugget_len * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        r = -2; gpx_set_error("refit_rows: nugget upload failed"); break;
-      }
-    }
-    if (hipMemsetAsync(ctx->d_info, 0, 2 * sizeof(int), ctx->stream) != hipSuccess) { r = -2; break; }
-    const int64_t n2 = np - keep;
-    if (n2 > 0) {
-      double* A21 = K->p + keep * K->ld;
-      if ((r = launch_kfill_rows(ctx, kp, X->p, n, keep, d_nug, nugget_len, nscal, A21, n2, np, K->ld)) != 0) break;
-      if (keep > 0) {
-        // The strip solve A21 <- A21 L11^-T has few rows (one batch of design points): through the leaf recursion its products
-        // have K = 128..512 on a handful of tiles (20 TF/s at N = 16384, 512 changed rows).  Large factors: through the old
-        // factor's explicit 1024-order block inverses (every product K >= 1024, 64-tiles), and the small trailing SYRK -- K = keep
-        // on n2^2 / 64^2 tiles, a serial k loop in a few dozen workgroups -- split over K into 1024-wide batches whose partial
-        // products are then subtracted in a fixed order.
-        const int64_t kc = 1024;
-        const bool wide = keep >= 4096 && n2 <= 2048 && Lold->prows >= 2048;
-        if (wide) {
-          const int64_t ib = chol_binv_order(Lold->prows), nbat = keep / kc, rem = keep - nbat * kc;
-          double *pT = nullptr, *pP = nullptr;
-          const int64_t tcap = std::max<int64_t>(4 * n2 * ib, 2 * n2 * keep);   // (the solve runs its few-row products as slices)
-          {
-            Scratch wide_sc(ctx);   // back to the pool before the factorisation of the new rows asks it for its own scratch
-            if ((r = wide_sc.get(tcap * 8, &pT)) != 0) break;
-            if ((r = wide_sc.get(nbat * n2 * n2 * 8, &pP)) != 0) break;
-            r = chol_trsm_right_leading(ctx, const_cast<gpx_mat*>(Lold), keep, A21, K->ld, n2, pT, tcap);
-            if (r == 0)
-              r = launch_gemm_batched(ctx, A21, K->ld, kc, A21, K->ld, kc, pP, n2, n2 * n2, n2, n2, kc, true, false, nbat);
-            if (r == 0) r = launch_sub_partials(ctx, (const double*)pP, nbat, n2, A21 + keep, K->ld);
-            if (r == 0 && rem > 0)
-              r = launch_gemm(ctx, A21 + nbat * kc, K->ld, A21 + nbat * kc, K->ld, A21 + keep, K->ld, n2, n2, rem, true, true, true);
-          }
-          if (r != 0) break;
-        } else {
-          // (against the OLD factor: the copy may still be in flight)
-          if ((r = chol_trsm_right(ctx, Lold->p, Lold->ld, Lold->aux, A21, K->ld, n2, keep)) != 0) break;
-          if ((r = launch_gemm(ctx, A21, K->ld, A21, K->ld, A21 + keep, K->ld, n2, n2, keep, true, true, true)) != 0) break;
-        }
-      }
-      if ((r = chol_potrf_nozero(ctx, A21 + keep, K->ld, n2, K->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, keep, n)) != 0)
-        break;
-    }
-    int info = 0;
-    if (side && hipStreamWaitEvent(Mst, ctx->ev_side, 0) != hipSuccess) { r = -2; break; }
-    if (hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { r = -2; break; }
-    K->factored = (info == 0);
-    if (info != 0) {
-      gpx_set_error("refit_rows: matrix is not positive definite (pivot %d <= 0)", info);
-      r = info;
-    }
-  } while (0);
+  MatHold K(ctx);
+  GPX_TRY(gpx_mat_new(ctx, n, n, 1, K.put()));
+  // a status, not an early return: both streams are drained on EVERY exit before K is freed or handed out
+  const int r = refit_rows_into(ctx, kp, X, nugget, nugget_len, Lold, keep, K.get());
   (void)hipStreamSynchronize(ctx->stream);
   //  an error between the fork and the join leaves the copy of the kept rows in flight on the side stream: it writes K
   // and reads Lold -- both may be freed right after this returns
   if (ctx->ev_side && ctx->streams[4] != ctx->stream) (void)hipStreamSynchronize(ctx->streams[4]);
-  if (r != 0) {
-    gpx_mat_free(ctx, K);
-    return r;
-  }
-  *outL = K;
-  return 0;
-}
-
-static int need_factor(const gpx_mat* L) {
-  GPX_ARG(L != nullptr, "factor is NULL");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
+  if (r != 0) return r;
+  *outL = K.release();
   return 0;
 }
 
@@ -1135,15 +1150,11 @@ int gpx_potrs(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* alpha) {
   double *dv, *ps;
   GPX_TRY(sc.get(np * 8, &dv));
   GPX_TRY(sc.get(sb, &ps));
-  int r = 0;
-  do {
-    if (hipMemsetAsync(dv, 0, (size_t)np * 8, ctx->stream) != hipSuccess) { r = -2; break; }
-    if (hipMemcpyAsync(dv, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
-    if ((r = chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, ps)) != 0) break;  // caches the block inverses in L
-    if (hipMemcpyAsync(alpha, dv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-  } while (0);
-  if (r == -2) gpx_set_error("potrs: HIP copy failed");
-  return r;
+  GPX_HIP(hipMemsetAsync(dv, 0, (size_t)np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(dv, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, ps));  // caches the block inverses in L
+  GPX_HIP(hipMemcpyAsync(alpha, dv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 // device-vector form, asynchronous on the selected stream: alpha (>= padded N doubles) <- K^-1 y
@@ -1222,7 +1233,6 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
   const int64_t n = L->rows, np = L->prows, M = Z->rows, d = kp.d;
   const bool var = var_host != nullptr || var_dev != nullptr;
   if (keepW) *keepW = nullptr;
-  GPX_ARG(X->rows == n, "X does not match the factor");
   if (M == 0) return 0;
   const int64_t mcmax = eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
@@ -1232,90 +1242,49 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
   const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
   const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
   const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
-  int r = 0;
+  // keepW: the solved W = L^-1 K(X, Z) stays, as a matrix of its own, for the cost's gradient at the same design
+  // (gpx_ivar_grad_w) -- when all of Z is one chunk; it then IS the buffer the solution lands in.  The caller's on success only.
+  MatHold Wm(ctx);
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  do {
-    // all M variances, device (when the caller did not bring its own)
-    if (var && !var_dev && (r = sc.get(M * 8, &var_dev)) != 0) break;
-    // keepW: the solved W = L^-1 K(X, Z) stays, as a matrix of its own, for the cost's gradient at the same design
-    // (gpx_ivar_grad_w) -- when all of Z is one chunk; it then IS the buffer the solution lands in
-    gpx_mat* Wm = nullptr;
-    if (keepW && var && M <= mcmax && gpx_mat_new(ctx, n, M, 1, &Wm) == 0 &&
-        (Wm->prows != np || Wm->ld != ldb_alloc || Wm->bytes < bytesB)) {
-      gpx_mat_free(ctx, Wm);
-      Wm = nullptr;
-    }
-    if (Wm) *keepW = Wm;
-    // (the kept matrix's buffer serves as pB or pW; it belongs to the gpx_mat and never goes through the scratch owner)
-    if (Wm && !oop) pB = Wm->p;
-    else if ((r = sc.get(bytesB, &pB)) != 0) break;
-    if (oop) {
-      if (Wm) pW = Wm->p;
-      else if ((r = sc.get(bytesB, &pW)) != 0) break;
-    }
-    if ((r = sc.get(bytes_out, &pout)) != 0) break;
-    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
-    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
-    if (mean) {
-      if ((r = sc.get(np * 8, &pal)) != 0) break;
-      if (hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        r = -2;
-        break;
-      }
-    }
-    for (int64_t j0 = 0; j0 < M && r == 0; j0 += mcmax) {
-      const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-      const int64_t mcp = gpx_round_up(mc, GPX_TILE);
-      double* B = pB;
-      const double* Zc = Z->p + j0 * d;
-      const int64_t ldb = gpx_skew_ld(mcp);
-      if ((r = launch_kfill(ctx, kp, X->p, n, Zc, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldb)) != 0) break;
-      if (mean) {
-        if ((r = launch_colreduce(ctx, B, ldb, n, mcp, pal, pout, ppart)) != 0) break;
-        if (hipMemcpyAsync(mean + j0, pout, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-          r = -2;
-          break;
-        }
-      }
-      if (var) {
-        const double* Wsol = B;
-        if (oop) {
-          if ((r = chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, pW, ldb, mcp)) != 0) break;
-          Wsol = pW;
-        } else if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp)) != 0) {
-          break;
-        }
-        if ((r = launch_colreduce(ctx, Wsol, ldb, n, mcp, nullptr, pout, ppart)) != 0) break;
-        if ((r = launch_kdiag(ctx, kp, Zc, mc, pkd)) != 0) break;
-        hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                           (const double*)pout, mc, var_dev + j0);
-      }
-    }
-    if (r == 0 && var_host &&
-        hipMemcpyAsync(var_host, var_dev, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      r = -2;
-  } while (0);
-  if (r != 0) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (keepW && *keepW) {
-      gpx_mat_free(ctx, *keepW);
-      *keepW = nullptr;
-    }
+  // all M variances, device (when the caller did not bring its own)
+  if (var && !var_dev) GPX_TRY(sc.get(M * 8, &var_dev));
+  if (keepW && var && M <= mcmax && gpx_mat_new(ctx, n, M, 1, Wm.put()) == 0 &&
+      (Wm->prows != np || Wm->ld != ldb_alloc || Wm->bytes < bytesB))
+    Wm.reset();
+  // (the kept matrix's buffer serves as pB or pW; it belongs to the gpx_mat and never goes through the scratch owner)
+  if (Wm.get() && !oop) pB = Wm->p;
+  else GPX_TRY(sc.get(bytesB, &pB));
+  if (oop) {
+    if (Wm.get()) pW = Wm->p;
+    else GPX_TRY(sc.get(bytesB, &pW));
   }
-  if (r == -2) gpx_set_error("posterior: HIP copy failed: %s", hipGetErrorString(hipGetLastError()));
-  return r;
+  GPX_TRY(sc.get(bytes_out, &pout));
+  GPX_TRY(sc.get(bytes_out, &pkd));
+  GPX_TRY(sc.get(bytes_part, &ppart));
+  if (mean) {
+    GPX_TRY(sc.get(np * 8, &pal));
+    GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
+    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+    GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Z->p + j0 * d, mc, pB, pW, pal, pout, mean ? mean + j0 : nullptr,
+                                var ? pout : nullptr, pkd, ppart));
+    if (var)
+      hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
+                         (const double*)pout, mc, var_dev + j0);
+  }
+  if (var_host) GPX_HIP(hipMemcpyAsync(var_host, var_dev, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (keepW) *keepW = Wm.release();
+  return 0;
 }
 
 int gpx_posterior(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                   const double* alpha, const gpx_mat* Z, double* mean, double* var) {
   GPX_ARG(ctx && X && Z, "NULL argument");
-  GPX_TRY(need_factor(L));
   GPX_ARG(mean == nullptr || alpha != nullptr, "alpha is required for the mean");
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", &kp));
   return posterior_impl(ctx, kp, L, X, alpha, Z, mean, var);
 }
 
@@ -1348,26 +1317,18 @@ static int ivar_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp,
                      const gpx_mat* Z, double* out, gpx_mat** W) {
   GPX_ARG(ctx && X && Z && out, "NULL argument");
   if (W) *W = nullptr;
-  GPX_TRY(need_factor(L));
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", &kp));
   GPX_ARG(Z->rows > 0, "IVAR needs at least one integration point");
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
+  MatHold Wm(ctx);   // the kept solve: the caller's only when the cost is on its way
   Scratch sc(ctx);   // (its scope exit completes the copy of the cost)
   double* pv;
   GPX_TRY(sc.get(Z->rows * 8, &pv));
-  int r = posterior_impl(ctx, kp, L, X, nullptr, Z, nullptr, nullptr, pv, W);
-  if (r == 0) {
-    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, Z->rows, ctx->d_scal);
-    if (hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
-  }
-  if (r == -2) gpx_set_error("ivar: HIP copy failed");
-  if (r != 0 && W && *W) {
-    gpx_mat_free(ctx, *W);
-    *W = nullptr;
-  }
-  return r;
+  GPX_TRY(posterior_impl(ctx, kp, L, X, nullptr, Z, nullptr, nullptr, pv, W ? Wm.put() : nullptr));
+  hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, Z->rows, ctx->d_scal);
+  GPX_HIP(hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (W) *W = Wm.release();
+  return 0;
 }
 
 // The cost again after a refit that KEPT the leading `keep` rows of the factor (gpx_refit_rows): W = L^-1 K(X, Z) of the previous
@@ -1380,38 +1341,31 @@ int gpx_ivar_update(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   GPX_ARG(ctx && X && Z && W && out, "NULL argument");
   GPX_TRY(need_factor(L));
   GPX_ARG(ctx->live_mats.count(W), "ivar_update: W is not a live matrix of this context");
-  KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_ARG(X->cols == d && X->pcols == d && Z->cols == d && Z->pcols == d, "point sets must be unpadded (n x d)");
   const int64_t n = L->rows, np = L->prows, M = Z->rows, mcp = gpx_round_up(M, GPX_TILE);
-  GPX_ARG(X->rows == n && M > 0, "X does not match the factor / no integration points");
+  GPX_ARG(X->rows == n && M > 0, "X does not match the factor / no integration points");   // (this entry's own wording)
+  KParams kp;
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", &kp));
   GPX_ARG(W->rows == n && W->cols == M && W->prows == np && W->pcols == mcp, "ivar_update: W has another shape");
   GPX_ARG(keep > 0 && keep < np && keep % GPX_TILE == 0, "ivar_update: keep must be a positive multiple of 128 below the padded order");
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   const int64_t n2 = n - keep, n2p = np - keep, ldw = W->ld;
   const int64_t bytes_out = mcp * 8, bytes_part = colreduce_partial_elems(np, mcp) * 8 + 8;
   Scratch sc(ctx);   // (its scope exit completes the copy of the cost)
   double *pout = nullptr, *pkd = nullptr, *ppart = nullptr, *pv = nullptr;
-  int r = 0;
-  do {
-    if ((r = sc.get(bytes_out, &pout)) != 0) break;
-    if ((r = sc.get(bytes_out, &pkd)) != 0) break;
-    if ((r = sc.get(bytes_part, &ppart)) != 0) break;
-    if ((r = sc.get(M * 8, &pv)) != 0) break;
-    double* W2 = W->p + keep * ldw;
-    if ((r = launch_kfill(ctx, kp, X->p + keep * d, n2, Z->p, M, 0, nullptr, 0, 0.0, W2, n2p, mcp, ldw)) != 0) break;
-    if ((r = launch_gemm(ctx, L->p + keep * L->ld, L->ld, W->p, ldw, W2, ldw, n2p, mcp, keep, false, true, false)) != 0) break;
-    if ((r = chol_trsm_left(ctx, L->p + keep * (L->ld + 1), L->ld, L->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, W2, ldw, n2p,
-                            mcp)) != 0) break;
-    if ((r = launch_colreduce(ctx, W->p, ldw, n, mcp, nullptr, pout, ppart)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Z->p, M, pkd)) != 0) break;
-    hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                       (const double*)pout, M, pv);
-    hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, M, ctx->d_scal);
-    if (hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
-  } while (0);
-  if (r == -2) gpx_set_error("ivar_update: HIP copy failed");
-  return r;
+  GPX_TRY(sc.get(bytes_out, &pout));
+  GPX_TRY(sc.get(bytes_out, &pkd));
+  GPX_TRY(sc.get(bytes_part, &ppart));
+  GPX_TRY(sc.get(M * 8, &pv));
+  double* W2 = W->p + keep * ldw;
+  GPX_TRY(launch_kfill(ctx, kp, X->p + keep * d, n2, Z->p, M, 0, nullptr, 0, 0.0, W2, n2p, mcp, ldw));
+  GPX_TRY(launch_gemm(ctx, L->p + keep * L->ld, L->ld, W->p, ldw, W2, ldw, n2p, mcp, keep, false, true, false));
+  GPX_TRY(chol_trsm_left(ctx, L->p + keep * (L->ld + 1), L->ld, L->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, W2, ldw, n2p, mcp));
+  GPX_TRY(launch_colreduce(ctx, W->p, ldw, n, mcp, nullptr, pout, ppart));
+  GPX_TRY(launch_kdiag(ctx, kp, Z->p, M, pkd));
+  hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
+                     (const double*)pout, M, pv);
+  hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, M, ctx->d_scal);
+  GPX_HIP(hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 // GP fit + IVAR in one call: K holds the assembled covariance and is factored in place exactly as gpx_potrf does; *out =
@@ -1447,10 +1401,9 @@ int gpx_col_sumsq(gpx_ctx* ctx, const gpx_mat* B, int64_t rows, double* out) {
   double *po, *pp;
   GPX_TRY(sc.get(B->pcols * 8, &po));
   GPX_TRY(sc.get(colreduce_partial_elems(B->prows, B->pcols) * 8 + 8, &pp));
-  int r = launch_colreduce(ctx, B->p, B->ld, rows, B->pcols, nullptr, po, pp);
-  if (r == 0 && hipMemcpyAsync(out, po, (size_t)B->cols * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = -2;
-  if (r == -2) gpx_set_error("col_sumsq: HIP copy failed");
-  return r;
+  GPX_TRY(launch_colreduce(ctx, B->p, B->ld, rows, B->pcols, nullptr, po, pp));
+  GPX_HIP(hipMemcpyAsync(out, po, (size_t)B->cols * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 // out[rows] = A v (host vectors; v has A->cols entries): a deterministic row reduction over the resident matrix
@@ -1461,15 +1414,11 @@ int gpx_matvec(gpx_ctx* ctx, const gpx_mat* A, const double* v, double* out) {
   double *pv, *po;
   GPX_TRY(sc.get(A->pcols * 8, &pv));
   GPX_TRY(sc.get((A->rows > 0 ? A->rows : 1) * 8, &po));
-  int r = 0;
-  do {
-    if (hipMemsetAsync(pv, 0, (size_t)A->pcols * 8, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(pv, v, (size_t)A->cols * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
-    if ((r = launch_rowreduce(ctx, A->p, A->ld, A->rows, A->pcols, pv, po)) != 0) break;
-    if (hipMemcpyAsync(out, po, (size_t)A->rows * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-  } while (0);
-  if (r == -2) gpx_set_error("matvec: HIP copy failed");
-  return r;
+  GPX_HIP(hipMemsetAsync(pv, 0, (size_t)A->pcols * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(pv, v, (size_t)A->cols * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, A->p, A->ld, A->rows, A->pcols, pv, po));
+  GPX_HIP(hipMemcpyAsync(out, po, (size_t)A->rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 // ---- measurement ---------------------------------------------------------------------------------------

@@ -885,47 +885,32 @@ static int leaf_mul_allow_lds(K kernel, size_t bytes) {
   return 0;
 }
 
+// one strip-multiply launch over m / ST strips.  The kernel is a template ARGUMENT, so every instantiation has a `once` of its
+// own: its LDS attribute is set once, on its first launch
+template <int ST, void (*KERNEL)(double*, int64_t, const double*, int)>
+static int launch_leaf_mul(gpx_ctx* ctx, size_t sh, double* X, int64_t ldx, const double* inv, int64_t m) {
+  static bool once = false;
+  if (!once) { GPX_TRY(leaf_mul_allow_lds(KERNEL, sh)); once = true; }
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)(m / ST)), dim3(256), sh, ctx->stream, X, ldx, inv, gpx_chain_prio(ctx));
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
 // X (m x 128) <- X * inv^T in place; m a multiple of 128
 static int launch_leaf_mul_right(gpx_ctx* ctx, double* X, int64_t ldx, const double* inv, int64_t m) {
   GPX_ARG(m % NB == 0 && (ldx % 2) == 0, "leaf multiply: rows must be a multiple of 128 and ld even");
   ProfScope ps(ctx, GPX_PROF_GEMM, 2.0 * (double)m * NB * NB, 0.0);
   // 32-row strips while they fill the chip once, 64-row strips (half the copies of the inverse) beyond that
-  if (m <= 32 * (int64_t)ctx->cus) {
-    constexpr int ST = 32;
-    const size_t sh = (size_t)(ST * LS) * sizeof(double);
-    static bool once = false;
-    if (!once) { GPX_TRY(leaf_mul_allow_lds(leaf_mul_right_kernel<ST>, sh)); once = true; }
-    hipLaunchKernelGGL(leaf_mul_right_kernel<ST>, dim3((unsigned)(m / ST)), dim3(256), sh, ctx->stream, X, ldx, inv, gpx_chain_prio(ctx));
-  } else {
-    constexpr int ST = 64;
-    const size_t sh = (size_t)(ST * LS) * sizeof(double);
-    static bool once = false;
-    if (!once) { GPX_TRY(leaf_mul_allow_lds(leaf_mul_right_kernel<ST>, sh)); once = true; }
-    hipLaunchKernelGGL(leaf_mul_right_kernel<ST>, dim3((unsigned)(m / ST)), dim3(256), sh, ctx->stream, X, ldx, inv, gpx_chain_prio(ctx));
-  }
-  GPX_HIP(hipGetLastError());
-  return 0;
+  if (m <= 32 * (int64_t)ctx->cus) return launch_leaf_mul<32, leaf_mul_right_kernel<32>>(ctx, 32 * LS * sizeof(double), X, ldx, inv, m);
+  return launch_leaf_mul<64, leaf_mul_right_kernel<64>>(ctx, 64 * LS * sizeof(double), X, ldx, inv, m);
 }
 
 // B (128 x m) <- inv * B in place; m a multiple of 128
 static int launch_leaf_mul_left(gpx_ctx* ctx, double* B, int64_t ldb, const double* inv, int64_t m) {
   GPX_ARG(m % NB == 0 && (ldb % 2) == 0, "leaf multiply: columns must be a multiple of 128 and ld even");
   ProfScope ps(ctx, GPX_PROF_GEMM, 2.0 * (double)m * NB * NB, 0.0);
-  if (m <= 32 * (int64_t)ctx->cus) {
-    constexpr int ST = 32;
-    const size_t sh = (size_t)(NB * (ST + 1)) * sizeof(double);
-    static bool once = false;
-    if (!once) { GPX_TRY(leaf_mul_allow_lds(leaf_mul_left_kernel<ST>, sh)); once = true; }
-    hipLaunchKernelGGL(leaf_mul_left_kernel<ST>, dim3((unsigned)(m / ST)), dim3(256), sh, ctx->stream, B, ldb, inv, gpx_chain_prio(ctx));
-  } else {
-    constexpr int ST = 64;
-    const size_t sh = (size_t)(NB * (ST + 1)) * sizeof(double);
-    static bool once = false;
-    if (!once) { GPX_TRY(leaf_mul_allow_lds(leaf_mul_left_kernel<ST>, sh)); once = true; }
-    hipLaunchKernelGGL(leaf_mul_left_kernel<ST>, dim3((unsigned)(m / ST)), dim3(256), sh, ctx->stream, B, ldb, inv, gpx_chain_prio(ctx));
-  }
-  GPX_HIP(hipGetLastError());
-  return 0;
+  if (m <= 32 * (int64_t)ctx->cus) return launch_leaf_mul<32, leaf_mul_left_kernel<32>>(ctx, NB * (32 + 1) * sizeof(double), B, ldb, inv, m);
+  return launch_leaf_mul<64, leaf_mul_left_kernel<64>>(ctx, NB * (64 + 1) * sizeof(double), B, ldb, inv, m);
 }
 
 int launch_leaf(gpx_ctx* ctx, double* A, int64_t ld, double* inv, int64_t base_index, int64_t n_valid) {
@@ -1199,18 +1184,14 @@ static int potrf_blocked(gpx_ctx* ctx, double* A, int64_t ld, int64_t n, double*
     GPX_TRY(launch_gemm(ctx, P, ld, P, ld, C, ld, w2, w2, w, true, true, true));
     spans.push_back({"top", j0 / B, t0, mark(M)});
     GPX_HIP(hipEventRecord(ev_col, M));
-    ctx->stream = S;
-    int r = 0;
-    if (hipStreamWaitEvent(S, ev_col, 0) != hipSuccess) r = -2;
-    t0 = mark(S);
-    if (r == 0) r = potrf_rec(ctx, C, ld, w2, invn, base + j0 + w, n_valid);
-    if (r == 0 && bi) r = binv_build_range(ctx, C, ld, invn, binv_at(j0 + w), ib, w2, ctx->pw_tmp_build);
-    spans.push_back({"chain", j0 / B, t0, mark(S)});
-    if (r == 0 && hipEventRecord(ev_diag, S) != hipSuccess) r = -2;
-    ctx->stream = M;
-    if (r != 0) {
-      if (r == -2) gpx_set_error("potrf: look-ahead stream plumbing failed");
-      return r;
+    {
+      StreamScope chain(ctx, S);
+      GPX_HIP(hipStreamWaitEvent(S, ev_col, 0));
+      t0 = mark(S);
+      GPX_TRY(potrf_rec(ctx, C, ld, w2, invn, base + j0 + w, n_valid));
+      if (bi) GPX_TRY(binv_build_range(ctx, C, ld, invn, binv_at(j0 + w), ib, w2, ctx->pw_tmp_build));
+      spans.push_back({"chain", j0 / B, t0, mark(S)});
+      GPX_HIP(hipEventRecord(ev_diag, S));
     }
     if (rest > 0) {
       double* P2 = P + w2 * ld;
@@ -1452,7 +1433,7 @@ int chol_binv_ensure(gpx_ctx* ctx, gpx_mat* Lm) {
   if (r == 0) r = chol_binv_finish(ctx, Lm, ib);
   (void)hipStreamSynchronize(ctx->stream);  // the product slabs go back to the pool
   gpx_dev_release(ctx, pt, nblk * ib * ib * 8);
-  if (r != 0) Lm->binv_ib = 0;
+  if (r != 0) Lm->binv_ib = 0;   // (why a status and no early return: a half-built cache must not pass for the inverses)
   return r;
 }
 

@@ -119,11 +119,6 @@ __global__ __launch_bounds__(256) void ivar_cost_kernel(const double* __restrict
   cost[j] = fabs((s0 - q[j] / (kcc[j] - ssc[j] + noise)) * inv_nmc);
 }
 
-int check_points(const gpx_mat* P, int d) {
-  GPX_ARG(P && P->cols == d && P->pcols == d, "point sets must be unpadded (n x d)");
-  return 0;
-}
-
 double pairwise_sum(std::vector<double>& v, int64_t m) {
   if (m == 0) return 0.0;
   while (m > 1) {
@@ -320,15 +315,10 @@ int gpx_kernel_eval(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
 int gpx_posterior_cov(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                       const gpx_mat* Z, double* cov) {
   GPX_ARG(ctx && L && X && Z && cov, "NULL argument");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_TRY(check_points(X, d));
-  GPX_TRY(check_points(Z, d));
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", &kp));
   const int64_t n = L->rows, np = L->prows, m = Z->rows, mp = gpx_round_up(m > 0 ? m : 1, GPX_TILE);
-  GPX_ARG(X->rows == n, "X does not match the factor");
   if (m == 0) return 0;
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   Scratch sc(ctx);
   void *pW, *pWt, *pK;
   GPX_TRY(sc.get(np * mp * 8, &pW));
@@ -353,33 +343,25 @@ int gpx_potri_impl(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP, int full) {
   GPX_ARG(ctx && L && outP, "NULL argument");
   GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   const int64_t np = L->prows;
-  gpx_mat* P = nullptr;
-  GPX_TRY(gpx_mat_new(ctx, L->rows, L->cols, 1, &P));
+  MatHold P(ctx);
+  GPX_TRY(gpx_mat_new(ctx, L->rows, L->cols, 1, P.put()));
   Scratch sc(ctx);
-  void *pI, *pT, *ptmp;
-  int r = 0;
-  do {
-    if ((r = sc.get(np * np * 8, &pI)) != 0) break;
-    if ((r = sc.get(np * np * 8, &pT)) != 0) break;
-    if ((r = sc.get((np / 2 + 64) * (np / 2 + 64) * 8, &ptmp)) != 0) break;
-    if ((r = chol_trtri(ctx, L, (double*)pI, (double*)ptmp)) != 0) break;                           // L^-1
-    if ((r = launch_transpose(ctx, (double*)pI, np, np, np, (double*)pT, np)) != 0) break;          // U = L^-T
-    // lower triangle of U U^T with the structurally zero part of every tile's k range skipped (N^3/3); `full`: the upper one is
-    // its mirror image (two passes over N^2 doubles) -- round 3 formed both triangles by a dense product (2 N^3)
-    if ((r = launch_gemm_tri(ctx, (double*)pT, np, (double*)pT, np, P->p, P->ld, np, np, np, true, false, true, 3)) != 0) break;
-    if (full) {
-      hipLaunchKernelGGL(mirror_lower_kernel, dim3((unsigned)(np / 32), (unsigned)(np / 32)), dim3(256), 0, ctx->stream, P->p,
-                         P->ld);
-      if (hipGetLastError() != hipSuccess) r = -2;
-    }
-  } while (0);
-  if (r != 0) {
-    gpx_mat_free(ctx, P);
-    if (r == -2) gpx_set_error("potri: HIP call failed");
-    return r;
+  double *pI, *pT, *ptmp;
+  GPX_TRY(sc.get(np * np * 8, &pI));
+  GPX_TRY(sc.get(np * np * 8, &pT));
+  GPX_TRY(sc.get((np / 2 + 64) * (np / 2 + 64) * 8, &ptmp));
+  GPX_TRY(chol_trtri(ctx, L, pI, ptmp));                           // L^-1
+  GPX_TRY(launch_transpose(ctx, pI, np, np, np, pT, np));          // U = L^-T
+  // lower triangle of U U^T with the structurally zero part of every tile's k range skipped (N^3/3); `full`: the upper one is
+  // its mirror image (two passes over N^2 doubles) -- round 3 formed both triangles by a dense product (2 N^3)
+  GPX_TRY(launch_gemm_tri(ctx, pT, np, pT, np, P->p, P->ld, np, np, np, true, false, true, 3));
+  if (full) {
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3((unsigned)(np / 32), (unsigned)(np / 32)), dim3(256), 0, ctx->stream, P->p,
+                       P->ld);
+    GPX_HIP(hipGetLastError());
   }
   GPX_HIP(hipStreamSynchronize(ctx->stream));
-  *outP = P;
+  *outP = P.release();
   return 0;
 }
 
@@ -391,7 +373,7 @@ int gpx_greedy_var(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
   GPX_ARG(nkeep >= 0 && nsel >= nkeep && (nkeep == 0 || keep), "bad keep/nsel");
   KParams kp;
   GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_TRY(check_points(Cm, d));
+  GPX_ARG(Cm->cols == d && Cm->pcols == d, "point sets must be unpadded (n x d)");
   const int64_t M = Cm->rows;
   GPX_ARG(M > 0, "no candidates");
   for (int64_t i = 0; i < nkeep; ++i) GPX_ARG(keep[i] >= 0 && keep[i] < M, "keep index out of range");
@@ -444,16 +426,10 @@ int gpx_greedy_ivar_step(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
                          const gpx_mat* X, const gpx_mat* Cm, const gpx_mat* Z, double noise, double* out_cost,
                          int64_t* out_best) {
   GPX_ARG(ctx && L && X && Cm && Z && out_best, "NULL argument");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_TRY(check_points(X, d));
-  GPX_TRY(check_points(Cm, d));
-  GPX_TRY(check_points(Z, d));
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, Cm, "point sets must be unpadded (n x d)", &kp));
   const int64_t n = L->rows, np = L->prows, M = Cm->rows, nmc = Z->rows;
-  GPX_ARG(X->rows == n, "X does not match the factor");
   GPX_ARG(M > 0 && nmc > 0, "need candidates and integration points");
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z, Cm));
   const int64_t zp = gpx_round_up(nmc, GPX_TILE);
   // candidate chunk: W_C (np x mc) + G (zp x mc) under ~24 GiB
   int64_t budget = (int64_t)24 << 30;
@@ -570,18 +546,12 @@ int64_t gpx_givar_pivot_elems(const gpx_givar* st) { return st ? st->pack : 0; }
 int gpx_givar_begin(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                     const gpx_mat* Cm, const gpx_mat* Z, double noise, int64_t nsel, gpx_givar** out) {
   GPX_ARG(ctx && L && X && Cm && Z && out, "NULL argument");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_TRY(check_points(X, d));
-  GPX_TRY(check_points(Cm, d));
-  GPX_TRY(check_points(Z, d));
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, Cm, "point sets must be unpadded (n x d)", &kp));
   const int64_t n = L->rows, np = L->prows, M = Cm->rows, nmc = Z->rows;
-  GPX_ARG(X->rows == n, "X does not match the factor");
   GPX_ARG(M > 0 && nmc > 0 && nsel >= 1, "need candidates, integration points and at least one pick");
-  GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z, Cm));
   const int64_t zp = gpx_round_up(nmc, GPX_TILE), Mp = gpx_round_up(M, GPX_TILE);
-  gpx_givar* st = new gpx_givar();
+  Held<gpx_givar, gpx_givar_end> st(ctx, new gpx_givar());
   st->kp = kp; st->d = d; st->Cm = Cm; st->n = n; st->np = np; st->M = M; st->Mp = Mp; st->nmc = nmc; st->zp = zp;
   st->nsel = nsel; st->cur = 0; st->noise = noise; st->s0 = 0.0;
   st->chunk = 128; st->nchunk = (zp + st->chunk - 1) / st->chunk;
@@ -592,59 +562,51 @@ int gpx_givar_begin(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
     const int64_t a = colreduce_partial_elems(np, Mp), b = colreduce_partial_elems(zp, Mp), c = colreduce_partial_elems(np, zp);
     st->part_elems = a > b ? (a > c ? a : c) : (b > c ? b : c);
   }
-  int r = 0;
-  void* p;
   Scratch sc(ctx);   // the work buffers of the set-up; everything in `st` is resident state and stays with it
   double *pWz = nullptr, *pWzt = nullptr, *pss = nullptr, *pkd = nullptr;
   const int64_t wide = zp > Mp ? zp : Mp;
-  do {
-    if ((r = gpx_dev_alloc(ctx, np * Mp * 8, &p)) != 0) break; st->Wc = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, zp * Mp * 8, &p)) != 0) break; st->G = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, nsel * Mp * 8, &p)) != 0) break; st->U = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, Mp * 8, &p)) != 0) break; st->v = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, Mp * 8, &p)) != 0) break; st->q = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, Mp * 8, &p)) != 0) break; st->cost = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, Mp * 8, &p)) != 0) break; st->hdot = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, st->part_elems * 8 + 8, &p)) != 0) break; st->part = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, st->nchunk * Mp * 8, &p)) != 0) break; st->qpart = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, st->pack * 8, &p)) != 0) break; st->buf = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, 1024 * 8, &p)) != 0) break; st->red = (double*)p;
-    if ((r = gpx_dev_alloc(ctx, 1024 * 8, &p)) != 0) break; st->redi = (int64_t*)p;
-    if ((r = sc.get(np * zp * 8, &pWz)) != 0) break;
-    if ((r = sc.get(np * zp * 8, &pWzt)) != 0) break;
-    if ((r = sc.get(wide * 8, &pss)) != 0) break;
-    if ((r = sc.get(wide * 8, &pkd)) != 0) break;
-    // ---- integration points: W_Z = L^-1 K(X, Z), var_z, S0 -- the launches of gpx_greedy_ivar_step, in its order ----
-    if ((r = launch_kfill(ctx, kp, X->p, n, Z->p, nmc, 0, nullptr, 0, 0.0, pWz, np, zp, zp)) != 0) break;
-    if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, pWz, zp, np, zp)) != 0) break;
-    if ((r = launch_colreduce(ctx, pWz, zp, n, zp, nullptr, pss, st->part)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Z->p, nmc, pkd)) != 0) break;
-    std::vector<double> hs((size_t)nmc), hk((size_t)nmc);
-    if (hipMemcpyAsync(hs.data(), pss, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    if (hipMemcpyAsync(hk.data(), pkd, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    if ((r = launch_transpose(ctx, pWz, np, zp, zp, pWzt, np)) != 0) break;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { r = -2; break; }
-    for (int64_t j = 0; j < nmc; ++j) hk[(size_t)j] -= hs[(size_t)j];
-    st->s0 = pairwise_sum(hk, nmc);
-    // ---- candidates: W_C, v, G = K(Z, C) - W_Z^T W_C, q ----
-    if ((r = launch_kfill(ctx, kp, X->p, n, Cm->p, M, 0, nullptr, 0, 0.0, st->Wc, np, Mp, Mp)) != 0) break;
-    if ((r = chol_trsm_left(ctx, L->p, L->ld, L->aux, st->Wc, Mp, np, Mp)) != 0) break;
-    if ((r = launch_colreduce(ctx, st->Wc, Mp, n, Mp, nullptr, pss, st->part)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, Cm->p, M, pkd)) != 0) break;
-    hipLaunchKernelGGL(givar_v_kernel, dim3((unsigned)(Mp / 256 + 1)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                       (const double*)pss, M, Mp, st->v);
-    if ((r = launch_kfill(ctx, kp, Z->p, nmc, Cm->p, M, 0, nullptr, 0, 0.0, st->G, zp, Mp, Mp)) != 0) break;
-    if ((r = launch_gemm(ctx, pWzt, np, st->Wc, Mp, st->G, Mp, zp, Mp, np, false, true, false)) != 0) break;
-    if ((r = launch_colreduce(ctx, st->G, Mp, nmc, Mp, nullptr, st->q, st->part)) != 0) break;
-    if (hipMemsetAsync(st->U, 0, (size_t)(nsel * Mp * 8), ctx->stream) != hipSuccess) { r = -2; break; }
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { r = -2; break; }
-  } while (0);
-  if (r != 0) {
-    gpx_givar_end(ctx, st);
-    if (r == -2) gpx_set_error("givar_begin: HIP call failed");
-    return r;
-  }
-  *out = st;
+  GPX_TRY(gpx_dev_alloc(ctx, np * Mp * 8, &st->Wc));
+  GPX_TRY(gpx_dev_alloc(ctx, zp * Mp * 8, &st->G));
+  GPX_TRY(gpx_dev_alloc(ctx, nsel * Mp * 8, &st->U));
+  GPX_TRY(gpx_dev_alloc(ctx, Mp * 8, &st->v));
+  GPX_TRY(gpx_dev_alloc(ctx, Mp * 8, &st->q));
+  GPX_TRY(gpx_dev_alloc(ctx, Mp * 8, &st->cost));
+  GPX_TRY(gpx_dev_alloc(ctx, Mp * 8, &st->hdot));
+  GPX_TRY(gpx_dev_alloc(ctx, st->part_elems * 8 + 8, &st->part));
+  GPX_TRY(gpx_dev_alloc(ctx, st->nchunk * Mp * 8, &st->qpart));
+  GPX_TRY(gpx_dev_alloc(ctx, st->pack * 8, &st->buf));
+  GPX_TRY(gpx_dev_alloc(ctx, 1024 * 8, &st->red));
+  GPX_TRY(gpx_dev_alloc(ctx, 1024 * 8, &st->redi));
+  GPX_TRY(sc.get(np * zp * 8, &pWz));
+  GPX_TRY(sc.get(np * zp * 8, &pWzt));
+  GPX_TRY(sc.get(wide * 8, &pss));
+  GPX_TRY(sc.get(wide * 8, &pkd));
+  // ---- integration points: W_Z = L^-1 K(X, Z), var_z, S0 -- the launches of gpx_greedy_ivar_step, in its order ----
+  GPX_TRY(launch_kfill(ctx, kp, X->p, n, Z->p, nmc, 0, nullptr, 0, 0.0, pWz, np, zp, zp));
+  GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, pWz, zp, np, zp));
+  GPX_TRY(launch_colreduce(ctx, pWz, zp, n, zp, nullptr, pss, st->part));
+  GPX_TRY(launch_kdiag(ctx, kp, Z->p, nmc, pkd));
+  std::vector<double> hs((size_t)nmc), hk((size_t)nmc);
+  GPX_HIP(hipMemcpyAsync(hs.data(), pss, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(hk.data(), pkd, (size_t)nmc * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_TRY(launch_transpose(ctx, pWz, np, zp, zp, pWzt, np));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  for (int64_t j = 0; j < nmc; ++j) hk[(size_t)j] -= hs[(size_t)j];
+  st->s0 = pairwise_sum(hk, nmc);
+  // ---- candidates: W_C, v, G = K(Z, C) - W_Z^T W_C, q ----
+  GPX_TRY(launch_kfill(ctx, kp, X->p, n, Cm->p, M, 0, nullptr, 0, 0.0, st->Wc, np, Mp, Mp));
+  GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, st->Wc, Mp, np, Mp));
+  GPX_TRY(launch_colreduce(ctx, st->Wc, Mp, n, Mp, nullptr, pss, st->part));
+  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, pkd));
+  hipLaunchKernelGGL(givar_v_kernel, dim3((unsigned)(Mp / 256 + 1)), dim3(256), 0, ctx->stream, (const double*)pkd,
+                     (const double*)pss, M, Mp, st->v);
+  GPX_TRY(launch_kfill(ctx, kp, Z->p, nmc, Cm->p, M, 0, nullptr, 0, 0.0, st->G, zp, Mp, Mp));
+  GPX_TRY(launch_gemm(ctx, pWzt, np, st->Wc, Mp, st->G, Mp, zp, Mp, np, false, true, false));
+  GPX_TRY(launch_colreduce(ctx, st->G, Mp, nmc, Mp, nullptr, st->q, st->part));
+  GPX_HIP(hipMemsetAsync(st->U, 0, (size_t)(nsel * Mp * 8), ctx->stream));
+  GPX_HIP(hipGetLastError());
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  *out = st.release();
   return 0;
 }
 
@@ -719,29 +681,26 @@ int gpx_greedy_ivar(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
                     const gpx_mat* Cm, const gpx_mat* Z, double noise, int64_t nsel, int64_t* out_idx, double* out_cost,
                     double* all_costs) {
   GPX_ARG(out_idx != nullptr, "NULL argument");
-  gpx_givar* st = nullptr;
-  GPX_TRY(gpx_givar_begin(ctx, kind, d, hyp, nhyp, L, X, Cm, Z, noise, nsel, &st));
-  gpx_mat* buf = nullptr;
-  int r = gpx_mat_alloc(ctx, st->pack, 1, 0, &buf);
-  for (int64_t t = 0; r == 0 && t < nsel; ++t) {
+  Held<gpx_givar, gpx_givar_end> st(ctx);
+  GPX_TRY(gpx_givar_begin(ctx, kind, d, hyp, nhyp, L, X, Cm, Z, noise, nsel, st.put()));
+  MatHold buf(ctx);
+  GPX_TRY(gpx_mat_alloc(ctx, st->pack, 1, 0, buf.put()));
+  for (int64_t t = 0; t < nsel; ++t) {
     double c = 0.0;
     int64_t s = 0;
-    if ((r = gpx_givar_score(ctx, st, &c, &s, all_costs ? all_costs + t * st->M : nullptr)) != 0) break;
+    GPX_TRY(gpx_givar_score(ctx, st.get(), &c, &s, all_costs ? all_costs + t * st->M : nullptr));
     if (s >= st->M) {
       gpx_set_error("greedy IVAR: pick %lld of %lld: no candidate has a finite cost (every remaining one is already in the design "
                     "with zero noise, or the state is not finite)", (long long)(t + 1), (long long)nsel);
-      r = -1;
-      break;
+      return -1;
     }
     out_idx[t] = s;
     if (out_cost) out_cost[t] = c;
     if (t + 1 == nsel) break;
-    if ((r = gpx_givar_pack(ctx, st, s, buf)) != 0) break;
-    r = gpx_givar_apply(ctx, st, buf);
+    GPX_TRY(gpx_givar_pack(ctx, st.get(), s, buf.get()));
+    GPX_TRY(gpx_givar_apply(ctx, st.get(), buf.get()));
   }
-  if (buf) gpx_mat_free(ctx, buf);
-  gpx_givar_end(ctx, st);
-  return r;
+  return 0;   // (buf, then the state: the holders let go in reverse order, as the hand-written exit did)
 }
 
 }  // extern "C"

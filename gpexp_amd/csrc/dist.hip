@@ -460,7 +460,7 @@ int gpx_comm_allgather_host(gpx_ctx* ctx, const double* in, int64_t n, double* o
     gpx_dev_release(ctx, ps_, n * 8);
     return r;
   }
-  do {
+  do {   // (a status ladder on purpose: r also carries the RCCL failure, -3, and both blocks go back below on every exit)
     if (hipMemcpyAsync(ps_, in, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { r = -2; break; }
     if (g_rccl.AllGather(ps_, pr, (size_t)n, ncclFloat64, (ncclComm_t)ctx->comm, ctx->stream) != 0) { r = -3; break; }
     if (hipMemcpyAsync(out, pr, (size_t)n * 8 * ctx->world, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }

@@ -180,98 +180,75 @@ int gpx_fitc_free(gpx_ctx* ctx, gpx_fitc* f) {
 int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
                  double noise, gpx_fitc** out) {
   GPX_ARG(ctx && X && S && out, "NULL argument");
-  gpx_fitc* f = new gpx_fitc();
+  Held<gpx_fitc, gpx_fitc_free> f(ctx, new gpx_fitc());
   f->Lu = f->Kuf = f->W = f->Ks = f->La = nullptr;
   f->g = f->ginv = nullptr;
-  int r = gpx_make_kparams(kind, d, hyp, nhyp, &f->kp);
-  if (r != 0) {
-    delete f;
-    return r;
-  }
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &f->kp));
   if (!(X->cols == d && X->pcols == d && S->cols == d && S->pcols == d && S->rows > 0 && X->rows > 0)) {
-    delete f;
     gpx_set_error("fitc: X and the inducing points must be non-empty unpadded (n x d) point sets");
     return -1;
   }
-  if ((r = gpx_kparams_sets(ctx, &f->kp, X, S)) != 0) {
-    delete f;
-    return r;
-  }
+  GPX_TRY(gpx_kparams_sets(ctx, &f->kp, X, S));
   const KParams& kp = f->kp;
   f->n = X->rows;
   f->nu = S->rows;
   f->noise = noise;
   Scratch tmp(ctx);
-  do {
-    // Lu = chol(K(S,S) + noise I)
-    if ((r = gpx_mat_new(ctx, f->nu, f->nu, 1, &f->Lu)) != 0) break;
-    f->nup = f->Lu->prows;
-    if ((r = launch_kfill(ctx, kp, S->p, f->nu, S->p, f->nu, 1, nullptr, 1, noise, f->Lu->p, f->nup, f->nup,
-                          f->Lu->ld)) != 0) break;
-    if ((r = factor_in_place(ctx, f->Lu, "K(inducing, inducing) + noise")) != 0) break;
-    // Kuf, W = Lu^-1 Kuf
-    if ((r = gpx_mat_new(ctx, f->nu, f->n, 1, &f->Kuf)) != 0) break;
-    f->np = f->Kuf->pcols;
-    if ((r = gpx_mat_new(ctx, f->nu, f->n, 1, &f->W)) != 0) break;
-    if ((r = gpx_mat_new(ctx, f->nu, f->n, 1, &f->Ks)) != 0) break;
-    if ((r = launch_kfill(ctx, kp, S->p, f->nu, X->p, f->n, 0, nullptr, 0, 0.0, f->Kuf->p, f->nup, f->np,
-                          f->Kuf->ld)) != 0) break;
-    // (out of place through Lu's 1024-order block inverses, every product K >= 1024 on 128-tiles: 7.9 ms against 9.3 for the
-    // in-place leaf recursion at nu = 4096, N = 32768.  The solve consumes its right-hand side: a second fill of Kuf into Ks --
-    // which is only written further down -- costs 0.19 ms, the copy it replaces 0.61.)
-    if ((r = launch_kfill(ctx, kp, S->p, f->nu, X->p, f->n, 0, nullptr, 0, 0.0, f->Ks->p, f->nup, f->np,
-                          f->Ks->ld)) != 0) break;
-    if ((r = chol_trsm_left_oop(ctx, f->Lu, f->Ks->p, f->Ks->ld, f->W->p, f->W->ld, f->np)) != 0) break;
-    // g = diag(K) + noise - colsum(W^2)
-    double *qd, *kd, *part;
-    void* pg;
-    if ((r = tmp.get(f->np * 8, &qd)) != 0) break;
-    if ((r = tmp.get(f->np * 8, &kd)) != 0) break;
-    if ((r = tmp.get(colreduce_partial_elems(f->nup, f->np) * 8 + 8, &part)) != 0) break;
-    if ((r = gpx_dev_alloc(ctx, f->np * 8, &pg)) != 0) break;
-    f->g = (double*)pg;
-    if ((r = gpx_dev_alloc(ctx, f->np * 8, &pg)) != 0) break;
-    f->ginv = (double*)pg;
-    if ((r = launch_colreduce(ctx, f->W->p, f->W->ld, f->nu, f->np, nullptr, qd, part)) != 0) break;
-    if ((r = launch_kdiag(ctx, kp, X->p, f->n, kd)) != 0) break;
-    hipLaunchKernelGGL(fitc_g_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, kd, qd, noise,
-                       f->n, f->np, f->g, f->ginv);
-    hipLaunchKernelGGL(log_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, f->g, f->n, ctx->d_scal);
-    if (hipMemcpyAsync(&f->sumlogg, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { r = -2; break; }
-    // Ks = -Kuf Gi;  A = Quu + Kuf Gi Kfu = Quu - Ks Kuf^T;  La = chol(A)
-    {
-      dim3 grid((unsigned)((f->np / 2 + 255) / 256), (unsigned)f->nup);
-      hipLaunchKernelGGL(scale_cols_neg_kernel, grid, dim3(256), 0, ctx->stream, f->Kuf->p, f->Kuf->ld, f->ginv, f->Ks->p,
-                         f->Ks->ld, f->np);
-    }
-    if ((r = gpx_mat_new(ctx, f->nu, f->nu, 1, &f->La)) != 0) break;
-    if ((r = launch_kfill(ctx, kp, S->p, f->nu, S->p, f->nu, 1, nullptr, 1, noise, f->La->p, f->nup, f->nup,
-                          f->La->ld)) != 0) break;
-    // nu x nu under a k range of N: as slices of the k range when C alone cannot fill the chip with 128-tiles (gemm_f64.hip,
-    // launch_gemm_ksplit: 11.2 -> 9.0 ms at nu = 4096, N = 32768; 1024 or 4096 tiles wanted instead of 2048: no faster)
-    {
-      const int64_t t128 = (f->nup / 128) * (f->nup / 128 + 1) / 2;
-      int64_t parts = 1;
-      while (parts < 16 && t128 * parts < 2048 && f->np % (2 * parts * 16) == 0 && f->np / (2 * parts) >= 4096) parts *= 2;
-      double* P = nullptr;
-      if (parts > 1 && tmp.get(parts * f->nup * f->nup * 8, &P) != 0) parts = 1;   // (no room for the partials: one launch)
-      if (parts > 1)
-        r = launch_gemm_ksplit(ctx, f->Ks->p, f->Ks->ld, f->Kuf->p, f->Kuf->ld, f->La->p, f->La->ld, f->nup, f->nup, f->np, true,
-                               parts, P);
-      else
-        r = launch_gemm(ctx, f->Ks->p, f->Ks->ld, f->Kuf->p, f->Kuf->ld, f->La->p, f->La->ld, f->nup, f->nup, f->np, true, true,
-                        true);
-      if (r != 0) break;
-    }
-    if ((r = factor_in_place(ctx, f->La, "Quu + Kuf G^-1 Kfu")) != 0) break;
-    if (hipGetLastError() != hipSuccess) { r = -2; break; }
-  } while (0);
-  if (r != 0) {
-    if (r == -2) gpx_set_error("fitc_fit: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-    fitc_release(ctx, f);
-    return r;
+  // Lu = chol(K(S,S) + noise I)
+  GPX_TRY(gpx_mat_new(ctx, f->nu, f->nu, 1, &f->Lu));
+  f->nup = f->Lu->prows;
+  GPX_TRY(launch_kfill(ctx, kp, S->p, f->nu, S->p, f->nu, 1, nullptr, 1, noise, f->Lu->p, f->nup, f->nup, f->Lu->ld));
+  GPX_TRY(factor_in_place(ctx, f->Lu, "K(inducing, inducing) + noise"));
+  // Kuf, W = Lu^-1 Kuf
+  GPX_TRY(gpx_mat_new(ctx, f->nu, f->n, 1, &f->Kuf));
+  f->np = f->Kuf->pcols;
+  GPX_TRY(gpx_mat_new(ctx, f->nu, f->n, 1, &f->W));
+  GPX_TRY(gpx_mat_new(ctx, f->nu, f->n, 1, &f->Ks));
+  GPX_TRY(launch_kfill(ctx, kp, S->p, f->nu, X->p, f->n, 0, nullptr, 0, 0.0, f->Kuf->p, f->nup, f->np, f->Kuf->ld));
+  // (out of place through Lu's 1024-order block inverses, every product K >= 1024 on 128-tiles: 7.9 ms against 9.3 for the
+  // in-place leaf recursion at nu = 4096, N = 32768.  The solve consumes its right-hand side: a second fill of Kuf into Ks --
+  // which is only written further down -- costs 0.19 ms, the copy it replaces 0.61.)
+  GPX_TRY(launch_kfill(ctx, kp, S->p, f->nu, X->p, f->n, 0, nullptr, 0, 0.0, f->Ks->p, f->nup, f->np, f->Ks->ld));
+  GPX_TRY(chol_trsm_left_oop(ctx, f->Lu, f->Ks->p, f->Ks->ld, f->W->p, f->W->ld, f->np));
+  // g = diag(K) + noise - colsum(W^2)
+  double *qd, *kd, *part;
+  GPX_TRY(tmp.get(f->np * 8, &qd));
+  GPX_TRY(tmp.get(f->np * 8, &kd));
+  GPX_TRY(tmp.get(colreduce_partial_elems(f->nup, f->np) * 8 + 8, &part));
+  GPX_TRY(gpx_dev_alloc(ctx, f->np * 8, &f->g));
+  GPX_TRY(gpx_dev_alloc(ctx, f->np * 8, &f->ginv));
+  GPX_TRY(launch_colreduce(ctx, f->W->p, f->W->ld, f->nu, f->np, nullptr, qd, part));
+  GPX_TRY(launch_kdiag(ctx, kp, X->p, f->n, kd));
+  hipLaunchKernelGGL(fitc_g_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, kd, qd, noise,
+                     f->n, f->np, f->g, f->ginv);
+  hipLaunchKernelGGL(log_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, f->g, f->n, ctx->d_scal);
+  GPX_HIP(hipMemcpyAsync(&f->sumlogg, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  // Ks = -Kuf Gi;  A = Quu + Kuf Gi Kfu = Quu - Ks Kuf^T;  La = chol(A)
+  {
+    dim3 grid((unsigned)((f->np / 2 + 255) / 256), (unsigned)f->nup);
+    hipLaunchKernelGGL(scale_cols_neg_kernel, grid, dim3(256), 0, ctx->stream, f->Kuf->p, f->Kuf->ld, f->ginv, f->Ks->p,
+                       f->Ks->ld, f->np);
   }
-  *out = f;
+  GPX_TRY(gpx_mat_new(ctx, f->nu, f->nu, 1, &f->La));
+  GPX_TRY(launch_kfill(ctx, kp, S->p, f->nu, S->p, f->nu, 1, nullptr, 1, noise, f->La->p, f->nup, f->nup, f->La->ld));
+  // nu x nu under a k range of N: as slices of the k range when C alone cannot fill the chip with 128-tiles (gemm_f64.hip,
+  // launch_gemm_ksplit: 11.2 -> 9.0 ms at nu = 4096, N = 32768; 1024 or 4096 tiles wanted instead of 2048: no faster)
+  {
+    const int64_t t128 = (f->nup / 128) * (f->nup / 128 + 1) / 2;
+    int64_t parts = 1;
+    while (parts < 16 && t128 * parts < 2048 && f->np % (2 * parts * 16) == 0 && f->np / (2 * parts) >= 4096) parts *= 2;
+    double* P = nullptr;
+    if (parts > 1 && tmp.get(parts * f->nup * f->nup * 8, &P) != 0) parts = 1;   // (no room for the partials: one launch)
+    if (parts > 1)
+      GPX_TRY(launch_gemm_ksplit(ctx, f->Ks->p, f->Ks->ld, f->Kuf->p, f->Kuf->ld, f->La->p, f->La->ld, f->nup, f->nup, f->np, true,
+                                 parts, P));
+    else
+      GPX_TRY(launch_gemm(ctx, f->Ks->p, f->Ks->ld, f->Kuf->p, f->Kuf->ld, f->La->p, f->La->ld, f->nup, f->nup, f->np, true, true,
+                          true));
+  }
+  GPX_TRY(factor_in_place(ctx, f->La, "Quu + Kuf G^-1 Kfu"));
+  GPX_HIP(hipGetLastError());
+  *out = f.release();
   return 0;
 }
 

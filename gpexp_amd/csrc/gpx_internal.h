@@ -193,7 +193,20 @@ struct gpx_ctx {
 
 // centre + exact-path decision for fills between the given point sets (any may be NULL); see KParams
 int gpx_kparams_sets(gpx_ctx* ctx, KParams* kp, const gpx_mat* A, const gpx_mat* B = nullptr, const gpx_mat* C = nullptr);
+// The prologue of the (kind, d, hyp, nhyp, L, X, Z) entry points (api.hip), after the caller's own NULL check of ctx, X, Z, C:
+// the kernel parameters, a factor that gpx_potrf produced, unpadded point sets (Z, C nullable; a failure reads `points_msg`: the
+// callers have two wordings), X of the factor's order, and -- for the callers that fill between point sets, i.e. pass a Z -- the
+// centre / exact-path decision of gpx_kparams_sets(X, Z, C).
+int gpx_entry_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                   const gpx_mat* Z, const gpx_mat* C, const char* points_msg, KParams* kp);
 int gpx_dev_alloc(gpx_ctx* ctx, int64_t bytes, void** out);
+template <typename T>
+int gpx_dev_alloc(gpx_ctx* ctx, int64_t bytes, T** out) {   // typed form, for a field that keeps the block
+  void* p = nullptr;
+  const int r = gpx_dev_alloc(ctx, bytes, &p);
+  if (r == 0) *out = (T*)p;
+  return r;
+}
 void gpx_dev_release(gpx_ctx* ctx, void* p, int64_t bytes);
 int gpx_mat_new(gpx_ctx* ctx, int64_t rows, int64_t cols, int pad, gpx_mat** out);
 
@@ -236,6 +249,46 @@ class Scratch {
   std::vector<std::pair<void*, int64_t>> bufs;
 };
 
+// Owner of an object created inside a call and handed to the caller only on success (a gpx_mat, the resident state of
+// gpx_givar_begin / gpx_mi_begin / gpx_fitc_fit): unless released, FREE takes it back on scope exit.  Those free functions fence or
+// synchronise themselves, so the holder does not.  Declared BEFORE the Scratch of the same function: scratch is then synchronised
+// and released first.
+template <class T, int (*FREE)(gpx_ctx*, T*)>
+class Held {
+ public:
+  explicit Held(gpx_ctx* c, T* obj = nullptr) : ctx(c), p(obj) {}
+  Held(const Held&) = delete;
+  Held& operator=(const Held&) = delete;
+  ~Held() { reset(); }
+  T** put() { return &p; }   // for the out-parameter of the call that creates the object
+  T* get() const { return p; }
+  T* operator->() const { return p; }
+  T* release() {
+    T* r = p;
+    p = nullptr;
+    return r;
+  }
+  void reset() {
+    if (p) (void)FREE(ctx, p);
+    p = nullptr;
+  }
+
+ private:
+  gpx_ctx* ctx;
+  T* p;
+};
+using MatHold = Held<gpx_mat, gpx_mat_free>;
+
+// ctx->stream switched to another stream of the context for a scope; the previous selection comes back on every exit
+struct StreamScope {
+  gpx_ctx* ctx;
+  hipStream_t prev;
+  StreamScope(gpx_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { c->stream = s; }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+  ~StreamScope() { ctx->stream = prev; }
+};
+
 // RAII-ish profiling bracket: records events around launches of one class when profiling is on
 struct ProfScope {
   gpx_ctx* ctx;
@@ -266,7 +319,16 @@ int gpx_prof_flush(gpx_ctx* ctx);
 
 // evaluation points per chunk of the posterior-shaped passes (gpx_posterior, gpx_acq): the N x chunk cross matrix under ~16 GiB,
 // or GPX_CROSS_BYTES
-extern "C" int64_t gpx_eval_chunk(int64_t np);
+extern "C" __attribute__((visibility("hidden"))) int64_t gpx_eval_chunk(int64_t np);
+// One chunk Zc (mc points) of those passes -- the ONE sequence behind gpx_posterior, gpx_ivar and gpx_acq, so that their values
+// agree by construction (api.hip):
+//   B = K(X, Zc) (np x mcp, row stride gpx_skew_ld(mcp));   mean_dev = B^T alpha_dev [-> mean_host, mc doubles];
+//   W = L^-1 B in place (Wout == NULL) or through the block inverses into Wout (B is consumed);   ssq = colsum(W^2);   kd = k(z, z)
+// alpha_dev == NULL: no mean.  ssq == NULL: the mean only.  mean_dev and ssq may be the same buffer (the copy is queued between
+// them).  Asynchronous.
+int gpx_posterior_chunk(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,
+                        double* B, double* Wout, const double* alpha_dev, double* mean_dev, double* mean_host, double* ssq,
+                        double* kd, double* part);
 
 // ---- kernel launchers (all asynchronous on ctx->stream) ------------------------------------------
 // kfill.hip
@@ -385,5 +447,5 @@ int launch_rowreduce(gpx_ctx* ctx, const double* B, int64_t ld, int64_t rows, in
 int launch_sum(gpx_ctx* ctx, const double* x, int64_t n, double* d_out);
 
 // design.hip
-extern "C" int gpx_potri_impl(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP, int full);
+extern "C" __attribute__((visibility("hidden"))) int gpx_potri_impl(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP, int full);
 int launch_transpose(gpx_ctx* ctx, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

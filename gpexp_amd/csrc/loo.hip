@@ -159,15 +159,6 @@ __global__ __launch_bounds__(256) void loo_ones_kernel(int64_t n, double* __rest
   if (i < n) v[i] = 1.0;
 }
 
-// a failed allocation keeps gpx_dev_alloc's own message ("hipMalloc(... bytes) failed: out of memory"), which the Python side
-// recognises; every other HIP failure is named here
-#define LOO_HIP(call)                                                                               \
-  if ((call) != hipSuccess) {                                                                       \
-    gpx_set_error("%s: HIP call failed: %s", who, hipGetErrorString(hipGetLastError()));            \
-    r = -2;                                                                                         \
-    break;                                                                                          \
-  }
-
 inline dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // dv (np doubles) <- alpha = K^-1 y: y zero padded, solved in place
@@ -184,57 +175,48 @@ int loo_alpha(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* dy, doubl
 extern "C" {
 
 int gpx_loo(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* mean, double* var, double* logp) {
-  static const char* who = "loo";
   GPX_ARG(ctx && L && y && logp, "NULL argument");
   GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   const int64_t n = L->rows, np = L->prows;
   GPX_ARG(n >= 1 && L->cols == n, "the factor must be square");
-  int r = 0;
+  Scratch sc(ctx);
+  double *pI, *ptmp, *pdy, *pal, *pps, *pp, *ppart, *pm, *pv, *plp;
+  GPX_TRY(sc.get(np * np * 8, &pI));
+  GPX_TRY(sc.get((np / 2 + 64) * (np / 2 + 64) * 8, &ptmp));
+  GPX_TRY(sc.get(np * 8, &pdy));
+  GPX_TRY(sc.get(np * 8, &pal));
+  GPX_TRY(sc.get(chol_potrs_scratch_bytes(np), &pps));
+  GPX_TRY(sc.get(np * 8, &pp));
+  GPX_TRY(sc.get(colreduce_partial_elems(n, np) * 8, &ppart));
+  GPX_TRY(sc.get(n * 8, &pm));
+  GPX_TRY(sc.get(n * 8, &pv));
+  GPX_TRY(sc.get(n * 8, &plp));
+  GPX_TRY(loo_alpha(ctx, L, y, pdy, pal, pps));
+  GPX_TRY(chol_trtri(ctx, L, pI, ptmp));  // L^-1, zero above the diagonal
+  // p_j = sum over the rows i < n of (L^-1)_ij^2 (rows >= n are the identity extension: see PADDING)
+  GPX_TRY(launch_colreduce(ctx, pI, np, n, np, nullptr, pp, ppart));
   {
-    Scratch sc(ctx);
-    void *pI, *ptmp, *pdy, *pal, *pps, *pp, *ppart, *pm, *pv, *plp;
-    do {
-      if ((r = sc.get(np * np * 8, &pI)) != 0) break;
-      if ((r = sc.get((np / 2 + 64) * (np / 2 + 64) * 8, &ptmp)) != 0) break;
-      if ((r = sc.get(np * 8, &pdy)) != 0) break;
-      if ((r = sc.get(np * 8, &pal)) != 0) break;
-      if ((r = sc.get(chol_potrs_scratch_bytes(np), &pps)) != 0) break;
-      if ((r = sc.get(np * 8, &pp)) != 0) break;
-      if ((r = sc.get(colreduce_partial_elems(n, np) * 8, &ppart)) != 0) break;
-      if ((r = sc.get(n * 8, &pm)) != 0) break;
-      if ((r = sc.get(n * 8, &pv)) != 0) break;
-      if ((r = sc.get(n * 8, &plp)) != 0) break;
-      if ((r = loo_alpha(ctx, L, y, (double*)pdy, (double*)pal, (double*)pps)) != 0) break;
-      if ((r = chol_trtri(ctx, L, (double*)pI, (double*)ptmp)) != 0) break;  // L^-1, zero above the diagonal
-      // p_j = sum over the rows i < n of (L^-1)_ij^2 (rows >= n are the identity extension: see PADDING)
-      if ((r = launch_colreduce(ctx, (const double*)pI, np, n, np, nullptr, (double*)pp, (double*)ppart)) != 0) break;
-      {
-        ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 48.0 * (double)n);
-        hipLaunchKernelGGL(loo_finish_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pdy, (const double*)pal,
-                           (const double*)pp, (int64_t)1, mean ? (double*)pm : nullptr, var ? (double*)pv : nullptr, (double*)plp);
-      }
-      LOO_HIP(hipGetLastError());
-      if ((r = launch_sum(ctx, (const double*)plp, n, ctx->d_scal)) != 0) break;
-      if (mean) LOO_HIP(hipMemcpyAsync(mean, pm, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-      if (var) LOO_HIP(hipMemcpyAsync(var, pv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-      LOO_HIP(hipMemcpyAsync(logp, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
-      LOO_HIP(hipStreamSynchronize(ctx->stream));
-    } while (0);
+    ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 48.0 * (double)n);
+    hipLaunchKernelGGL(loo_finish_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pdy, (const double*)pal,
+                       (const double*)pp, (int64_t)1, mean ? pm : nullptr, var ? pv : nullptr, plp);
   }
-  return r;
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, plp, n, ctx->d_scal));
+  if (mean) GPX_HIP(hipMemcpyAsync(mean, pm, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (var) GPX_HIP(hipMemcpyAsync(var, pv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(logp, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 int gpx_loo_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                  const double* nugget, int64_t nugget_len, const double* y, int64_t slab_rows, double* logp, double* grad) {
-  static const char* who = "loo_grad";
   GPX_ARG(ctx && L && X && y && logp && grad, "NULL argument");
-  GPX_ARG(L->factored && L->aux, "matrix has not been factored by gpx_potrf");
   GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
           "loo_grad: hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
           "gpx_loo itself takes every kernel");
   KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_ARG(X->cols == d && X->pcols == d && X->rows == L->rows, "X does not match the factor");
+  GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, nullptr, nullptr, "X does not match the factor", &kp));
   const int64_t n = L->rows, np = L->prows;
   GPX_ARG(n >= 1 && L->cols == n, "the factor must be square");
   GPX_ARG(nugget_len == 0 || nugget_len == 1 || nugget_len == n, "nugget_len must be 0, 1 or N");
@@ -245,120 +227,111 @@ int gpx_loo_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
   // a per-point nugget of length 1 is the scalar (n == 1)
   const bool per_point = nugget_len > 1;
   const double nscal = nugget_len == 1 ? nugget[0] : 0.0;
-  gpx_mat* P = nullptr;
-  GPX_TRY(gpx_potri_impl(ctx, L, &P, 1));  // both triangles: the rows of P are read whole
-  int r = 0;
+  MatHold P(ctx);
+  GPX_TRY(gpx_potri_impl(ctx, L, P.put(), 1));  // both triangles: the rows of P are read whole
+  Scratch sc(ctx);
+  double *pdy, *pal, *pps, *pone, *pD = nullptr, *pDal = nullptr, *pav, *pqv, *pterm, *plp, *out, *pdK = nullptr;
+  void* pW = nullptr;
+  GPX_TRY(sc.get(np * 8, &pdy));
+  GPX_TRY(sc.get(np * 8, &pal));
+  GPX_TRY(sc.get(chol_potrs_scratch_bytes(np), &pps));
+  GPX_TRY(sc.get(np * 8, &pone));
+  GPX_TRY(sc.get(np * 8, &pav));
+  GPX_TRY(sc.get(np * 8, &pqv));
+  GPX_TRY(sc.get(np * 8, &pterm));
+  GPX_TRY(sc.get(np * 8, &plp));
+  GPX_TRY(sc.get((nlen + 3) * 8, &out));  // [0, nlen): lengths, nlen: signalSize, nlen + 1: noise, nlen + 2: L_LOO
+  const double* al = pal;
+  GPX_TRY(loo_alpha(ctx, L, y, pdy, pal, pps));
+  // ---- value: p_i from the diagonal of P
   {
-    Scratch sc(ctx);
-    void *pdy, *pal, *pps, *pone, *pD = nullptr, *pDal = nullptr, *pav, *pqv, *pterm, *plp, *pout, *pdK = nullptr, *pW = nullptr;
-    do {
-      if ((r = sc.get(np * 8, &pdy)) != 0) break;
-      if ((r = sc.get(np * 8, &pal)) != 0) break;
-      if ((r = sc.get(chol_potrs_scratch_bytes(np), &pps)) != 0) break;
-      if ((r = sc.get(np * 8, &pone)) != 0) break;
-      if ((r = sc.get(np * 8, &pav)) != 0) break;
-      if ((r = sc.get(np * 8, &pqv)) != 0) break;
-      if ((r = sc.get(np * 8, &pterm)) != 0) break;
-      if ((r = sc.get(np * 8, &plp)) != 0) break;
-      if ((r = sc.get((nlen + 3) * 8, &pout)) != 0) break;
-      double* out = (double*)pout;  // [0, nlen): lengths, nlen: signalSize, nlen + 1: noise, nlen + 2: L_LOO
-      const double* al = (const double*)pal;
-      if ((r = loo_alpha(ctx, L, y, (double*)pdy, (double*)pal, (double*)pps)) != 0) break;
-      // ---- value: p_i from the diagonal of P
-      {
-        ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 32.0 * (double)n);
-        hipLaunchKernelGGL(loo_finish_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pdy, al, (const double*)P->p,
-                           P->ld + 1, (double*)nullptr, (double*)nullptr, (double*)plp);
-      }
-      LOO_HIP(hipGetLastError());
-      if ((r = launch_sum(ctx, (const double*)plp, n, out + nlen + 2)) != 0) break;
-      // ---- noise: a = P alpha, q_i = sum_l P_il^2 (weights: ones below n, zeros from n on)
-      LOO_HIP(hipMemsetAsync(pone, 0, (size_t)np * 8, ctx->stream));
-      hipLaunchKernelGGL(loo_ones_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (double*)pone);
-      LOO_HIP(hipGetLastError());
-      if ((r = launch_rowreduce(ctx, P->p, P->ld, n, np, al, (double*)pav, 0)) != 0) break;
-      if ((r = launch_rowreduce(ctx, P->p, P->ld, n, np, (const double*)pone, (double*)pqv, 1)) != 0) break;
-      hipLaunchKernelGGL(loo_rowterm_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, al, (const double*)P->p, P->ld,
-                         (const double*)pav, 0.0, 1.0, (const double*)pqv, 0.0, 1.0, (double*)pterm);
-      LOO_HIP(hipGetLastError());
-      if ((r = launch_sum(ctx, (const double*)pterm, n, out + nlen + 1)) != 0) break;
-      // ---- signalSize: P K0 = I - P D.  Scalar nugget: the noise sums scaled; per point: two more row reductions
-      if (per_point) {
-        if ((r = sc.get(np * 8, &pD)) != 0) break;
-        if ((r = sc.get(np * 8, &pDal)) != 0) break;
-        LOO_HIP(hipMemsetAsync(pD, 0, (size_t)np * 8, ctx->stream));
-        LOO_HIP(hipMemsetAsync(pDal, 0, (size_t)np * 8, ctx->stream));
-        LOO_HIP(hipMemcpyAsync(pD, nugget, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(loo_vecmul_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pD, al, (double*)pDal);
-        LOO_HIP(hipGetLastError());
-        if ((r = launch_rowreduce(ctx, P->p, P->ld, n, np, (const double*)pDal, (double*)pav, 0)) != 0) break;
-        if ((r = launch_rowreduce(ctx, P->p, P->ld, n, np, (const double*)pD, (double*)pqv, 1)) != 0) break;
-      }
-      {
-        const double c = per_point ? 1.0 : nscal;
-        hipLaunchKernelGGL(loo_rowterm_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, al, (const double*)P->p, P->ld,
-                           (const double*)pav, 1.0 / sig, -c / sig, (const double*)pqv, 1.0 / sig, -c / sig, (double*)pterm);
-      }
-      LOO_HIP(hipGetLastError());
-      if ((r = launch_sum(ctx, (const double*)pterm, n, out + nlen)) != 0) break;
-      // ---- lengths: dK, W = P dK in row slabs, fused row dots.  dK and W take the row stride np: their blocks then have the size
-      // of the two N x N work matrices gpx_potri_impl has just handed back to the pool
-      if ((r = sc.get(np * np * 8, &pdK)) != 0) break;
-      int64_t slab = slab_rows == 0 || slab_rows > np ? np : slab_rows;
-      if (slab_rows == 0) {
-        // auto: the whole matrix when it fits, otherwise the largest slab the free memory admits (after the pool has been given
-        // back: gpx_dev_alloc trims it before it gives up)
-        if (gpx_dev_alloc(ctx, slab * np * 8, &pW) != 0) {
-          pW = nullptr;
-          size_t fr = 0, tot = 0;
-          LOO_HIP(hipMemGetInfo(&fr, &tot));
-          slab = (int64_t)((double)fr * 0.9 / (8.0 * (double)np)) / GPX_TILE * GPX_TILE;
-          if (slab > np) slab = np;
-          while (slab >= GPX_TILE && gpx_dev_alloc(ctx, slab * np * 8, &pW) != 0) {
-            pW = nullptr;
-            slab = slab / 2 / GPX_TILE * GPX_TILE;
-          }
-          if (!pW) { r = -2; break; }  // gpx_dev_alloc's message stands
-        }
-        sc.adopt(pW, slab * np * 8);
-      } else if ((r = sc.get(slab * np * 8, &pW)) != 0) {
-        break;
-      }
-      for (int q = 0; q < nlen && r == 0; ++q) {
-        {
-          ProfScope ps(ctx, GPX_PROF_KFILL, 0.0, 8.0 * (double)np * np);
-          const size_t sh = (size_t)(2 * TS * d) * sizeof(double);
-          hipLaunchKernelGGL(loo_dkfill_kernel, dim3((unsigned)(np / TS), (unsigned)(np / TS)), dim3(256), sh, ctx->stream, kp,
-                             X->p, n, q, (double*)pdK, np);
-        }
-        LOO_HIP(hipGetLastError());
-        for (int64_t r0 = 0; r0 < n && r == 0; r0 += slab) {
-          const int64_t m = r0 + slab <= np ? slab : np - r0;          // rows of W in this slab (a multiple of 128)
-          const int64_t rows = r0 + m <= n ? m : n - r0;               // of them real points
-          if ((r = launch_gemm(ctx, P->p + r0 * P->ld, P->ld, (const double*)pdK, np, (double*)pW, np, m, np, np, false, false,
-                               false)) != 0)
-            break;
-          ProfScope ps(ctx, GPX_PROF_REDUCE, 4.0 * (double)rows * n, 16.0 * (double)rows * n);
-          hipLaunchKernelGGL(loo_rowdots_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)pW, np,
-                             (const double*)P->p, P->ld, r0, n, al, (double*)pterm);
-        }
-        if (r != 0) break;
-        LOO_HIP(hipGetLastError());
-        if ((r = launch_sum(ctx, (const double*)pterm, n, out + q)) != 0) break;
-      }
-      if (r != 0) break;
-      std::vector<double> h((size_t)nlen + 3);
-      LOO_HIP(hipMemcpyAsync(h.data(), pout, (size_t)(nlen + 3) * 8, hipMemcpyDeviceToHost, ctx->stream));
-      LOO_HIP(hipStreamSynchronize(ctx->stream));
-      // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho
-      for (int k = 0; k < nlen; ++k) grad[k] = h[(size_t)k] / hyp[k];
-      grad[nlen] = h[(size_t)nlen];
-      grad[nlen + 1] = h[(size_t)nlen + 1];
-      *logp = h[(size_t)nlen + 2];
-    } while (0);
+    ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 32.0 * (double)n);
+    hipLaunchKernelGGL(loo_finish_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pdy, al, (const double*)P->p,
+                       P->ld + 1, (double*)nullptr, (double*)nullptr, plp);
   }
-  gpx_mat_free(ctx, P);
-  return r;
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, plp, n, out + nlen + 2));
+  // ---- noise: a = P alpha, q_i = sum_l P_il^2 (weights: ones below n, zeros from n on)
+  GPX_HIP(hipMemsetAsync(pone, 0, (size_t)np * 8, ctx->stream));
+  hipLaunchKernelGGL(loo_ones_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, pone);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_rowreduce(ctx, P->p, P->ld, n, np, al, pav, 0));
+  GPX_TRY(launch_rowreduce(ctx, P->p, P->ld, n, np, pone, pqv, 1));
+  hipLaunchKernelGGL(loo_rowterm_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, al, (const double*)P->p, P->ld,
+                     (const double*)pav, 0.0, 1.0, (const double*)pqv, 0.0, 1.0, pterm);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, pterm, n, out + nlen + 1));
+  // ---- signalSize: P K0 = I - P D.  Scalar nugget: the noise sums scaled; per point: two more row reductions
+  if (per_point) {
+    GPX_TRY(sc.get(np * 8, &pD));
+    GPX_TRY(sc.get(np * 8, &pDal));
+    GPX_HIP(hipMemsetAsync(pD, 0, (size_t)np * 8, ctx->stream));
+    GPX_HIP(hipMemsetAsync(pDal, 0, (size_t)np * 8, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(pD, nugget, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(loo_vecmul_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, (const double*)pD, al, pDal);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_rowreduce(ctx, P->p, P->ld, n, np, pDal, pav, 0));
+    GPX_TRY(launch_rowreduce(ctx, P->p, P->ld, n, np, pD, pqv, 1));
+  }
+  {
+    const double c = per_point ? 1.0 : nscal;
+    hipLaunchKernelGGL(loo_rowterm_kernel, blocks256(n), dim3(256), 0, ctx->stream, n, al, (const double*)P->p, P->ld,
+                       (const double*)pav, 1.0 / sig, -c / sig, (const double*)pqv, 1.0 / sig, -c / sig, pterm);
+  }
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, pterm, n, out + nlen));
+  // ---- lengths: dK, W = P dK in row slabs, fused row dots.  dK and W take the row stride np: their blocks then have the size
+  // of the two N x N work matrices gpx_potri_impl has just handed back to the pool
+  GPX_TRY(sc.get(np * np * 8, &pdK));
+  int64_t slab = slab_rows == 0 || slab_rows > np ? np : slab_rows;
+  if (slab_rows == 0) {
+    // auto: the whole matrix when it fits, otherwise the largest slab the free memory admits (after the pool has been given
+    // back: gpx_dev_alloc trims it before it gives up).  Not GPX_TRY: a refused size is retried smaller, and when nothing fits
+    // gpx_dev_alloc's own out-of-memory text stands, which the Python side recognises
+    if (gpx_dev_alloc(ctx, slab * np * 8, &pW) != 0) {
+      pW = nullptr;
+      size_t fr = 0, tot = 0;
+      GPX_HIP(hipMemGetInfo(&fr, &tot));
+      slab = (int64_t)((double)fr * 0.9 / (8.0 * (double)np)) / GPX_TILE * GPX_TILE;
+      if (slab > np) slab = np;
+      while (slab >= GPX_TILE && gpx_dev_alloc(ctx, slab * np * 8, &pW) != 0) {
+        pW = nullptr;
+        slab = slab / 2 / GPX_TILE * GPX_TILE;
+      }
+      if (!pW) return -2;
+    }
+    sc.adopt(pW, slab * np * 8);
+  } else {
+    GPX_TRY(sc.get(slab * np * 8, &pW));
+  }
+  for (int q = 0; q < nlen; ++q) {
+    {
+      ProfScope ps(ctx, GPX_PROF_KFILL, 0.0, 8.0 * (double)np * np);
+      const size_t sh = (size_t)(2 * TS * d) * sizeof(double);
+      hipLaunchKernelGGL(loo_dkfill_kernel, dim3((unsigned)(np / TS), (unsigned)(np / TS)), dim3(256), sh, ctx->stream, kp,
+                         X->p, n, q, pdK, np);
+    }
+    GPX_HIP(hipGetLastError());
+    for (int64_t r0 = 0; r0 < n; r0 += slab) {
+      const int64_t m = r0 + slab <= np ? slab : np - r0;          // rows of W in this slab (a multiple of 128)
+      const int64_t rows = r0 + m <= n ? m : n - r0;               // of them real points
+      GPX_TRY(launch_gemm(ctx, P->p + r0 * P->ld, P->ld, pdK, np, (double*)pW, np, m, np, np, false, false, false));
+      ProfScope ps(ctx, GPX_PROF_REDUCE, 4.0 * (double)rows * n, 16.0 * (double)rows * n);
+      hipLaunchKernelGGL(loo_rowdots_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)pW, np,
+                         (const double*)P->p, P->ld, r0, n, al, pterm);
+    }
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_sum(ctx, pterm, n, out + q));
+  }
+  std::vector<double> h((size_t)nlen + 3);
+  GPX_HIP(hipMemcpyAsync(h.data(), out, (size_t)(nlen + 3) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho
+  for (int k = 0; k < nlen; ++k) grad[k] = h[(size_t)k] / hyp[k];
+  grad[nlen] = h[(size_t)nlen];
+  grad[nlen + 1] = h[(size_t)nlen + 1];
+  *logp = h[(size_t)nlen + 2];
+  return 0;
 }
 
 }  // extern "C"

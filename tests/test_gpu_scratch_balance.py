@@ -10,9 +10,28 @@ Shapes (d = 3): the smallest that reach each allocation branch --
     N = 2100            the out-of-place solve of gpx_posterior / gpx_acq (padded order >= 2048)
     N = 4100, M = 260   the block-inverse scratch of gpx_acq_grad's backward solve (padded order >= 4096)
 The factor's explicit block inverses are a cache inside the factor, built by the first solve against it: the model fixture's
-gpx_potrs builds them, so that the entries under test start from the steady state."""
+gpx_potrs builds them, so that the entries under test start from the steady state.
+
+FAILURE EXITS.  The same books must balance when an entry gives up half way.  Every case below is a call that answers with a
+non-zero status AFTER it has taken pooled memory: a nugget / noise of -2 on a kernel of signal variance 1.3 makes the first pivot
+the factorisation meets negative, which it REPORTS (a status, nothing is provoked on the device).  Asserted per case: GpxError,
+`outstanding_bytes` exactly where it was, and the same entry called validly right afterwards returns, byte for byte, what it
+returns in a process that never saw the failure (one child process computes those digests for all cases).
+    refit_rows  N = 300, keep = 128     the in-place strip solve, main stream only
+    refit_rows  N = 4500, keep = 4096   the copy of the kept rows on the side stream + the `wide` scratch scope (one more model)
+    mi_greedy, mi_begin                 260 candidates: gpx_potrf of K(C, C) - 2 I fails inside the call, S is handed back
+    fitc_fit    N = 300, 64 inducing    the first in-place factorisation fails with the model half built
+None of them is rejected by an argument check before the first allocation."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -185,3 +204,105 @@ ENTRIES = [
 def test_outstanding_bytes_return_to_their_value(name, make, n):
     ctx, call = make(n)
     balanced(ctx, call)
+
+
+# ---- failure exits ---------------------------------------------------------------------------------------------------------------
+BAD = -2.0   # as nugget / noise: the first pivot is 1.3 - 2 < 0 (or smaller still, behind a strip update)
+
+
+def _refit_rows(n, keep):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+
+    def call(nugget):
+        Lnew = dev.refit_rows(ctx, spec, X, nugget, L, keep)
+        out = Lnew.to_host(tri=1)
+        Lnew.free()
+        return [out]
+    return ctx, call
+
+
+def _mi_greedy_noise(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    return ctx, lambda noise: list(dev.mi_greedy(ctx, spec, Z, noise, 4))
+
+
+def _mi_begin(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+
+    def call(noise):
+        st = dev.MiState(ctx, spec, Z, noise, 4, 0, 0, M)
+        rowbuf = dev.alloc_vector(ctx, M)
+        st.row(0, rowbuf)
+        val, idx = st.score(0, rowbuf)
+        ctx.lib.gpx_mi_end(ctx.h, st.h)
+        st.h = None
+        rowbuf.free()
+        return [np.array([val]), np.array([idx])]
+    return ctx, call
+
+
+def _fitc_fit(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+
+    def call(noise):
+        S = dev.points(ctx, Xh[:64])
+        try:
+            f = dev.FitcModel(ctx, spec, X, S, noise)
+            coeff, quad = f.solve(y)
+            release(ctx, f)
+        finally:
+            S.free()
+        return [coeff, np.array([quad])]
+    return ctx, call
+
+
+FAILURES = [
+    ("refit_rows-N300-keep128", _refit_rows, (300, 128)), ("refit_rows-N4500-keep4096", _refit_rows, (4500, 4096)),
+    ("mi_greedy-M260", _mi_greedy_noise, (300,)), ("mi_begin-M260", _mi_begin, (300,)),
+    ("fitc_fit-N300-nu64", _fitc_fit, (300,)),
+]
+
+
+def digest(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def valid_digests():
+    """Every case's VALID call, in case order, in a process that runs nothing else."""
+    return {name: digest(make(*args)[1](NOISE)) for name, make, args in FAILURES}
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][0][7:])
+
+
+@pytest.mark.parametrize("name,make,args", FAILURES, ids=[f[0] for f in FAILURES])
+def test_failure_exit_returns_its_scratch_and_leaves_the_entry_usable(name, make, args, fresh):
+    from gpexp_amd._lib import GpxError
+    ctx, call = make(*args)
+    before = ctx.pool_stats()[1]
+    with pytest.raises(GpxError) as err:
+        call(BAD)
+    after = ctx.pool_stats()[1]
+    print("%s: %s\n    outstanding %d -> %d bytes" % (name, err.value, before, after))
+    assert after == before, "the failed call left %d bytes of pool keys outstanding" % (after - before)
+    got = digest(call(NOISE))
+    print("    valid call afterwards %s, fresh process %s" % (got[:16], fresh[name][:16]))
+    assert got == fresh[name]
+    assert ctx.pool_stats()[1] == before
+    assert ctx.guard_violations() <= 0   # 0 under GPX_ALLOC_GUARD=1, -1 with the guard off
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+    print("RESULT " + json.dumps(valid_digests()))
