@@ -12,7 +12,19 @@
 //     var(z)   = k(z,z) - sum_i Gi_i k_zi^2 + |La^-1 Kuf Gi k_z|^2           (one NT GEMM + one right TRSM per chunk)
 // Quu and K both carry the nugget, exactly as the reference builds them.  gpx_fitc_dense materialises Q + G and P for
 // the reference's `covarianceMatrix` / `precisionMatrix` attributes (small N only; parity tests).
-#include "gpx_internal.h"
+//
+// gpx_fitc_lml_grad: the hyper-parameter gradient of that likelihood (none in the reference: its own is unrunnable).  With
+// B = Quu^-1 Kuf, alpha = P y, M = alpha alpha^T - P (N x N, never formed), m = diag M, Y = La^-1 Ks:
+//     m_i = alpha_i^2 - Gi_i + |Y[:, i]|^2
+//     R   = B (M - diag m) = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(Gi + m)        (nu x N)
+//     T   = R B^T                                                                        (nu x nu, symmetric)
+//     dL/d theta = 1/2 [ 2 sum R o dKuf - sum T o dK(S,S) + sum_i m_i dk(x_i,x_i) ],   dL/d noise = 1/2 [ sum m - tr T ]
+// Two nu x nu x N solves (B through Lu, Y through La) and three nu x nu x N products (B Ks^T, its product with Y, R B^T) on the
+// fp64-MFMA GEMM; the sums against dKuf and dK(S,S) come from ONE tiled kernel (fitc_wsum_kernel) that recomputes the
+// derivative of every pair from the point coordinates and stores none of the d derivative matrices.  Working memory:
+// THREE nu x N buffers (B^T then the solve's input then R; B; Y) and TWO nu x nu ones (B Ks^T, T), plus vectors and the
+// per-tile partial sums.
+#include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
 #include <vector>
@@ -142,6 +154,156 @@ __global__ __launch_bounds__(256) void scale_cols_kernel(double* __restrict__ Bt
   *reinterpret_cast<double2*>(Bt + r * ld + c) = v;
 }
 
+// ---- hyper-parameter gradient ----------------------------------------------------------------------------------------------
+constexpr int TS = 64;
+
+// The weighted derivative sums over a RECTANGULAR pair of point sets: rows u < na are the points A, columns i < nb the points B,
+// Mw (row stride ld, storage of at least round_up(na, 64) x round_up(nb, 64)) the weights.  partial[tile][q]:
+//   q < nd:  sum Mw_ui K0_ui e_q(u, i)^2  (SE, nd = d; e_q = (a_q - b_q) / cl_q)   or   sum Mw_ui rho dk_ui/d rho  (Matern, nd = 1)
+//   q = nd:  sum Mw_ui K0_ui
+// K0 = the covariance without a nugget.  As lmlgrad_kernel (hyper.hip): a 64 x 64 tile per workgroup, raw coordinates of both sets
+// in LDS, differences first and then scaled, every thread 8 rows x 2 adjacent columns (one 16-byte load of Mw per row), the
+// tile's sums through lml_tile_term / lml_tile_store (gpx_device.h: wave shuffles and 4 LDS words per sum).  Rows >= na and columns >= nb are masked BY INDEX: what the padding of Mw holds is read
+// and dropped.  K0 is recomputed, for the squared exponential too, although Kuf holds it: one exp is ~30 fp64 operations beside
+// the ~6 d of the distance and the sums, a second operand would double the kernel's 8 bytes per pair, K(S,S) is not kept at
+// all (Lu overwrote it).  By operation count the two passes are a few per cent of the call's products; not timed on their own.
+__global__ __launch_bounds__(256) void fitc_wsum_kernel(KParams kp, const double* __restrict__ A, int64_t na,
+                                                        const double* __restrict__ B, int64_t nb,
+                                                        const double* __restrict__ Mw, int64_t ld,
+                                                        double* __restrict__ partial) {
+  extern __shared__ double sm[];
+  const int d = kp.d;
+  double* As = sm;               // [TS][d] raw coords of the row points
+  double* Bs = sm + TS * d;      // [TS][d] of the column points
+  double* red = Bs + TS * d;     // [4] per-wave partials
+  const int t = threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.y * TS, j0 = (int64_t)blockIdx.x * TS;
+  for (int idx = t; idx < TS * d; idx += 256) {
+    int p = idx / d, k = idx - p * d;
+    int64_t gi = i0 + p, gj = j0 + p;
+    As[idx] = gi < na ? A[gi * d + k] : 0.0;
+    Bs[idx] = gj < nb ? B[gj * d + k] : 0.0;
+  }
+  __syncthreads();
+  const int tx = t & 31, ty = t >> 5;
+  double tk[16];  // Mw_ui * K0_ui of this thread's 8 rows x 2 columns
+  double drho = 0.0;
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    const int r = ty + 8 * a;
+    const int64_t gi = i0 + r;
+    const double2 mv = *reinterpret_cast<const double2*>(Mw + gi * ld + j0 + 2 * tx);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int cc = 2 * tx + c;
+      const int64_t gj = j0 + cc;
+      double v = 0.0;
+      if (gi < na && gj < nb) {
+        double acc = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double e = (As[r * d + k] - Bs[cc * d + k]) * kp.scale[k];
+          acc = fma(e, e, acc);
+        }
+        const double w = c == 0 ? mv.x : mv.y;
+        double kv, dv;
+        lml_pair(kp, acc, &kv, &dv);
+        v = w * kv;
+        drho = fma(w, dv, drho);
+      }
+      tk[a * 2 + c] = v;
+    }
+  }
+  const int nd = lml_nd(kp.kind, d);
+  for (int q = 0; q <= nd; ++q)
+    lml_tile_store(lml_tile_term(kp, q, nd, As, Bs, tk, drho, tx, ty), red,
+                   partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 1) + q);
+}
+
+// m[i] = alpha_i^2 - ginv_i + ssq_i (= M_ii) and c[i] = alpha_i^2 + ssq_i (= ginv_i + m_i) for i < n; both 0 on the padding
+__global__ __launch_bounds__(256) void fitc_mdiag_kernel(const double* __restrict__ alpha, const double* __restrict__ ginv,
+                                                         const double* __restrict__ ssq, int64_t n, int64_t np,
+                                                         double* __restrict__ m, double* __restrict__ c) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  const double v = i < n ? fma(alpha[i], alpha[i], ssq[i]) : 0.0;
+  c[i] = v;
+  m[i] = i < n ? v - ginv[i] : 0.0;
+}
+
+// R[u][i] += ba[u] alpha[i] - B[u][i] c[i]  (rows = blockIdx.y, two columns per thread; `cols` even)
+__global__ __launch_bounds__(256) void fitc_r_kernel(double* __restrict__ R, int64_t ldr, const double* __restrict__ B, int64_t ldb,
+                                                     const double* __restrict__ ba, const double* __restrict__ alpha,
+                                                     const double* __restrict__ c, int64_t cols) {
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  const int64_t r = blockIdx.y;
+  if (j >= cols) return;
+  double2 v = *reinterpret_cast<double2*>(R + r * ldr + j);
+  const double2 b = *reinterpret_cast<const double2*>(B + r * ldb + j);
+  const double2 al = *reinterpret_cast<const double2*>(alpha + j);
+  const double2 cv = *reinterpret_cast<const double2*>(c + j);
+  const double bu = ba[r];
+  v.x += fma(bu, al.x, -b.x * cv.x);
+  v.y += fma(bu, al.y, -b.y * cv.y);
+  *reinterpret_cast<double2*>(R + r * ldr + j) = v;
+}
+
+// out[i] = A[i][i], i < n
+__global__ __launch_bounds__(256) void diag_kernel(const double* __restrict__ A, int64_t ld, int64_t n, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = A[i * (ld + 1)];
+}
+
+// the sums of fitc_wsum_kernel for the na x nb weights Mw into out[nd + 1] (device); ppart: (tiles of Mw) x (nd + 1) doubles
+int fitc_wsums(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat* B, const double* Mw, int64_t ld, double* ppart,
+               double* out) {
+  const int64_t na = A->rows, nb = B->rows, tr = gpx_round_up(na, TS) / TS, tc = gpx_round_up(nb, TS) / TS;
+  const int nq = lml_nd(kp.kind, kp.d) + 1;
+  ProfScope ps(ctx, GPX_PROF_REDUCE, 0.0, 8.0 * (double)na * nb);
+  const size_t sh = (size_t)(2 * TS * kp.d + 4) * sizeof(double);
+  hipLaunchKernelGGL(fitc_wsum_kernel, dim3((unsigned)tc, (unsigned)tr), dim3(256), sh, ctx->stream, kp, A->p, na, B->p, nb, Mw, ld,
+                     ppart);
+  GPX_HIP(hipGetLastError());
+  return launch_tile_sums(ctx, ppart, tr * tc, nq, out);
+}
+
+// dt (np doubles, device) <- alpha = P y:  u = Kuf Gi y = -(Ks y);  w = A^-1 u;  t = Kfu w;  alpha = Gi (y - t), 0 on the padding.
+// dy (np): y, zero padded.  du (nup), part (colreduce partials for nup x np), ps (chol_potrs_scratch_bytes(nup)): scratch.
+int fitc_alpha(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* dy, double* du, double* dt, double* part, double* ps) {
+  GPX_HIP(hipMemsetAsync(dy, 0, (size_t)f->np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(dy, y, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipMemsetAsync(du, 0, (size_t)f->nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, f->Ks->p, f->Ks->ld, f->nu, f->np, dy, du));
+  hipLaunchKernelGGL(negate_kernel, dim3((unsigned)((f->nup + 255) / 256)), dim3(256), 0, ctx->stream, du, f->nup);
+  // both sweeps against chol(A) through its explicit 1024-order block inverses (cached in La by the first solve): the
+  // leaf-level sweeps stream every 512-row diagonal block through one workgroup (0.80 ms of the 1.4 ms at nu = 4096)
+  GPX_TRY(chol_potrs(ctx, f->La, du, ps));
+  GPX_TRY(launch_colreduce(ctx, f->Kuf->p, f->Kuf->ld, f->nu, f->np, du, dt, part));
+  hipLaunchKernelGGL(fitc_coeff_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, f->ginv, dy, dt,
+                     f->np);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+// log det(Q + G) = sum log g + log det A - log det Quu.  Blocking.
+int fitc_logdet(gpx_ctx* ctx, const gpx_fitc* f, double* out) {
+  double la = 0.0, lu = 0.0;
+  GPX_TRY(launch_logdet(ctx, f->La->p, f->La->ld, f->nu, ctx->d_scal));
+  GPX_HIP(hipMemcpyAsync(&la, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  GPX_TRY(launch_logdet(ctx, f->Lu->p, f->Lu->ld, f->nu, ctx->d_scal));
+  GPX_HIP(hipMemcpyAsync(&lu, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  *out = f->sumlogg + la - lu;
+  return 0;
+}
+
+// y^T alpha, summed on the host in index order
+double fitc_quad(const double* y, const double* coeff, int64_t n) {
+  double s = 0.0;
+  for (int64_t i = 0; i < n; ++i) s += y[i] * coeff[i];
+  return s;
+}
+
 }  // namespace
 
 int64_t fitc_n(const gpx_fitc* f) { return f->n; }
@@ -263,47 +425,118 @@ int gpx_fitc_shape(const gpx_fitc* f, int64_t* n, int64_t* nu) {
 int gpx_fitc_solve(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* coeff, double* quad) {
   GPX_ARG(ctx && f && y && coeff, "NULL argument");
   Scratch tmp(ctx);
-  double *dy, *du, *dt, *part;
+  double *dy, *du, *dt, *part, *ps;
   GPX_TRY(tmp.get(f->np * 8, &dy));
   GPX_TRY(tmp.get(f->nup * 8, &du));
   GPX_TRY(tmp.get(f->np * 8, &dt));
   GPX_TRY(tmp.get(colreduce_partial_elems(f->nup, f->np) * 8 + 8, &part));
-  GPX_HIP(hipMemsetAsync(dy, 0, (size_t)f->np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(dy, y, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  GPX_HIP(hipMemsetAsync(du, 0, (size_t)f->nup * 8, ctx->stream));
-  // u = Kuf Gi y = -(Ks y);  w = A^-1 u;  t = Kfu w;  coeff = Gi (y - t)
-  GPX_TRY(launch_rowreduce(ctx, f->Ks->p, f->Ks->ld, f->nu, f->np, dy, du));
-  hipLaunchKernelGGL(negate_kernel, dim3((unsigned)((f->nup + 255) / 256)), dim3(256), 0, ctx->stream, du, f->nup);
-  // both sweeps against chol(A) through its explicit 1024-order block inverses (cached in La by the first solve): the
-  // leaf-level sweeps stream every 512-row diagonal block through one workgroup (0.80 ms of the 1.4 ms at nu = 4096)
-  double* ps;
   GPX_TRY(tmp.get(chol_potrs_scratch_bytes(f->nup), &ps));
-  GPX_TRY(chol_potrs(ctx, f->La, du, ps));
-  GPX_TRY(launch_colreduce(ctx, f->Kuf->p, f->Kuf->ld, f->nu, f->np, du, dt, part));
-  hipLaunchKernelGGL(fitc_coeff_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, f->ginv, dy, dt,
-                     f->np);
-  GPX_HIP(hipGetLastError());
+  GPX_TRY(fitc_alpha(ctx, f, y, dy, du, dt, part, ps));
   GPX_HIP(hipMemcpyAsync(coeff, dt, (size_t)f->n * 8, hipMemcpyDeviceToHost, ctx->stream));
   GPX_HIP(hipStreamSynchronize(ctx->stream));
-  if (quad) {
-    double s = 0.0;
-    for (int64_t i = 0; i < f->n; ++i) s += y[i] * coeff[i];
-    *quad = s;
-  }
+  if (quad) *quad = fitc_quad(y, coeff, f->n);
   return 0;
 }
 
 // log det(Q + G) = sum log g + log det A - log det Quu
 int gpx_fitc_logdet(gpx_ctx* ctx, const gpx_fitc* f, double* out) {
   GPX_ARG(ctx && f && out, "NULL argument");
-  double la = 0.0, lu = 0.0;
-  GPX_TRY(launch_logdet(ctx, f->La->p, f->La->ld, f->nu, ctx->d_scal));
-  GPX_HIP(hipMemcpyAsync(&la, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
-  GPX_HIP(hipStreamSynchronize(ctx->stream));
-  GPX_TRY(launch_logdet(ctx, f->Lu->p, f->Lu->ld, f->nu, ctx->d_scal));
-  GPX_HIP(hipMemcpyAsync(&lu, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
-  GPX_HIP(hipStreamSynchronize(ctx->stream));
-  *out = f->sumlogg + la - lu;
+  return fitc_logdet(ctx, f, out);
+}
+
+// *logp (nullable) = the log marginal likelihood of y, grad[nlen + 2] = its derivatives [lengths..., signalSize, noise variance]
+// (header comment: the formula, the products and the buffers)
+int gpx_fitc_lml_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                      const gpx_mat* S, const double* y, double* logp, double* grad) {
+  GPX_ARG(ctx && f && X && S && y && grad, "NULL argument");
+  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
+          "fitc_lml_grad: hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
+          "the Mehler kernel has none");
+  KParams kp;
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
+  bool same = kind == f->kp.kind && d == f->kp.d && kp.sig == f->kp.sig;
+  for (int k = 0; same && k < d; ++k) same = kp.scale[k] == f->kp.scale[k];
+  GPX_ARG(same, "fitc_lml_grad: (kind, d, hyp) is not the kernel the model was fitted with");
+  GPX_ARG(X->cols == d && X->pcols == d && X->rows == f->n && S->cols == d && S->pcols == d && S->rows == f->nu,
+          "fitc_lml_grad: X and S must be the unpadded (n x d) nodes and (nu x d) inducing points of the model");
+  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int64_t ldk = f->Ks->ld, ldt = gpx_skew_ld(nup);
+  GPX_ARG(f->W->ld == ldk && f->Kuf->ld == ldk, "fitc_lml_grad: the model's nu x N matrices differ in row stride");
+  const int nd = lml_nd(kind, d), nq = nd + 1;
+  Scratch tmp(ctx);
+  double *dy, *du, *al, *part, *ps, *ssq, *mv, *cv, *ba, *dg, *b1, *Bm, *Y, *C1, *T, *ppart, *out;
+  const int64_t big = np * ldt > nup * ldk ? np * ldt : nup * ldk;
+  const int64_t tiles = (nup / TS) * ((np > nup ? np : nup) / TS);   // of R (nup x np) or of T (nup x nup), whichever has more
+  GPX_TRY(tmp.get(np * 8, &dy));
+  GPX_TRY(tmp.get(nup * 8, &du));
+  GPX_TRY(tmp.get(np * 8, &al));
+  GPX_TRY(tmp.get(colreduce_partial_elems(nup, np) * 8 + 8, &part));
+  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
+  GPX_TRY(tmp.get(np * 8, &ssq));
+  GPX_TRY(tmp.get(np * 8, &mv));
+  GPX_TRY(tmp.get(np * 8, &cv));
+  GPX_TRY(tmp.get(nup * 8, &ba));
+  GPX_TRY(tmp.get(nup * 8, &dg));
+  GPX_TRY(tmp.get(big * 8, &b1));
+  GPX_TRY(tmp.get(nup * ldk * 8, &Bm));
+  GPX_TRY(tmp.get(nup * ldk * 8, &Y));
+  GPX_TRY(tmp.get(nup * ldt * 8, &C1));
+  GPX_TRY(tmp.get(nup * ldt * 8, &T));
+  GPX_TRY(tmp.get(tiles * nq * 8, &ppart));
+  GPX_TRY(tmp.get((2 * nq + 2) * 8, &out));   // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T
+  GPX_TRY(fitc_alpha(ctx, f, y, dy, du, al, part, ps));
+  // B = Quu^-1 Kuf = Lu^-T W through its transpose: B^T = W^T Lu^-1
+  GPX_TRY(launch_transpose(ctx, f->W->p, nup, np, ldk, b1, ldt));
+  GPX_TRY(chol_trsm_right_n(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, b1, ldt, np, nup));
+  GPX_TRY(launch_transpose(ctx, b1, np, nup, ldt, Bm, ldk));
+  // Y = La^-1 Ks through La's block inverses (the solve consumes its right-hand side: a copy);  m, c = Gi + m
+  GPX_TRY(gpx_copy2d(ctx, f->Ks->p, ldk, b1, ldk, nup, np));
+  GPX_TRY(chol_trsm_left_oop(ctx, f->La, b1, ldk, Y, ldk, np));
+  GPX_TRY(launch_colreduce(ctx, Y, ldk, nu, np, nullptr, ssq, part));
+  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
+                     (const double*)f->ginv, (const double*)ssq, n, np, mv, cv);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, mv, n, out + 2 * nq));
+  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(c), over the consumed copy
+  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
+  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
+  GPX_TRY(launch_gemm(ctx, C1, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, 4.0 * (double)nup * np, 24.0 * (double)nup * np);
+    hipLaunchKernelGGL(fitc_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
+                       (const double*)Bm, ldk, (const double*)ba, (const double*)al, (const double*)cv, np);
+  }
+  GPX_HIP(hipGetLastError());
+  // T = R B^T;  the sums against dKuf (weights R) and dK(S,S) (weights T: the same kernel with both point sets = S -- T is
+  // nu x nu, so the symmetric half that lml_trace would save is nothing, and one kernel serves both);  tr T
+  GPX_TRY(launch_gemm(ctx, b1, ldk, Bm, ldk, T, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, ppart, out));
+  GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, ppart, out + nq));
+  hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, dg);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, dg, nu, out + 2 * nq + 1));
+  // (the copies land in locals: the stream is drained before any error return, so none is pending when they go away)
+  std::vector<double> h((size_t)(2 * nq + 2)), hal(logp ? (size_t)n : 0);
+  const hipError_t eh = hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t ea = logp ? hipMemcpyAsync(hal.data(), al, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  GPX_HIP(eh);
+  GPX_HIP(ea);
+  GPX_HIP(es);
+  const double* hr = h.data();
+  const double* ht = h.data() + nq;
+  const double msum = h[(size_t)2 * nq], trT = h[(size_t)2 * nq + 1];
+  // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho;  dK/d signalSize = K0 / s and dk(x,x)/d signalSize = 1
+  for (int k = 0; k < nd; ++k) grad[k] = 0.5 * (2.0 * hr[k] - ht[k]) / hyp[k];
+  grad[nd] = 0.5 * ((2.0 * hr[nd] - ht[nd]) / hyp[nd] + msum);
+  grad[nd + 1] = 0.5 * (msum - trT);
+  if (logp) {
+    double logdet;
+    GPX_TRY(fitc_logdet(ctx, f, &logdet));
+    *logp = -0.5 * fitc_quad(y, hal.data(), n) - 0.5 * logdet - 0.5 * (double)n * 1.8378770664093454836;  // log 2 pi
+  }
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// Per-pair and per-workgroup device helpers shared by the element-wise kernels of design.hip, hyper.hip, grad.hip and acq.hip
-// (gfx950).  __device__ __forceinline__ functions and templates only -- no kernels, no host code.  The tiled fills (kfill.hip)
+// Per-pair and per-workgroup device helpers shared by the element-wise kernels of design.hip, hyper.hip, grad.hip, acq.hip and
+// fitc.hip (gfx950).  __device__ __forceinline__ functions and templates only -- no kernels, no host code.  The tiled fills (kfill.hip)
 // and the reductions of reduce.hip / chol.hip have their own forms and do not come through here.
 #pragma once
 #include "gpx_internal.h"
@@ -38,6 +38,66 @@ static __device__ __forceinline__ double kpair(const KParams& kp, const double* 
   const double t = sqrt(acc);
   if (kp.kind == GPX_K_MATERN32) return kp.sig * (1.0 + t) * exp(-t);
   return kp.sig * (1.0 + t + acc * (1.0 / 3.0)) * exp(-t);
+}
+
+// ---- hyper-parameter derivative of one pair (the trace kernels of hyper.hip and the FITC gradient of fitc.hip) ---------------
+// One pair of points under a stationary kernel with hyper-parameter derivatives: acc = the scaled squared distance (SE: sum_k
+// e_k^2; Matern: t^2 with t = sqrt(nu') r / rho).  kv = k(a, b) without the nugget; dv = rho dk/d rho for the isotropic Materns
+// (round 6; the reference's own Matern raises, kernels.py:93-97):
+//   nu = 3/2: k = s (1 + t) e^-t,           dk/dt = -s t e^-t            rho dk/d rho = -t dk/dt = s t^2 e^-t
+//   nu = 5/2: k = s (1 + t + t^2/3) e^-t,   dk/dt = -s t (1 + t) e^-t / 3                     = s t^2 (1 + t) e^-t / 3
+static __device__ __forceinline__ void lml_pair(const KParams& kp, double acc, double* kv, double* dv) {
+  if (kp.kind == GPX_K_SE) {
+    *kv = kp.sig * exp(-0.5 * acc);
+    *dv = 0.0;
+    return;
+  }
+  const double t = sqrt(acc), e = kp.sig * exp(-t);
+  if (kp.kind == GPX_K_MATERN32) {
+    *kv = (1.0 + t) * e;
+    *dv = acc * e;
+  } else {
+    *kv = (1.0 + t + acc * (1.0 / 3.0)) * e;
+    *dv = acc * (1.0 + t) * e * (1.0 / 3.0);
+  }
+}
+// number of length-type hyper-parameters in the trace sums: d correlation lengths (SE) or the one rho (Matern)
+static __host__ __device__ __forceinline__ int lml_nd(int kind, int d) { return kind == GPX_K_SE ? d : 1; }
+
+// The end of a 64 x 64 trace tile of 256 threads (lmlgrad_kernel, lmlgrad_slab_kernel, fitc_wsum_kernel), thread (tx, ty) =
+// (t & 31, t >> 5) holding the rows ty + 8 a and the columns 2 tx + c: tk[2 a + c] = weight * K0 of its 16 pairs, drho = its sum of
+// weight * rho dk/d rho, As / Bs = the raw coordinates of the tile's row / column points ([64][d] each).
+// lml_tile_term: this thread's part of sum q -- q < nd: weight K0 e_q^2 (SE) or drho (Matern); q == nd: weight K0.
+static __device__ __forceinline__ double lml_tile_term(const KParams& kp, int q, int nd, const double* As, const double* Bs,
+                                                       const double (&tk)[16], double drho, int tx, int ty) {
+  const int d = kp.d;
+  double s = 0.0;
+  if (q < nd && kp.kind != GPX_K_SE) {
+    s = drho;
+  } else if (q < nd) {
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+      const int r = ty + 8 * a;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const double e = (As[r * d + q] - Bs[(2 * tx + c) * d + q]) * kp.scale[q];
+        s = fma(tk[a * 2 + c], e * e, s);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < 16; ++a) s += tk[a];
+  }
+  return s;
+}
+// lml_tile_store: *dst = the sum of s over the workgroup -- wave shuffles, then the 4 LDS words red[], in a fixed order.
+static __device__ __forceinline__ void lml_tile_store(double s, double* red, double* dst) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  __syncthreads();
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (t == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ---- radial pair: the kernels whose point derivative is a radial factor times the coordinate difference -------------------

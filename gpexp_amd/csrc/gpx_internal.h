@@ -446,6 +446,9 @@ int launch_rowreduce(gpx_ctx* ctx, const double* B, int64_t ld, int64_t rows, in
                      double* out, int weighted_squares = 0);
 int launch_sum(gpx_ctx* ctx, const double* x, int64_t n, double* d_out);
 
+// hyper.hip: out[q] = sum over the tiles of partial[tile][q], q < nq, in a fixed order (the final pass of the tiled traces)
+int launch_tile_sums(gpx_ctx* ctx, const double* partial, int64_t nblocks, int nq, double* out);
+
 // design.hip
 extern "C" __attribute__((visibility("hidden"))) int gpx_potri_impl(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP, int full);
 int launch_transpose(gpx_ctx* ctx, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

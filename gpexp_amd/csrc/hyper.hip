@@ -18,29 +18,7 @@ namespace {
 constexpr int TS = 64;
 
 // ---- lml_grad ------------------------------------------------------------------------------------------
-// One pair of points under a stationary kernel with hyper-parameter derivatives: acc = the scaled squared distance (SE: sum_k
-// e_k^2; Matern: t^2 with t = sqrt(nu') r / rho).  kv = k(a, b) without the nugget; dv = rho dk/d rho for the isotropic Materns
-// (round 6; the reference's own Matern raises, kernels.py:93-97):
-//   nu = 3/2: k = s (1 + t) e^-t,           dk/dt = -s t e^-t            rho dk/d rho = -t dk/dt = s t^2 e^-t
-//   nu = 5/2: k = s (1 + t + t^2/3) e^-t,   dk/dt = -s t (1 + t) e^-t / 3                     = s t^2 (1 + t) e^-t / 3
-__device__ __forceinline__ void lml_pair(const KParams& kp, double acc, double* kv, double* dv) {
-  if (kp.kind == GPX_K_SE) {
-    *kv = kp.sig * exp(-0.5 * acc);
-    *dv = 0.0;
-    return;
-  }
-  const double t = sqrt(acc), e = kp.sig * exp(-t);
-  if (kp.kind == GPX_K_MATERN32) {
-    *kv = (1.0 + t) * e;
-    *dv = acc * e;
-  } else {
-    *kv = (1.0 + t + acc * (1.0 / 3.0)) * e;
-    *dv = acc * (1.0 + t) * e * (1.0 / 3.0);
-  }
-}
-// number of length-type hyper-parameters in the trace sums: d correlation lengths (SE) or the one rho (Matern)
-__host__ __device__ __forceinline__ int lml_nd(int kind, int d) { return kind == GPX_K_SE ? d : 1; }
-
+// (the per-pair value lml_pair and the count lml_nd of length-type parameters: gpx_device.h)
 // partial[block][q], q = 0..nd-1: sum T_ij K0_ij e_k^2 (SE: scaled differences, nd = d) or sum T_ij rho dK_ij/d rho (Matern, nd = 1),
 // q = nd: sum T_ij K0_ij, q = nd+1: sum_i T_ii
 __global__ __launch_bounds__(256) void lmlgrad_kernel(KParams kp, const double* __restrict__ X, int64_t n,
@@ -94,35 +72,10 @@ __global__ __launch_bounds__(256) void lmlgrad_kernel(KParams kp, const double* 
       tk[a * 2 + c] = v;
     }
   }
-  const int lane = t & 63, wave = t >> 6;
   const int nd = lml_nd(kp.kind, d);
-  for (int q = 0; q <= nd + 1; ++q) {
-    double s = 0.0;
-    if (q < nd && kp.kind != GPX_K_SE) {
-      s = drho;
-    } else if (q < nd) {
-#pragma unroll
-      for (int a = 0; a < 8; ++a) {
-        const int r = ty + 8 * a;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const double e = (As[r * d + q] - Bs[(2 * tx + c) * d + q]) * kp.scale[q];
-          s = fma(tk[a * 2 + c], e * e, s);
-        }
-      }
-    } else if (q == nd) {
-#pragma unroll
-      for (int a = 0; a < 16; ++a) s += tk[a];
-    } else {
-      s = diag;
-    }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (t == 0)
-      partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 2) + q] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
+  for (int q = 0; q <= nd + 1; ++q)
+    lml_tile_store(q <= nd ? lml_tile_term(kp, q, nd, As, Bs, tk, drho, tx, ty) : diag, red,
+                   partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 2) + q);
 }
 
 __global__ __launch_bounds__(256) void lmlgrad_final_kernel(const double* __restrict__ partial, int64_t nblocks,
@@ -188,35 +141,10 @@ __global__ __launch_bounds__(256) void lmlgrad_slab_kernel(KParams kp, const dou
       tk[a * 2 + c] = v;
     }
   }
-  const int lane = t & 63, wave = t >> 6;
   const int nd = lml_nd(kp.kind, d);
-  for (int q = 0; q <= nd + 1; ++q) {
-    double s = 0.0;
-    if (q < nd && kp.kind != GPX_K_SE) {
-      s = drho;
-    } else if (q < nd) {
-#pragma unroll
-      for (int a = 0; a < 8; ++a) {
-        const int r = ty + 8 * a;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const double e = (As[r * d + q] - Bs[(2 * tx + c) * d + q]) * kp.scale[q];
-          s = fma(tk[a * 2 + c], e * e, s);
-        }
-      }
-    } else if (q == nd) {
-#pragma unroll
-      for (int a = 0; a < 16; ++a) s += tk[a];
-    } else {
-      s = diag;
-    }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (t == 0)
-      partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 2) + q] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
+  for (int q = 0; q <= nd + 1; ++q)
+    lml_tile_store(q <= nd ? lml_tile_term(kp, q, nd, As, Bs, tk, drho, tx, ty) : diag, red,
+                   partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 2) + q);
 }
 
 // Z (s x n2, row stride ldz) = [ I_s 0 ]
@@ -352,6 +280,14 @@ int mi_inverse(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const
 }
 
 }  // namespace
+
+// out[q] = the sum over the nblocks tiles of partial[tile][q], q < nq, in lmlgrad_final_kernel's fixed order: the second pass of
+// a tiled trace for the callers outside this file (fitc.hip).  Asynchronous.
+int launch_tile_sums(gpx_ctx* ctx, const double* partial, int64_t nblocks, int nq, double* out) {
+  hipLaunchKernelGGL(lmlgrad_final_kernel, dim3(nq), dim3(256), 0, ctx->stream, partial, nblocks, nq, out);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
 
 extern "C" {
 

@@ -288,7 +288,7 @@ class FitcModel:
     """Device-resident FITC model (gpx_fitc_*): chol(Quu), Kuf, G and chol(Quu + Kuf G^-1 Kfu)."""
 
     def __init__(self, ctx, spec, X, S, noise):
-        self.ctx, self.X = ctx, X
+        self.ctx, self.X, self.S = ctx, X, S
         h = c_vp()
         check(ctx.lib.gpx_fitc_fit(ctx.h, *spec.args(), X.h, S.h, float(noise), C.byref(h)))
         self.h = h
@@ -305,6 +305,18 @@ class FitcModel:
         out = C.c_double()
         check(self.ctx.lib.gpx_fitc_logdet(self.ctx.h, self.h, C.byref(out)))
         return out.value
+
+    def lml_grad(self, spec, y, want_value=True):
+        """(log marginal likelihood of y, its TRUE derivatives [lengths..., signalSize, noise variance]) (gpx_fitc_lml_grad) for
+        `spec` = the kernel the model was fitted with.  want_value=False: (None, derivatives) -- the call then skips the two
+        log-determinants and the copy of alpha that only the value needs."""
+        y = as_f64(y)
+        assert y.shape == (self.n,)
+        out = np.empty(spec.nsums)
+        lp = C.c_double()
+        check(self.ctx.lib.gpx_fitc_lml_grad(self.ctx.h, self.h, *spec.args(), self.X.h, self.S.h, dptr(y),
+                                             C.byref(lp) if want_value else None, dptr(out)))
+        return (lp.value if want_value else None), out
 
     def posterior(self, coeff, Z, want_mean=True, want_var=True):
         m = Z.shape[0]

@@ -431,12 +431,21 @@ class GP:
         passes an unknown keyword and raises TypeError (gp.py:429-430)."""
         evals = np.asarray(evals, dtype=float)
         if self.FITC is not None and noiseIn is None:
-            if returnDeriv == 1:
-                raise NotImplementedError("no hyper-parameter gradient for the FITC likelihood (the reference's own is "
-                                          "unrunnable, kernels.py:140-141)")
+            spec = self.kernel._spec()
+            if returnDeriv == 1 and spec.kind == _dev.K_MEHLER:
+                raise NotImplementedError("no hyper-parameter gradient of the FITC likelihood for %s (squared exponential "
+                                          "and isotropic Matern kernels only)" % type(self.kernel).__name__)
             _, model = self._fitc_model(pts)
             quad = model.solve(evals)[1]
-            return -0.5 * quad - 0.5 * model.logdet() - len(evals) / 2.0 * np.log(2.0 * np.pi)
+            out = -0.5 * quad - 0.5 * model.logdet() - len(evals) / 2.0 * np.log(2.0 * np.pi)
+            if returnDeriv == 1:
+                # gpx_fitc_lml_grad: a few nu x nu x N products on the fitted model, no N x N matrix; its entries are true
+                # derivatives, 'noise' w.r.t. the noise variance -- scaled as in the dense branch below (gp.py:463-464)
+                keys = list(self.kernel.hyperParam.keys()) + ['noise']
+                outD = dict(zip(keys, model.lml_grad(spec, evals, want_value=False)[1]))   # the value: `out`, as without the gradient
+                outD['noise'] *= self.noise * 2.0
+                return out, outD
+            return out
         nugget = self.noise if noiseIn is None else noiseIn
         X, L, _ = self._factor(pts, nugget, remember=False)
         ctx = _dev.context()
@@ -529,9 +538,10 @@ class GP:
         `analyticGradient=True` L-BFGS-B gets its gradient from gpx_loo_grad, whose 'noise' entry already is the derivative
         w.r.t. the noise variance.  Any other string raises ValueError.
 
-        `analyticGradient=True` (opt-in; squared-exponential kernel) hands L-BFGS-B the gradient from
-        gpx_lml_grad instead of letting it difference the objective (gp.py:635, approx_grad=True): one factorisation per
-        iterate instead of nparams+1.  The default reproduces the reference's numerical-gradient search."""
+        `analyticGradient=True` (opt-in; squared-exponential and isotropic Matern kernels) hands L-BFGS-B the
+        gradient from gpx_lml_grad -- on a FITC model from gpx_fitc_lml_grad -- instead of letting it difference the objective
+        (gp.py:635, approx_grad=True): one factorisation (one FITC fit) per iterate instead of nparams+1.  The default
+        reproduces the reference's numerical-gradient search."""
         if objective not in ("lml", "loo"):
             raise ValueError("findOptParamsLogLike: objective must be 'lml' or 'loo', not %r" % (objective,))
         if paramsStart is None:

@@ -326,6 +326,20 @@ int gpx_fitc_shape(const gpx_fitc* f, int64_t* n, int64_t* nu);
 int gpx_fitc_solve(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* coeff, double* quad);
 /* log det(Q + G) (loglikeParams, gp.py:434) */
 int gpx_fitc_logdet(gpx_ctx* ctx, const gpx_fitc* f, double* out);
+/* *logp = the FITC log marginal likelihood of y (as gpx_fitc_solve + gpx_fitc_logdet give it: -1/2 y^T P y - 1/2 log det(Q + G)
+ * - N/2 log 2 pi; nullable) and grad[nlen + 2] = its derivatives in gpx_lml_grad's order [lengths..., signalSize, noise]; the
+ * reference has no runnable counterpart.  Kernel entries are TRUE derivatives and the noise entry is the derivative w.r.t. the
+ * noise VARIANCE (no factor 2 * noise), the convention of gpx_loo_grad.  (kind, d, hyp) = the kernel the model was fitted with,
+ * X and S its nodes and inducing points (anything else is an argument error); squared exponential and isotropic Matern only, as
+ * gpx_lml_grad (Mehler is an argument error).  y: host, N.  The model is not modified.  The 1e-12 guard that the model adds to g
+ * before inverting it is IGNORED by the derivative (Gi is taken as 1 / g; the value's sum log g has no guard either).
+ * With B = Quu^-1 Kuf, alpha = P y, M = alpha alpha^T - P (never formed), m = diag M:  R = B (M - diag m),  T = R B^T,
+ *     dL/d theta = 1/2 [ 2 sum R o dKuf - sum T o dK(S,S) + sum_i m_i dk(x_i,x_i) ],    dL/d noise = 1/2 [ sum m - tr T ].
+ * Two nu x nu x N triangular solves and three nu x nu x N products: ~8 nu^2 N flops (the fit: ~4 nu^2 N), plus one tiled pass
+ * that recomputes the kernel derivatives from the coordinates (no derivative matrix is stored).  Memory: three nu x N and two
+ * nu x nu work matrices; nothing N x N.  All reductions run in a fixed order: two calls agree bit for bit. */
+int gpx_fitc_lml_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                      const gpx_mat* S, const double* y, double* logp, double* grad);
 /* GP.evaluate / evaluateVariance with the FITC precision (gp.py:132-145, 246-255): mean (nullable; needs coeff) and the
  * SIGNED variance (nullable) at the M points of Z */
 int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const double* coeff, const gpx_mat* Z,

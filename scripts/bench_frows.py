@@ -181,6 +181,13 @@ if want("fitc"):
            note="chol(Quu), Kuf, G = diag(K - Q), chol(Quu + Kuf G^-1 Kfu): two nu-order factorisations + two nu x nu x N products")
     _, t = best(lambda: m.solve(yf))
     report("gpx_fitc_solve", "GP.train with the Woodbury precision (gp.py:100-101)", dict(N=Nf, nu=nu), t, nbytes=2.0 * 8.0 * Nf * nu)
+    m.lml_grad(sp, yf)                                     # warm: pools, block inverses of Lu and La
+    _, t = best(lambda: m.lml_grad(sp, yf))
+    report("gpx_fitc_lml_grad", "none in the reference (its FITC gradient is unrunnable); before: nparams + 1 = %d calls of "
+           "gpx_fitc_fit per optimiser iterate" % (d + 3), dict(N=Nf, nu=nu, d=d, kernel="ARD-SE", nlen=d), t,
+           flops=8.0 * Nf * nu * nu + 1.0 * nu ** 3,
+           note="B = Quu^-1 Kuf and Y = La^-1 Ks (nu^2 N each, a triangular solve counted as in SURVEY 8d), B Ks^T, its product with "
+                "Y and T = R B^T (2 nu^2 N each), one nu-order right solve; then the tiled derivative sums over R (nu x N) and T")
 # ---- f2: refit of the changed rows
 if want("refit"):
     Nr = 4096 if quick else 16384
