@@ -24,6 +24,16 @@
 // derivative of every pair from the point coordinates and stores none of the d derivative matrices.  Working memory:
 // THREE nu x N buffers (B^T then the solve's input then R; B; Y) and TWO nu x nu ones (B Ks^T, T), plus vectors and the
 // per-tile partial sums.
+//
+// gpx_fitc_lml_grad_inducing: the same call also returns dL/dS, the gradient w.r.t. the inducing-point LOCATIONS (the pseudo-inputs
+// of Snelson & Ghahramani; nothing here assumes S is a subset of X).  Moving s_u changes row u of Kuf and row and column u of
+// K(S,S); the diagonals k(s_u,s_u), k(x_i,x_i) and the nugget inside Quu do not depend on S.  So, with the R and T above,
+//     dL/ds_u[l] = sum_i R[u][i] dk(s_u, x_i)/ds_u[l] - sum_v 1/2 (T[u][v] + T[v][u]) dk(s_u, s_v)/ds_u[l]
+// with the TRUE point derivatives of acq.hip's table (zero and smooth at coincident points: S a subset of X needs no special case;
+// the v = u term vanishes).  T is symmetric up to round-off (~1e-15 of its largest entry), and row u of T is used for both halves.
+// No further solve or product: one row-wise weighted pass over the nu x N and the nu x nu pairs (fitc_wgrad_kernel, launched
+// twice), of the size of the two fitc_wsum_kernel passes, and a small kernel that adds its per-segment partials in index order.
+// Scratch grows by those partials (segments x nu x d) and the nu x d result; nothing of size nu x N x d exists.
 #include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
@@ -266,6 +276,137 @@ int fitc_wsums(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat*
   return launch_tile_sums(ctx, ppart, tr * tc, nq, out);
 }
 
+// ---- gradient w.r.t. the inducing-point locations -----------------------------------------------------------------------------
+// Rows of a strip whose running sums one thread holds at a time: all 8 of its rows up to DMAX = 4, beyond that as many as keep the
+// sums at 32 doubles per thread (the strip is then walked in 8 / rows passes over the segment's column tiles).
+constexpr int wgrad_rows(int dmax) { return dmax <= 4 ? 8 : 32 / dmax; }
+
+// column tiles of 64 per segment of a row strip, for weights of na x nb: a function of the shape alone (the sums must not depend
+// on the device), at least 2 tiles, and few enough that strips x segments reaches 1024 workgroups where the shape has them --
+// nu = 4096 has 64 strips, so against N = 32768 it gets 16 segments of 32 tiles.
+int64_t wgrad_tiles_per_segment(int64_t na, int64_t nb) {
+  const int64_t strips = gpx_round_up(na, TS) / TS, tc = gpx_round_up(nb, TS) / TS;
+  const int64_t want = (1024 + strips - 1) / strips;
+  const int64_t tps = (tc + want - 1) / want;
+  return tps < 2 ? 2 : tps;
+}
+int64_t wgrad_segments(int64_t na, int64_t nb) {
+  const int64_t tc = gpx_round_up(nb, TS) / TS, tps = wgrad_tiles_per_segment(na, nb);
+  return (tc + tps - 1) / tps;
+}
+
+// The row-wise weighted sums of the point derivative over a RECTANGULAR pair of point sets (rows u < na: the points A, columns
+// c < nb: the points B, weights Mw as for fitc_wsum_kernel):
+//     partial[seg][u][l] = sum over the columns c of segment `seg` of Mw[u][c] f(r_uc) (a_u[l] - b_c[l])
+// f = the radial factor of radial_pair (gpx_device.h); the kernel's constant and the sign are applied once, by
+// fitc_wgrad_sum_kernel.  Workgroup (blockIdx.x, blockIdx.y) = (segment, strip of 64 rows): the strip's raw coordinates stay in
+// LDS, the segment's column tiles [blockIdx.x tps, ...) pass through LDS one at a time.  Thread (tx, ty) = (t & 31, t >> 5) holds
+// the columns 2 tx + c of the tile in registers and the rows ty + 8 a: one 16-byte load of Mw per row, differences first and then
+// scaled, d running sums per row kept across the tiles.  At the end the 32 threads of a row add their sums by shuffles in a fixed
+// order and tx = 0 writes the row's d partials.  Rows >= na and columns >= nb are masked BY INDEX (a select, not a product: the
+// padding of Mw may hold NaN); their coordinates are staged as zeros, so f is finite there.
+template <int KIND, int DMAX>
+__global__ __launch_bounds__(256) void fitc_wgrad_kernel(KParams kp, const double* __restrict__ A, int64_t na,
+                                                         const double* __restrict__ B, int64_t nb,
+                                                         const double* __restrict__ Mw, int64_t ld, int64_t tc, int64_t tps,
+                                                         double* __restrict__ partial) {
+  extern __shared__ double sm[];
+  constexpr int RP = wgrad_rows(DMAX);
+  const int d = kp.d;
+  double* As = sm;            // [TS][d] raw coords of the row points
+  double* Bs = sm + TS * d;   // [TS][d] of the column points of the current tile
+  const int t = threadIdx.x, tx = t & 31, ty = t >> 5;
+  const int64_t i0 = (int64_t)blockIdx.y * TS;
+  const int64_t t0 = (int64_t)blockIdx.x * tps, t1 = t0 + tps < tc ? t0 + tps : tc;
+  for (int idx = t; idx < TS * d; idx += 256) {
+    const int64_t gi = i0 + idx / d;
+    As[idx] = gi < na ? A[gi * d + idx % d] : 0.0;
+  }
+  for (int pass = 0; pass < 8 / RP; ++pass) {
+    double acc[RP][DMAX];
+#pragma unroll
+    for (int a = 0; a < RP; ++a)
+#pragma unroll
+      for (int l = 0; l < DMAX; ++l) acc[a][l] = 0.0;
+    for (int64_t jt = t0; jt < t1; ++jt) {
+      const int64_t j0 = jt * TS;
+      __syncthreads();   // the previous tile has been read by everyone (before the first tile: As is complete)
+      for (int idx = t; idx < TS * d; idx += 256) {
+        const int64_t gj = j0 + idx / d;
+        Bs[idx] = gj < nb ? B[gj * d + idx % d] : 0.0;
+      }
+      __syncthreads();
+      double pc[2][DMAX];
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int l = 0; l < DMAX; ++l) pc[c][l] = l < d ? Bs[(2 * tx + c) * d + l] : 0.0;
+#pragma unroll
+      for (int a = 0; a < RP; ++a) {
+        const int r = ty + 8 * (pass * RP + a);
+        const int64_t gi = i0 + r;
+        const double2 mv = *reinterpret_cast<const double2*>(Mw + gi * ld + j0 + 2 * tx);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          double diff[DMAX];
+          const double f = radial_pair<KIND, DMAX>(kp, As + r * d, pc[c], diff);   // diff = a_u - b_c
+          const double w = (gi < na && j0 + 2 * tx + c < nb) ? (c == 0 ? mv.x : mv.y) * f : 0.0;
+#pragma unroll
+          for (int l = 0; l < DMAX; ++l) acc[a][l] = fma(w, diff[l], acc[a][l]);
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < RP; ++a) {
+      const int64_t gi = i0 + ty + 8 * (pass * RP + a);
+#pragma unroll
+      for (int l = 0; l < DMAX; ++l) {
+        if (l < d) {   // (uniform)
+          double s = acc[a][l];
+          for (int off = 16; off > 0; off >>= 1) s += __shfl_down(s, off, 32);
+          if (tx == 0 && gi < na) partial[((int64_t)blockIdx.x * na + gi) * d + l] = s;
+        }
+      }
+    }
+  }
+}
+
+// out[u][l] (i = u d + l < count) from the partials of fitc_wgrad_kernel, the segments added in index order, with the constant
+// that turns (factor * difference) into the TRUE derivative dk(u, p)/du_l = -c_l f (u_l - p_l) (the table of acq.hip):
+// c_l = scale_l^2 (SE), sig scale^2 (Matern 3/2), sig scale^2 / 3 (Matern 5/2).  subtract = 0: out = -c sum;  1: out -= -c sum.
+__global__ __launch_bounds__(256) void fitc_wgrad_sum_kernel(KParams kp, const double* __restrict__ partial, int64_t nseg,
+                                                             int64_t count, int subtract, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const int l = (int)(i % kp.d);
+  double s = 0.0;
+  for (int64_t g = 0; g < nseg; ++g) s += partial[g * count + i];
+  double c = kp.scale[l] * kp.scale[l];
+  if (kp.kind == GPX_K_MATERN32) c *= kp.sig;
+  if (kp.kind == GPX_K_MATERN52) c *= kp.sig / 3.0;
+  out[i] = subtract ? fma(c, s, out[i]) : -c * s;
+}
+
+// out[na x d] (device) = (subtract ? out - : ) sum_c Mw[u][c] dk(a_u, b_c)/da_u;  ppart: wgrad_segments(na, nb) x na x d doubles
+int fitc_wgrad(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat* B, const double* Mw, int64_t ld, double* ppart,
+               int subtract, double* out) {
+  const int64_t na = A->rows, nb = B->rows, tr = gpx_round_up(na, TS) / TS, tc = gpx_round_up(nb, TS) / TS;
+  const int64_t tps = wgrad_tiles_per_segment(na, nb), nseg = wgrad_segments(na, nb), count = na * kp.d;
+  ProfScope ps(ctx, GPX_PROF_REDUCE, (double)na * nb * (6.0 * kp.d + 25.0), 8.0 * (double)na * nb);
+  const size_t sh = (size_t)(2 * TS * kp.d) * sizeof(double);
+  const dim3 grid((unsigned)nseg, (unsigned)tr);
+#define GPX_CALL(K_, DM_)                                                                                                    \
+  hipLaunchKernelGGL((fitc_wgrad_kernel<K_, DM_>), grid, dim3(256), sh, ctx->stream, kp, A->p, na, B->p, nb, Mw, ld, tc, tps, \
+                     ppart)
+  GPX_RADIAL_DISPATCH(kp.kind, kp.d, GPX_CALL);
+#undef GPX_CALL
+  GPX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fitc_wgrad_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, kp,
+                     (const double*)ppart, nseg, count, subtract, out);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
 // dt (np doubles, device) <- alpha = P y:  u = Kuf Gi y = -(Ks y);  w = A^-1 u;  t = Kfu w;  alpha = Gi (y - t), 0 on the padding.
 // dy (np): y, zero padded.  du (nup), part (colreduce partials for nup x np), ps (chol_potrs_scratch_bytes(nup)): scratch.
 int fitc_alpha(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* dy, double* du, double* dt, double* part, double* ps) {
@@ -329,6 +470,119 @@ int fitc_solve_beta_t(gpx_ctx* ctx, const gpx_fitc* f, const double* B, int64_t 
 }
 
 namespace {
+
+// Shared body of gpx_fitc_lml_grad / gpx_fitc_lml_grad_inducing (header comment: the formulas, the products and the buffers).
+// logp, grad[nlen + 2] and grad_s[nu x d] (all host) are each nullable here; the entries decide what is required.
+int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                       const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
+  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
+          "fitc_lml_grad: hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
+          "the Mehler kernel has none");
+  KParams kp;
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
+  bool same = kind == f->kp.kind && d == f->kp.d && kp.sig == f->kp.sig;
+  for (int k = 0; same && k < d; ++k) same = kp.scale[k] == f->kp.scale[k];
+  GPX_ARG(same, "fitc_lml_grad: (kind, d, hyp) is not the kernel the model was fitted with");
+  GPX_ARG(X->cols == d && X->pcols == d && X->rows == f->n && S->cols == d && S->pcols == d && S->rows == f->nu,
+          "fitc_lml_grad: X and S must be the unpadded (n x d) nodes and (nu x d) inducing points of the model");
+  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int64_t ldk = f->Ks->ld, ldt = gpx_skew_ld(nup);
+  GPX_ARG(f->W->ld == ldk && f->Kuf->ld == ldk, "fitc_lml_grad: the model's nu x N matrices differ in row stride");
+  const int nd = lml_nd(kind, d), nq = nd + 1;
+  Scratch tmp(ctx);
+  double *dy, *du, *al, *part, *ps, *ssq, *mv, *cv, *ba, *dg, *b1, *Bm, *Y, *C1, *T, *ppart, *out, *gpart = nullptr, *gs = nullptr;
+  const int64_t big = np * ldt > nup * ldk ? np * ldt : nup * ldk;
+  const int64_t tiles = (nup / TS) * ((np > nup ? np : nup) / TS);   // of R (nup x np) or of T (nup x nup), whichever has more
+  GPX_TRY(tmp.get(np * 8, &dy));
+  GPX_TRY(tmp.get(nup * 8, &du));
+  GPX_TRY(tmp.get(np * 8, &al));
+  GPX_TRY(tmp.get(colreduce_partial_elems(nup, np) * 8 + 8, &part));
+  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
+  GPX_TRY(tmp.get(np * 8, &ssq));
+  GPX_TRY(tmp.get(np * 8, &mv));
+  GPX_TRY(tmp.get(np * 8, &cv));
+  GPX_TRY(tmp.get(nup * 8, &ba));
+  GPX_TRY(tmp.get(nup * 8, &dg));
+  GPX_TRY(tmp.get(big * 8, &b1));
+  GPX_TRY(tmp.get(nup * ldk * 8, &Bm));
+  GPX_TRY(tmp.get(nup * ldk * 8, &Y));
+  GPX_TRY(tmp.get(nup * ldt * 8, &C1));
+  GPX_TRY(tmp.get(nup * ldt * 8, &T));
+  GPX_TRY(tmp.get(tiles * nq * 8, &ppart));
+  GPX_TRY(tmp.get((2 * nq + 2) * 8, &out));   // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T
+  if (grad_s) {   // the per-segment partials of fitc_wgrad (weights R or T, whichever has more segments) and the nu x d result
+    const int64_t sr = wgrad_segments(nu, n), st = wgrad_segments(nu, nu);
+    GPX_TRY(tmp.get((sr > st ? sr : st) * nu * d * 8, &gpart));
+    GPX_TRY(tmp.get(nu * d * 8, &gs));
+  }
+  GPX_TRY(fitc_alpha(ctx, f, y, dy, du, al, part, ps));
+  // B = Quu^-1 Kuf = Lu^-T W through its transpose: B^T = W^T Lu^-1
+  GPX_TRY(launch_transpose(ctx, f->W->p, nup, np, ldk, b1, ldt));
+  GPX_TRY(chol_trsm_right_n(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, b1, ldt, np, nup));
+  GPX_TRY(launch_transpose(ctx, b1, np, nup, ldt, Bm, ldk));
+  // Y = La^-1 Ks through La's block inverses (the solve consumes its right-hand side: a copy);  m, c = Gi + m
+  GPX_TRY(gpx_copy2d(ctx, f->Ks->p, ldk, b1, ldk, nup, np));
+  GPX_TRY(chol_trsm_left_oop(ctx, f->La, b1, ldk, Y, ldk, np));
+  GPX_TRY(launch_colreduce(ctx, Y, ldk, nu, np, nullptr, ssq, part));
+  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
+                     (const double*)f->ginv, (const double*)ssq, n, np, mv, cv);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, mv, n, out + 2 * nq));
+  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(c), over the consumed copy
+  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
+  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
+  GPX_TRY(launch_gemm(ctx, C1, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, 4.0 * (double)nup * np, 24.0 * (double)nup * np);
+    hipLaunchKernelGGL(fitc_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
+                       (const double*)Bm, ldk, (const double*)ba, (const double*)al, (const double*)cv, np);
+  }
+  GPX_HIP(hipGetLastError());
+  // T = R B^T;  the sums against dKuf (weights R) and dK(S,S) (weights T: the same kernel with both point sets = S -- T is
+  // nu x nu, so the symmetric half that lml_trace would save is nothing, and one kernel serves both);  tr T
+  GPX_TRY(launch_gemm(ctx, b1, ldk, Bm, ldk, T, ldt, nup, nup, np, true, false, false));
+  if (grad) {
+    GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, ppart, out));
+    GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, ppart, out + nq));
+    hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, dg);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_sum(ctx, dg, nu, out + 2 * nq + 1));
+  }
+  // dL/ds_u = sum_i R[u][i] dk(s_u, x_i)/ds_u - sum_v T[u][v] dk(s_u, s_v)/ds_u: moving s_u changes row u of Kuf and row and column
+  // u of K(S,S) (T is symmetric, so row u serves for both; the v = u term is zero); the diagonals and the nugget do not move
+  if (grad_s) {
+    GPX_TRY(fitc_wgrad(ctx, kp, S, X, b1, ldk, gpart, 0, gs));
+    GPX_TRY(fitc_wgrad(ctx, kp, S, S, T, ldt, gpart, 1, gs));
+  }
+  // (the copies land in locals or in the caller's grad_s: the stream is drained before any error return, so none is pending then)
+  std::vector<double> h((size_t)(2 * nq + 2)), hal(logp ? (size_t)n : 0);
+  const hipError_t eh = grad ? hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t ea = logp ? hipMemcpyAsync(hal.data(), al, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t eg = grad_s ? hipMemcpyAsync(grad_s, gs, (size_t)(nu * d) * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  GPX_HIP(eh);
+  GPX_HIP(ea);
+  GPX_HIP(eg);
+  GPX_HIP(es);
+  if (grad) {
+    const double* hr = h.data();
+    const double* ht = h.data() + nq;
+    const double msum = h[(size_t)2 * nq], trT = h[(size_t)2 * nq + 1];
+    // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho;  dK/d signalSize = K0 / s and dk(x,x)/d signalSize = 1
+    for (int k = 0; k < nd; ++k) grad[k] = 0.5 * (2.0 * hr[k] - ht[k]) / hyp[k];
+    grad[nd] = 0.5 * ((2.0 * hr[nd] - ht[nd]) / hyp[nd] + msum);
+    grad[nd + 1] = 0.5 * (msum - trT);
+  }
+  if (logp) {
+    double logdet;
+    GPX_TRY(fitc_logdet(ctx, f, &logdet));
+    *logp = -0.5 * fitc_quad(y, hal.data(), n) - 0.5 * logdet - 0.5 * (double)n * 1.8378770664093454836;  // log 2 pi
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -449,95 +703,14 @@ int gpx_fitc_logdet(gpx_ctx* ctx, const gpx_fitc* f, double* out) {
 int gpx_fitc_lml_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                       const gpx_mat* S, const double* y, double* logp, double* grad) {
   GPX_ARG(ctx && f && X && S && y && grad, "NULL argument");
-  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
-          "fitc_lml_grad: hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
-          "the Mehler kernel has none");
-  KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  bool same = kind == f->kp.kind && d == f->kp.d && kp.sig == f->kp.sig;
-  for (int k = 0; same && k < d; ++k) same = kp.scale[k] == f->kp.scale[k];
-  GPX_ARG(same, "fitc_lml_grad: (kind, d, hyp) is not the kernel the model was fitted with");
-  GPX_ARG(X->cols == d && X->pcols == d && X->rows == f->n && S->cols == d && S->pcols == d && S->rows == f->nu,
-          "fitc_lml_grad: X and S must be the unpadded (n x d) nodes and (nu x d) inducing points of the model");
-  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
-  const int64_t ldk = f->Ks->ld, ldt = gpx_skew_ld(nup);
-  GPX_ARG(f->W->ld == ldk && f->Kuf->ld == ldk, "fitc_lml_grad: the model's nu x N matrices differ in row stride");
-  const int nd = lml_nd(kind, d), nq = nd + 1;
-  Scratch tmp(ctx);
-  double *dy, *du, *al, *part, *ps, *ssq, *mv, *cv, *ba, *dg, *b1, *Bm, *Y, *C1, *T, *ppart, *out;
-  const int64_t big = np * ldt > nup * ldk ? np * ldt : nup * ldk;
-  const int64_t tiles = (nup / TS) * ((np > nup ? np : nup) / TS);   // of R (nup x np) or of T (nup x nup), whichever has more
-  GPX_TRY(tmp.get(np * 8, &dy));
-  GPX_TRY(tmp.get(nup * 8, &du));
-  GPX_TRY(tmp.get(np * 8, &al));
-  GPX_TRY(tmp.get(colreduce_partial_elems(nup, np) * 8 + 8, &part));
-  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
-  GPX_TRY(tmp.get(np * 8, &ssq));
-  GPX_TRY(tmp.get(np * 8, &mv));
-  GPX_TRY(tmp.get(np * 8, &cv));
-  GPX_TRY(tmp.get(nup * 8, &ba));
-  GPX_TRY(tmp.get(nup * 8, &dg));
-  GPX_TRY(tmp.get(big * 8, &b1));
-  GPX_TRY(tmp.get(nup * ldk * 8, &Bm));
-  GPX_TRY(tmp.get(nup * ldk * 8, &Y));
-  GPX_TRY(tmp.get(nup * ldt * 8, &C1));
-  GPX_TRY(tmp.get(nup * ldt * 8, &T));
-  GPX_TRY(tmp.get(tiles * nq * 8, &ppart));
-  GPX_TRY(tmp.get((2 * nq + 2) * 8, &out));   // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T
-  GPX_TRY(fitc_alpha(ctx, f, y, dy, du, al, part, ps));
-  // B = Quu^-1 Kuf = Lu^-T W through its transpose: B^T = W^T Lu^-1
-  GPX_TRY(launch_transpose(ctx, f->W->p, nup, np, ldk, b1, ldt));
-  GPX_TRY(chol_trsm_right_n(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, b1, ldt, np, nup));
-  GPX_TRY(launch_transpose(ctx, b1, np, nup, ldt, Bm, ldk));
-  // Y = La^-1 Ks through La's block inverses (the solve consumes its right-hand side: a copy);  m, c = Gi + m
-  GPX_TRY(gpx_copy2d(ctx, f->Ks->p, ldk, b1, ldk, nup, np));
-  GPX_TRY(chol_trsm_left_oop(ctx, f->La, b1, ldk, Y, ldk, np));
-  GPX_TRY(launch_colreduce(ctx, Y, ldk, nu, np, nullptr, ssq, part));
-  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
-                     (const double*)f->ginv, (const double*)ssq, n, np, mv, cv);
-  GPX_HIP(hipGetLastError());
-  GPX_TRY(launch_sum(ctx, mv, n, out + 2 * nq));
-  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(c), over the consumed copy
-  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
-  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
-  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
-  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
-  GPX_TRY(launch_gemm(ctx, C1, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
-  {
-    ProfScope pr(ctx, GPX_PROF_REDUCE, 4.0 * (double)nup * np, 24.0 * (double)nup * np);
-    hipLaunchKernelGGL(fitc_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
-                       (const double*)Bm, ldk, (const double*)ba, (const double*)al, (const double*)cv, np);
-  }
-  GPX_HIP(hipGetLastError());
-  // T = R B^T;  the sums against dKuf (weights R) and dK(S,S) (weights T: the same kernel with both point sets = S -- T is
-  // nu x nu, so the symmetric half that lml_trace would save is nothing, and one kernel serves both);  tr T
-  GPX_TRY(launch_gemm(ctx, b1, ldk, Bm, ldk, T, ldt, nup, nup, np, true, false, false));
-  GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, ppart, out));
-  GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, ppart, out + nq));
-  hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, dg);
-  GPX_HIP(hipGetLastError());
-  GPX_TRY(launch_sum(ctx, dg, nu, out + 2 * nq + 1));
-  // (the copies land in locals: the stream is drained before any error return, so none is pending when they go away)
-  std::vector<double> h((size_t)(2 * nq + 2)), hal(logp ? (size_t)n : 0);
-  const hipError_t eh = hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t ea = logp ? hipMemcpyAsync(hal.data(), al, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
-  GPX_HIP(eh);
-  GPX_HIP(ea);
-  GPX_HIP(es);
-  const double* hr = h.data();
-  const double* ht = h.data() + nq;
-  const double msum = h[(size_t)2 * nq], trT = h[(size_t)2 * nq + 1];
-  // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho;  dK/d signalSize = K0 / s and dk(x,x)/d signalSize = 1
-  for (int k = 0; k < nd; ++k) grad[k] = 0.5 * (2.0 * hr[k] - ht[k]) / hyp[k];
-  grad[nd] = 0.5 * ((2.0 * hr[nd] - ht[nd]) / hyp[nd] + msum);
-  grad[nd + 1] = 0.5 * (msum - trT);
-  if (logp) {
-    double logdet;
-    GPX_TRY(fitc_logdet(ctx, f, &logdet));
-    *logp = -0.5 * fitc_quad(y, hal.data(), n) - 0.5 * logdet - 0.5 * (double)n * 1.8378770664093454836;  // log 2 pi
-  }
-  return 0;
+  return fitc_lml_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, logp, grad, nullptr);
+}
+
+// the same with grad_s[nu x d] = dL/dS (required); logp and grad nullable
+int gpx_fitc_lml_grad_inducing(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                               const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
+  GPX_ARG(ctx && f && X && S && y && grad_s, "NULL argument");
+  return fitc_lml_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, logp, grad, grad_s);
 }
 
 // mean[j] = k(z_j, X) . coeff (coeff nullable),  var[j] = k(z,z) - k_z^T P k_z (signed; nullable)

@@ -306,14 +306,20 @@ class FitcModel:
         check(self.ctx.lib.gpx_fitc_logdet(self.ctx.h, self.h, C.byref(out)))
         return out.value
 
-    def lml_grad(self, spec, y, want_value=True):
+    def lml_grad(self, spec, y, want_value=True, want_inducing=False):
         """(log marginal likelihood of y, its TRUE derivatives [lengths..., signalSize, noise variance]) (gpx_fitc_lml_grad) for
         `spec` = the kernel the model was fitted with.  want_value=False: (None, derivatives) -- the call then skips the two
-        log-determinants and the copy of alpha that only the value needs."""
+        log-determinants and the copy of alpha that only the value needs.  want_inducing=True: a third entry, the (nu, d) TRUE
+        derivatives w.r.t. the inducing-point locations, from the same call (gpx_fitc_lml_grad_inducing)."""
         y = as_f64(y)
         assert y.shape == (self.n,)
         out = np.empty(spec.nsums)
         lp = C.c_double()
+        if want_inducing:
+            gs = np.empty((self.S.shape[0], spec.d))
+            check(self.ctx.lib.gpx_fitc_lml_grad_inducing(self.ctx.h, self.h, *spec.args(), self.X.h, self.S.h, dptr(y),
+                                                          C.byref(lp) if want_value else None, dptr(out), dptr(gs)))
+            return (lp.value if want_value else None), out, gs
         check(self.ctx.lib.gpx_fitc_lml_grad(self.ctx.h, self.h, *spec.args(), self.X.h, self.S.h, dptr(y),
                                              C.byref(lp) if want_value else None, dptr(out)))
         return (lp.value if want_value else None), out

@@ -258,14 +258,18 @@ class GP:
         nodes = np.asarray(nodes, dtype=float)
         assert nodes.ndim == 2 and nodes.shape[1] == self.kernel.dimension, \
             (" Incorrect dimension of input points fed to kernel ", nodes.shape)
+        self._draw_fitcnodes(nodes)
+        ctx = _dev.context()
+        X = _dev.points(ctx, nodes)
+        return X, _dev.FitcModel(ctx, self.kernel._spec(), X, _dev.points(ctx, self.fitcnodes), float(self.noise))
+
+    def _draw_fitcnodes(self, nodes):
+        """The inducing points, unless set already: a random subset of the nodes (gp.py:186-189)."""
         if self.fitcnodes is None:
             nNodes = len(nodes)
             nu = int(np.floor(nNodes * self.FITC))
             indu = np.random.permutation(nNodes)[0:nu]
             self.fitcnodes = np.array(nodes[indu], dtype=float)
-        ctx = _dev.context()
-        X = _dev.points(ctx, nodes)
-        return X, _dev.FitcModel(ctx, self.kernel._spec(), X, _dev.points(ctx, self.fitcnodes), float(self.noise))
 
     def addNodesAndComputeCovariance(self, nodes, noiseIn=None):
         """Set the training locations and factor their covariance (no function values needed)."""
@@ -424,12 +428,19 @@ class GP:
         """Log marginal likelihood of (pts, evals) under the current hyper-parameters."""
         return self.loglikeParams(pts, evals)
 
-    def loglikeParams(self, pts, evals, returnDeriv=0, noiseIn=None):
+    def loglikeParams(self, pts, evals, returnDeriv=0, noiseIn=None, inducingDeriv=False):
         """-1/2 y^T K^-1 y - 1/2 log det K - N/2 log 2 pi  [, {key: d/d key}] (gp.py:394-468).
 
         Does not touch the trained state.  `noiseIn` (per-point nugget) works here; in the reference that branch
-        passes an unknown keyword and raises TypeError (gp.py:429-430)."""
+        passes an unknown keyword and raises TypeError (gp.py:429-430).
+
+        `inducingDeriv=True` (FITC models, with returnDeriv=1): the dict gains the key 'fitcnodes' after 'noise', the (nu, d)
+        TRUE derivative of the value w.r.t. the inducing-point locations `self.fitcnodes` (gpx_fitc_lml_grad_inducing, the same
+        call that gives the other entries).  ValueError on a dense model, with a per-point `noiseIn` or with returnDeriv=0."""
         evals = np.asarray(evals, dtype=float)
+        if inducingDeriv and (self.FITC is None or noiseIn is not None or returnDeriv != 1):
+            raise ValueError("loglikeParams: inducingDeriv=True needs a FITC model without noiseIn (the dense likelihood has no "
+                             "inducing points) and returnDeriv=1")
         if self.FITC is not None and noiseIn is None:
             spec = self.kernel._spec()
             if returnDeriv == 1 and spec.kind == _dev.K_MEHLER:
@@ -442,8 +453,11 @@ class GP:
                 # gpx_fitc_lml_grad: a few nu x nu x N products on the fitted model, no N x N matrix; its entries are true
                 # derivatives, 'noise' w.r.t. the noise variance -- scaled as in the dense branch below (gp.py:463-464)
                 keys = list(self.kernel.hyperParam.keys()) + ['noise']
-                outD = dict(zip(keys, model.lml_grad(spec, evals, want_value=False)[1]))   # the value: `out`, as without the gradient
+                res = model.lml_grad(spec, evals, want_value=False, want_inducing=bool(inducingDeriv))
+                outD = dict(zip(keys, res[1]))   # the value: `out`, as without the gradient
                 outD['noise'] *= self.noise * 2.0
+                if inducingDeriv:
+                    outD['fitcnodes'] = res[2]
                 return out, outD
             return out
         nugget = self.noise if noiseIn is None else noiseIn
@@ -530,7 +544,8 @@ class GP:
 
     # ---- hyper-parameter fit: host driver around loglikeParams -----------------------------------
     def findOptParamsLogLike(self, pts, evals, paramsStart=None, paramLowerBounds=None, paramUpperBounds=None,
-                             useNoise=None, maxiter=40, useLastParams=True, analyticGradient=False, objective="lml"):
+                             useNoise=None, maxiter=40, useLastParams=True, analyticGradient=False, objective="lml",
+                             optimizeInducing=False, inducingBounds=None):
         """Maximise the marginal likelihood over the kernel hyper-parameters (+ noise unless `useNoise` is given);
         bounds default to [max(v/10, 1e-3), min(10 v, 10)], noise to [1e-12, 1] from 1e-5 (gp.py:498-590).
 
@@ -541,9 +556,24 @@ class GP:
         `analyticGradient=True` (opt-in; squared-exponential and isotropic Matern kernels) hands L-BFGS-B the
         gradient from gpx_lml_grad -- on a FITC model from gpx_fitc_lml_grad -- instead of letting it difference the objective
         (gp.py:635, approx_grad=True): one factorisation (one FITC fit) per iterate instead of nparams+1.  The default
-        reproduces the reference's numerical-gradient search."""
+        reproduces the reference's numerical-gradient search.
+
+        `optimizeInducing=True` (FITC models; needs analyticGradient=True and objective="lml") fits the inducing-point
+        LOCATIONS with the hyper-parameters, as Snelson & Ghahramani's pseudo-inputs: L-BFGS-B searches [hyper-parameters...,
+        noise (unless useNoise), vec(S)] jointly, one gpx_fitc_fit and one gpx_fitc_lml_grad_inducing per iterate.  S starts
+        at `self.fitcnodes` (drawn as usual if None) and stays inside `inducingBounds` = (lower (d,), upper (d,)), default the
+        bounding box of `pts`.  On return `self.fitcnodes` holds the optimised points; the returned dict has no entry for
+        them."""
         if objective not in ("lml", "loo"):
             raise ValueError("findOptParamsLogLike: objective must be 'lml' or 'loo', not %r" % (objective,))
+        if optimizeInducing:
+            if self.FITC is None:
+                raise ValueError("findOptParamsLogLike: optimizeInducing=True needs a FITC model (GP(..., FITC=fraction))")
+            if not analyticGradient:
+                raise ValueError("findOptParamsLogLike: optimizeInducing=True needs analyticGradient=True (nu * d numerical "
+                                 "differences per iterate are not offered)")
+            if objective != "lml":
+                raise ValueError("findOptParamsLogLike: optimizeInducing=True needs objective='lml' (no FITC leave-one-out)")
         if paramsStart is None:
             paramsStart = copy.deepcopy(self.kernel.hyperParam)
         if paramLowerBounds is None:
@@ -559,10 +589,31 @@ class GP:
             lbs.append(1e-12)
             ubs.append(1e0)
             vals.append(1e-5)
+        nhyp = len(keys)
+        if optimizeInducing:
+            ptsArr = np.asarray(pts, dtype=float)
+            self._draw_fitcnodes(ptsArr)          # the subset the first likelihood call would draw
+            shapeS = np.shape(self.fitcnodes)
+            if inducingBounds is None:
+                inducingBounds = (ptsArr.min(axis=0), ptsArr.max(axis=0))
+            lo, hi = (np.broadcast_to(np.asarray(b, dtype=float), shapeS[1:]) for b in inducingBounds)
+            vals = list(vals) + list(np.clip(np.asarray(self.fitcnodes, dtype=float), lo, hi).ravel())
+            lbs = list(lbs) + list(np.tile(lo, shapeS[0]))
+            ubs = list(ubs) + list(np.tile(hi, shapeS[0]))
 
         def objFunc(in0, gradIn):
-            self.updateKernelParams(dict(zip(keys, in0)))
-            if objective == "loo":
+            self.updateKernelParams(dict(zip(keys, in0[:nhyp])))
+            if optimizeInducing:
+                self.fitcnodes = np.array(in0[nhyp:], dtype=float).reshape(shapeS)
+                if gradIn.size > 0:
+                    margLogLike, derivs = self.loglikeParams(pts, evals, returnDeriv=1, inducingDeriv=True)
+                    if 'noise' in keys:
+                        derivs['noise'] /= 2.0 * self.noise     # as below: the search variable is the noise VARIANCE
+                    gradIn[:nhyp] = -np.array([derivs[k] for k in keys])
+                    gradIn[nhyp:] = -derivs['fitcnodes'].ravel()
+                else:
+                    margLogLike = self.loglikeParams(pts, evals, returnDeriv=0)
+            elif objective == "loo":
                 if gradIn.size > 0:
                     margLogLike, derivs = self.looLogLike(pts, evals, returnDeriv=1)
                     gradIn[:] = -np.array([derivs[k] for k in keys])
@@ -583,8 +634,10 @@ class GP:
 
         paramsOut, optValue = self.chooseParams(lbs, ubs, vals, objFunc, maxiter=maxiter, useLastParams=useLastParams,
                                                 analyticGradient=analyticGradient)
-        params = dict(zip(keys, paramsOut))
+        params = dict(zip(keys, paramsOut[:nhyp]))
         self.updateKernelParams(params)
+        if optimizeInducing:
+            self.fitcnodes = np.array(paramsOut[nhyp:], dtype=float).reshape(shapeS)
         return params, optValue
 
     def chooseParams(self, paramLowerBounds, paramUpperBounds, startValues, costFunction, maxiter=40,

@@ -340,6 +340,19 @@ int gpx_fitc_logdet(gpx_ctx* ctx, const gpx_fitc* f, double* out);
  * nu x nu work matrices; nothing N x N.  All reductions run in a fixed order: two calls agree bit for bit. */
 int gpx_fitc_lml_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                       const gpx_mat* S, const double* y, double* logp, double* grad);
+/* As gpx_fitc_lml_grad, plus grad_s[u*d + l] = dL / dS[u][l] (host, nu x d; required): the gradient of the FITC log marginal
+ * likelihood w.r.t. the inducing-point LOCATIONS (the pseudo-inputs of Snelson & Ghahramani; S need not be a subset of X).  logp
+ * and grad are nullable; every other rule of gpx_fitc_lml_grad applies, and logp / grad hold the same bits it returns.  Moving
+ * s_u changes row u of Kuf and row and column u of K(S,S) only; the diagonals k(s_u,s_u), k(x_i,x_i) and the nugget inside Quu do
+ * not depend on S.  With the R (nu x N) and T = R B^T (nu x nu, symmetric) of gpx_fitc_lml_grad:
+ *     dL/ds_u[l] = sum_i R[u][i] dk(s_u, x_i)/ds_u[l] - sum_v 1/2 (T[u][v] + T[v][u]) dk(s_u, s_v)/ds_u[l]
+ * dk(u, p)/du is the TRUE derivative of gpx_acq_grad:  SE -(u_l - p_l) / cl_l^2 k;  Matern 3/2 -sig (3 / rho^2) e^-t (u - p);
+ * Matern 5/2 -sig (5 / (3 rho^2)) (1 + t) e^-t (u - p).  It is zero and smooth at u = p: coincident points (S a subset of X) need
+ * no special case, and the v = u term vanishes.  No further solve or product: one row-wise weighted pass over the nu x N and the
+ * nu x nu pairs from the coordinates; scratch grows by its per-segment partial sums (segments x nu x d, the segment count a
+ * function of the shape only) and the nu x d result.  Fixed-order reductions, no atomics: two calls agree bit for bit. */
+int gpx_fitc_lml_grad_inducing(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                               const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s);
 /* GP.evaluate / evaluateVariance with the FITC precision (gp.py:132-145, 246-255): mean (nullable; needs coeff) and the
  * SIGNED variance (nullable) at the M points of Z */
 int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const double* coeff, const gpx_mat* Z,

@@ -188,6 +188,13 @@ if want("fitc"):
            flops=8.0 * Nf * nu * nu + 1.0 * nu ** 3,
            note="B = Quu^-1 Kuf and Y = La^-1 Ks (nu^2 N each, a triangular solve counted as in SURVEY 8d), B Ks^T, its product with "
                 "Y and T = R B^T (2 nu^2 N each), one nu-order right solve; then the tiled derivative sums over R (nu x N) and T")
+    m.lml_grad(sp, yf, want_inducing=True)                 # warm: the partial sums and the nu x d result
+    _, t2 = best(lambda: m.lml_grad(sp, yf, want_inducing=True))
+    report("gpx_fitc_lml_grad_inducing", "none in the reference (its inducing points are a frozen random subset)",
+           dict(N=Nf, nu=nu, d=d, kernel="ARD-SE", nlen=d), t2, flops=8.0 * Nf * nu * nu + 1.0 * nu ** 3,
+           note="gpx_fitc_lml_grad plus dL/dS (nu x d): one more row-wise weighted pass over the nu x N and nu x nu pairs and the sum "
+                "of its per-segment partials; the products are those of gpx_fitc_lml_grad, so the rate is on the same count; "
+                "ratio to gpx_fitc_lml_grad in this run: %.3f" % (t2 / t))
 # ---- f2: refit of the changed rows
 if want("refit"):
     Nr = 4096 if quick else 16384
