@@ -54,6 +54,8 @@ _SIGS = {
     "gpx_fitc_logdet": (C.c_int, [c_vp, c_vp, c_dp]),
     "gpx_fitc_lml_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp]),
     "gpx_fitc_lml_grad_inducing": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "gpx_fitc_loo": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "gpx_fitc_loo_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp]),
     "gpx_fitc_posterior": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_dp]),
     "gpx_fitc_dense": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),
     "gpx_potrs_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),

@@ -34,6 +34,31 @@
 // No further solve or product: one row-wise weighted pass over the nu x N and the nu x nu pairs (fitc_wgrad_kernel, launched
 // twice), of the size of the two fitc_wsum_kernel passes, and a small kernel that adds its per-segment partials in index order.
 // Scratch grows by those partials (segments x nu x d) and the nu x d result; nothing of size nu x N x d exists.
+//
+// gpx_fitc_loo / gpx_fitc_loo_grad: leave-one-out cross-validation UNDER THE MODEL'S OWN PRIOR of the observations, N(0, Q + G) (the
+// covariance the likelihood above scores; P is its precision), and the hyper-parameter gradient of its log predictive probability.
+// p(y_i | y_-i) is the Gaussian conditional of N(0, Q + G) -- FITC refitted on X \ {x_i} with the same inducing points, y_i
+// predicted through Q -- and NOT gpx_fitc_posterior at x_i after such a refit, which keeps the reference's true k(z, X) against P.
+// With ssq_i = |Y[:, i]|^2 (P = Gi - Y^T Y):
+//     p_i = P_ii = ginv_i - ssq_i,   mean_i = y_i - alpha_i / p_i,   var_i = 1 / p_i,   L = sum_i [1/2 log p_i - alpha_i^2 / (2 p_i)] - N/2 log 2 pi
+// gpx_fitc_loo is the set-up the gradients share (alpha, Y by one nu x nu x N solve, ssq by one column reduction) and one
+// element-wise kernel; the terms of L are formed and summed as gpx_loo does (loo.hip).  The gradient is dL = 1/2 tr(M dKt) with
+//     r = alpha / p,  b = P r,  c_i = (1 + alpha_i^2 / p_i) / p_i,  C = diag(c),     M = alpha b^T + b alpha^T - P C P,  m = diag M
+// (M symmetric, N x N, never formed), and from R = B (M - diag m) on it IS gpx_fitc_lml_grad: T = R B^T, the two weighted passes, tr T
+// and the host assembly are one body (fitc_grad_tail), as is the set-up (fitc_work_begin).  Upstream of R only nu-sized objects:
+//     C1 = B Y^T,   H = Y C Y^T,   C2 = (B diag(ginv o c)) Y^T - C1 H                                            (nu x nu each)
+//     B P C P       = B diag(ginv^2 o c) - (C1 Y) diag(c o ginv) - C2 Y
+//     diag(P C P)_i = ginv_i^2 c_i - 2 ginv_i c_i ssq_i + sum_k Y_ki (H Y)_ki
+//     R             = C2 Y + C1 (Y diag(c o ginv)) + (B alpha) b^T + (B b) alpha^T - B diag(ginv^2 o c + m)
+// Seven nu x nu x N products through launch_gemm (H, H Y, C1, the scaled B Y^T, C2 Y, C1 (Y diag(c o ginv)) -- subtracted into C2 Y's
+// result with Y scaled by -(c o ginv) in place, launch_gemm accumulating as C - A B --, T) and one nu^3 (C1 H), beside the two
+// solves: about twice gpx_fitc_lml_grad.  The column sums sum_k Y_ki (H Y)_ki go through launch_colreduce (the product times Y entry
+// by entry, weights of one), b through launch_rowreduce + launch_colreduce; the new kernels are element-wise (fitc_loo_terms_kernel,
+// fitc_loo_mdiag_kernel, fitc_loo_r_kernel, scale_cols_to_kernel): padding written as zeros, masked by index, two columns per thread
+// where fitc_r_kernel does so.  No atomics; every reduction in a fixed order.  Working memory: THREE nu x N buffers (the consumed
+// copy / Y C / H Y / the scaled B / R in turn; B; Y) and THREE nu x nu ones (C1, C2, H then T), vectors and the per-tile partial
+// sums; gpx_fitc_loo: two nu x N buffers and vectors.  Nothing N x N.  p_i <= 0 or not finite: no test, as gpx_loo -- the
+// arithmetic's NaN (log) or negative variance comes back.
 #include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
@@ -257,6 +282,99 @@ __global__ __launch_bounds__(256) void fitc_r_kernel(double* __restrict__ R, int
   *reinterpret_cast<double2*>(R + r * ldr + j) = v;
 }
 
+// ---- leave-one-out: the element-wise and column-wise kernels (the header comment has the formulas) --------------------------------
+// From alpha, ginv and ssq, for i < n:  p = ginv - ssq (= P_ii),  r = alpha / p,  c = (1 + alpha^2 / p) / p,  gc = ginv c,  ngc = -gc,
+// the predictions mean = y - alpha / p, var = 1 / p, and the point's term lp of L_LOO exactly as loo_finish_kernel (loo.hip) forms
+// it.  r, c, gc, ngc, mean, var are each nullable (gpx_fitc_loo wants the predictions, the gradient wants the vectors); what is
+// written is written over all np entries, 0 from n on (masked by index: p is 0 there).
+__global__ __launch_bounds__(256) void fitc_loo_terms_kernel(const double* __restrict__ alpha, const double* __restrict__ ginv,
+                                                             const double* __restrict__ ssq, const double* __restrict__ y, int64_t n,
+                                                             int64_t np, double* __restrict__ r, double* __restrict__ c,
+                                                             double* __restrict__ gc, double* __restrict__ ngc,
+                                                             double* __restrict__ mean, double* __restrict__ var,
+                                                             double* __restrict__ lp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  const bool in = i < n;
+  const double gi = ginv[i], al = alpha[i];
+  const double p = in ? gi - ssq[i] : 1.0;
+  const double cc = in ? (1.0 + al * al / p) / p : 0.0;
+  if (r) r[i] = in ? al / p : 0.0;
+  if (c) c[i] = cc;
+  if (gc) gc[i] = in ? gi * cc : 0.0;
+  if (ngc) ngc[i] = in ? -(gi * cc) : 0.0;
+  if (mean) mean[i] = in ? y[i] - al / p : 0.0;
+  if (var) var[i] = in ? 1.0 / p : 0.0;
+  lp[i] = in ? 0.5 * log(p) - 0.5 * al * al / p - 0.9189385332046727418 : 0.0;  // 1/2 log 2 pi
+}
+
+// From t = Y^T (Y r) and hy_i = sum_k Y_ki (H Y)_ki, for i < n:
+//   b = ginv r - t (= P r),   m = 2 alpha b - (ginv^2 c - 2 ginv c ssq + hy) (= M_ii),   e = ginv^2 c + m;   all 0 on the padding
+__global__ __launch_bounds__(256) void fitc_loo_mdiag_kernel(const double* __restrict__ alpha, const double* __restrict__ ginv,
+                                                             const double* __restrict__ ssq, const double* __restrict__ r,
+                                                             const double* __restrict__ c, const double* __restrict__ t,
+                                                             const double* __restrict__ hy, int64_t n, int64_t np,
+                                                             double* __restrict__ b, double* __restrict__ m, double* __restrict__ e) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  double bv = 0.0, mv = 0.0, ev = 0.0;
+  if (i < n) {
+    const double gi = ginv[i], g2c = gi * gi * c[i];
+    bv = fma(gi, r[i], -t[i]);
+    mv = 2.0 * alpha[i] * bv - (g2c - 2.0 * gi * c[i] * ssq[i] + hy[i]);
+    ev = g2c + mv;
+  }
+  b[i] = bv;
+  m[i] = mv;
+  e[i] = ev;
+}
+
+// R[u][i] += ba[u] b[i] + bb[u] alpha[i] - B[u][i] e[i]  (rows = blockIdx.y, two columns per thread; `cols` even), as fitc_r_kernel
+__global__ __launch_bounds__(256) void fitc_loo_r_kernel(double* __restrict__ R, int64_t ldr, const double* __restrict__ B, int64_t ldb,
+                                                         const double* __restrict__ ba, const double* __restrict__ bb,
+                                                         const double* __restrict__ alpha, const double* __restrict__ b,
+                                                         const double* __restrict__ e, int64_t cols) {
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  const int64_t r = blockIdx.y;
+  if (j >= cols) return;
+  double2 v = *reinterpret_cast<double2*>(R + r * ldr + j);
+  const double2 bm = *reinterpret_cast<const double2*>(B + r * ldb + j);
+  const double2 al = *reinterpret_cast<const double2*>(alpha + j);
+  const double2 bv = *reinterpret_cast<const double2*>(b + j);
+  const double2 ev = *reinterpret_cast<const double2*>(e + j);
+  const double u1 = ba[r], u2 = bb[r];
+  v.x += fma(u1, bv.x, fma(u2, al.x, -bm.x * ev.x));
+  v.y += fma(u1, bv.y, fma(u2, al.y, -bm.y * ev.y));
+  *reinterpret_cast<double2*>(R + r * ldr + j) = v;
+}
+
+// out[r][c] = in[r][c] * (s ? s[c] : 1) * (other ? other[r][c] : 1)  (rows = blockIdx.y, two columns per thread; `cols` even;
+// `other` has in's row stride; out may be `in` itself, hence no __restrict__ on the two)
+__global__ __launch_bounds__(256) void scale_cols_to_kernel(const double* in, int64_t ldi, const double* __restrict__ s,
+                                                            const double* __restrict__ other, double* out, int64_t ldo,
+                                                            int64_t cols) {
+  const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  const int64_t r = blockIdx.y;
+  if (c >= cols) return;
+  double2 v = *reinterpret_cast<const double2*>(in + r * ldi + c);
+  if (s) {
+    const double2 w = *reinterpret_cast<const double2*>(s + c);
+    v.x *= w.x;
+    v.y *= w.y;
+  }
+  if (other) {
+    const double2 o = *reinterpret_cast<const double2*>(other + r * ldi + c);
+    v.x *= o.x;
+    v.y *= o.y;
+  }
+  *reinterpret_cast<double2*>(out + r * ldo + c) = v;
+}
+
+__global__ void fill_kernel(double* __restrict__ x, int64_t n, double v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+
 // out[i] = A[i][i], i < n
 __global__ __launch_bounds__(256) void diag_kernel(const double* __restrict__ A, int64_t ld, int64_t n, double* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -471,96 +589,117 @@ int fitc_solve_beta_t(gpx_ctx* ctx, const gpx_fitc* f, const double* B, int64_t 
 
 namespace {
 
-// Shared body of gpx_fitc_lml_grad / gpx_fitc_lml_grad_inducing (header comment: the formulas, the products and the buffers).
-// logp, grad[nlen + 2] and grad_s[nu x d] (all host) are each nullable here; the entries decide what is required.
-int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
-                       const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
-  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
-          "fitc_lml_grad: hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
-          "the Mehler kernel has none");
-  KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  bool same = kind == f->kp.kind && d == f->kp.d && kp.sig == f->kp.sig;
-  for (int k = 0; same && k < d; ++k) same = kp.scale[k] == f->kp.scale[k];
-  GPX_ARG(same, "fitc_lml_grad: (kind, d, hyp) is not the kernel the model was fitted with");
-  GPX_ARG(X->cols == d && X->pcols == d && X->rows == f->n && S->cols == d && S->pcols == d && S->rows == f->nu,
-          "fitc_lml_grad: X and S must be the unpadded (n x d) nodes and (nu x d) inducing points of the model");
+#define FITC_ARG(cond, what, msg)                                                              \
+  do {                                                                                         \
+    if (!(cond)) {                                                                             \
+      gpx_set_error("%s:%d bad argument: %s: %s", __FILE__, __LINE__, what, msg);              \
+      return -1;                                                                               \
+    }                                                                                          \
+  } while (0)
+
+// The argument rules the hyper-parameter gradients share (gpx_fitc_lml_grad*, gpx_fitc_loo_grad; `what` names the entry in the
+// message): a kernel with hyper-parameter derivatives, the one the model was fitted with, and the model's own X and S.
+int fitc_grad_args(const gpx_fitc* f, const char* what, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                   const gpx_mat* S, KParams* kp) {
+  FITC_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52, what,
+           "hyper-parameter derivatives exist for the squared exponential and the isotropic Materns (as gpx_lml_grad); "
+           "the Mehler kernel has none");
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, kp));
+  bool same = kind == f->kp.kind && d == f->kp.d && kp->sig == f->kp.sig;
+  for (int k = 0; same && k < d; ++k) same = kp->scale[k] == f->kp.scale[k];
+  FITC_ARG(same, what, "(kind, d, hyp) is not the kernel the model was fitted with");
+  FITC_ARG(X->cols == d && X->pcols == d && X->rows == f->n && S->cols == d && S->pcols == d && S->rows == f->nu, what,
+           "X and S must be the unpadded (n x d) nodes and (nu x d) inducing points of the model");
+  FITC_ARG(f->W->ld == f->Ks->ld && f->Kuf->ld == f->Ks->ld, what, "the model's nu x N matrices differ in row stride");
+  return 0;
+}
+
+// Work buffers of the calls that start from alpha, Y = La^-1 Ks and its column sums of squares (gpx_fitc_loo), and of the
+// gradients, which add B = Quu^-1 Kuf and end in the common tail from R on (fitc_grad_tail).  All from the caller's Scratch.
+struct FitcWork {
+  int64_t ldk, ldt;
+  int nq;
+  double *dy, *du, *al, *part, *ps, *ssq, *b1, *Y;              // every call
+  double *ba, *dg, *Bm, *C1, *T, *ppart, *out, *gpart, *gs;     // gradients (gpart, gs: with dL/dS only)
+};
+
+// Takes the buffers and queues the common set-up:  al = alpha = P y,  Y = La^-1 Ks,  ssq_i = |Y[:, i]|^2;  with `grad` also
+// Bm = B = Quu^-1 Kuf and the buffers of the tail (nq = sums per weighted pass; want_s: those of dL/dS).  b1 is free afterwards.
+int fitc_work_begin(gpx_ctx* ctx, const gpx_fitc* f, const double* y, bool grad, int nq, int d, bool want_s, Scratch& tmp,
+                    FitcWork* w) {
   const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
-  const int64_t ldk = f->Ks->ld, ldt = gpx_skew_ld(nup);
-  GPX_ARG(f->W->ld == ldk && f->Kuf->ld == ldk, "fitc_lml_grad: the model's nu x N matrices differ in row stride");
-  const int nd = lml_nd(kind, d), nq = nd + 1;
-  Scratch tmp(ctx);
-  double *dy, *du, *al, *part, *ps, *ssq, *mv, *cv, *ba, *dg, *b1, *Bm, *Y, *C1, *T, *ppart, *out, *gpart = nullptr, *gs = nullptr;
-  const int64_t big = np * ldt > nup * ldk ? np * ldt : nup * ldk;
-  const int64_t tiles = (nup / TS) * ((np > nup ? np : nup) / TS);   // of R (nup x np) or of T (nup x nup), whichever has more
-  GPX_TRY(tmp.get(np * 8, &dy));
-  GPX_TRY(tmp.get(nup * 8, &du));
-  GPX_TRY(tmp.get(np * 8, &al));
-  GPX_TRY(tmp.get(colreduce_partial_elems(nup, np) * 8 + 8, &part));
-  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
-  GPX_TRY(tmp.get(np * 8, &ssq));
-  GPX_TRY(tmp.get(np * 8, &mv));
-  GPX_TRY(tmp.get(np * 8, &cv));
-  GPX_TRY(tmp.get(nup * 8, &ba));
-  GPX_TRY(tmp.get(nup * 8, &dg));
-  GPX_TRY(tmp.get(big * 8, &b1));
-  GPX_TRY(tmp.get(nup * ldk * 8, &Bm));
-  GPX_TRY(tmp.get(nup * ldk * 8, &Y));
-  GPX_TRY(tmp.get(nup * ldt * 8, &C1));
-  GPX_TRY(tmp.get(nup * ldt * 8, &T));
-  GPX_TRY(tmp.get(tiles * nq * 8, &ppart));
-  GPX_TRY(tmp.get((2 * nq + 2) * 8, &out));   // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T
-  if (grad_s) {   // the per-segment partials of fitc_wgrad (weights R or T, whichever has more segments) and the nu x d result
-    const int64_t sr = wgrad_segments(nu, n), st = wgrad_segments(nu, nu);
-    GPX_TRY(tmp.get((sr > st ? sr : st) * nu * d * 8, &gpart));
-    GPX_TRY(tmp.get(nu * d * 8, &gs));
+  const int64_t ldk = w->ldk = f->Ks->ld, ldt = w->ldt = gpx_skew_ld(nup);
+  w->nq = nq;
+  w->gpart = w->gs = nullptr;
+  const int64_t big = grad && np * ldt > nup * ldk ? np * ldt : nup * ldk;
+  GPX_TRY(tmp.get(np * 8, &w->dy));
+  GPX_TRY(tmp.get(nup * 8, &w->du));
+  GPX_TRY(tmp.get(np * 8, &w->al));
+  GPX_TRY(tmp.get(colreduce_partial_elems(nup, np) * 8 + 8, &w->part));
+  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &w->ps));
+  GPX_TRY(tmp.get(np * 8, &w->ssq));
+  GPX_TRY(tmp.get(big * 8, &w->b1));
+  GPX_TRY(tmp.get(nup * ldk * 8, &w->Y));
+  if (grad) {
+    const int64_t tiles = (nup / TS) * ((np > nup ? np : nup) / TS);   // of R (nup x np) or of T (nup x nup), whichever has more
+    GPX_TRY(tmp.get(nup * 8, &w->ba));
+    GPX_TRY(tmp.get(nup * 8, &w->dg));
+    GPX_TRY(tmp.get(nup * ldk * 8, &w->Bm));
+    GPX_TRY(tmp.get(nup * ldt * 8, &w->C1));
+    GPX_TRY(tmp.get(nup * ldt * 8, &w->T));
+    GPX_TRY(tmp.get(tiles * nq * 8, &w->ppart));
+    // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T, and the sum of the leave-one-out terms
+    GPX_TRY(tmp.get((2 * nq + 3) * 8, &w->out));
+    if (want_s) {   // the per-segment partials of fitc_wgrad (weights R or T, whichever has more segments) and the nu x d result
+      const int64_t sr = wgrad_segments(nu, n), st = wgrad_segments(nu, nu);
+      GPX_TRY(tmp.get((sr > st ? sr : st) * nu * d * 8, &w->gpart));
+      GPX_TRY(tmp.get(nu * d * 8, &w->gs));
+    }
   }
-  GPX_TRY(fitc_alpha(ctx, f, y, dy, du, al, part, ps));
-  // B = Quu^-1 Kuf = Lu^-T W through its transpose: B^T = W^T Lu^-1
-  GPX_TRY(launch_transpose(ctx, f->W->p, nup, np, ldk, b1, ldt));
-  GPX_TRY(chol_trsm_right_n(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, b1, ldt, np, nup));
-  GPX_TRY(launch_transpose(ctx, b1, np, nup, ldt, Bm, ldk));
-  // Y = La^-1 Ks through La's block inverses (the solve consumes its right-hand side: a copy);  m, c = Gi + m
-  GPX_TRY(gpx_copy2d(ctx, f->Ks->p, ldk, b1, ldk, nup, np));
-  GPX_TRY(chol_trsm_left_oop(ctx, f->La, b1, ldk, Y, ldk, np));
-  GPX_TRY(launch_colreduce(ctx, Y, ldk, nu, np, nullptr, ssq, part));
-  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
-                     (const double*)f->ginv, (const double*)ssq, n, np, mv, cv);
-  GPX_HIP(hipGetLastError());
-  GPX_TRY(launch_sum(ctx, mv, n, out + 2 * nq));
-  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(c), over the consumed copy
-  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
-  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
-  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
-  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
-  GPX_TRY(launch_gemm(ctx, C1, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
-  {
-    ProfScope pr(ctx, GPX_PROF_REDUCE, 4.0 * (double)nup * np, 24.0 * (double)nup * np);
-    hipLaunchKernelGGL(fitc_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
-                       (const double*)Bm, ldk, (const double*)ba, (const double*)al, (const double*)cv, np);
+  GPX_TRY(fitc_alpha(ctx, f, y, w->dy, w->du, w->al, w->part, w->ps));
+  if (grad) {
+    // B = Quu^-1 Kuf = Lu^-T W through its transpose: B^T = W^T Lu^-1
+    GPX_TRY(launch_transpose(ctx, f->W->p, nup, np, ldk, w->b1, ldt));
+    GPX_TRY(chol_trsm_right_n(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, w->b1, ldt, np, nup));
+    GPX_TRY(launch_transpose(ctx, w->b1, np, nup, ldt, w->Bm, ldk));
   }
-  GPX_HIP(hipGetLastError());
+  // Y = La^-1 Ks through La's block inverses (the solve consumes its right-hand side: a copy)
+  GPX_TRY(gpx_copy2d(ctx, f->Ks->p, ldk, w->b1, ldk, nup, np));
+  GPX_TRY(chol_trsm_left_oop(ctx, f->La, w->b1, ldk, w->Y, ldk, np));
+  GPX_TRY(launch_colreduce(ctx, w->Y, ldk, nu, np, nullptr, w->ssq, w->part));
+  return 0;
+}
+
+// The common tail of the gradients, from R = B (M - diag m) in w.b1 and sum m in w.out[2 nq]:  T = R B^T, the weighted sums against
+// dKuf and dK(S,S), tr T, dL/dS, the copies and the host assembly.  grad[nlen + 2] and grad_s[nu x d] (host) are each nullable.
+// (xsrc, xdst, xcount): one more device-to-host copy queued with the others (alpha for the marginal likelihood's value).
+int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const FitcWork& w, const double* hyp, const gpx_mat* X,
+                   const gpx_mat* S, double* grad, double* grad_s, const double* xsrc, double* xdst, int64_t xcount,
+                   double* loo_value) {
+  const int64_t nu = f->nu, np = f->np, nup = f->nup, ldk = w.ldk, ldt = w.ldt;
+  const int nq = w.nq, nd = nq - 1, d = kp.d;
+  double *b1 = w.b1, *T = w.T, *out = w.out;
   // T = R B^T;  the sums against dKuf (weights R) and dK(S,S) (weights T: the same kernel with both point sets = S -- T is
   // nu x nu, so the symmetric half that lml_trace would save is nothing, and one kernel serves both);  tr T
-  GPX_TRY(launch_gemm(ctx, b1, ldk, Bm, ldk, T, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(launch_gemm(ctx, b1, ldk, w.Bm, ldk, T, ldt, nup, nup, np, true, false, false));
   if (grad) {
-    GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, ppart, out));
-    GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, ppart, out + nq));
-    hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, dg);
+    GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, w.ppart, out));
+    GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, w.ppart, out + nq));
+    hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, w.dg);
     GPX_HIP(hipGetLastError());
-    GPX_TRY(launch_sum(ctx, dg, nu, out + 2 * nq + 1));
+    GPX_TRY(launch_sum(ctx, w.dg, nu, out + 2 * nq + 1));
   }
   // dL/ds_u = sum_i R[u][i] dk(s_u, x_i)/ds_u - sum_v T[u][v] dk(s_u, s_v)/ds_u: moving s_u changes row u of Kuf and row and column
   // u of K(S,S) (T is symmetric, so row u serves for both; the v = u term is zero); the diagonals and the nugget do not move
   if (grad_s) {
-    GPX_TRY(fitc_wgrad(ctx, kp, S, X, b1, ldk, gpart, 0, gs));
-    GPX_TRY(fitc_wgrad(ctx, kp, S, S, T, ldt, gpart, 1, gs));
+    GPX_TRY(fitc_wgrad(ctx, kp, S, X, b1, ldk, w.gpart, 0, w.gs));
+    GPX_TRY(fitc_wgrad(ctx, kp, S, S, T, ldt, w.gpart, 1, w.gs));
   }
-  // (the copies land in locals or in the caller's grad_s: the stream is drained before any error return, so none is pending then)
-  std::vector<double> h((size_t)(2 * nq + 2)), hal(logp ? (size_t)n : 0);
+  // (the copies land in locals or in the caller's buffers: the stream is drained before any error return, so none is pending then)
+  std::vector<double> h((size_t)(2 * nq + 3));
   const hipError_t eh = grad ? hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  const hipError_t ea = logp ? hipMemcpyAsync(hal.data(), al, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  const hipError_t eg = grad_s ? hipMemcpyAsync(grad_s, gs, (size_t)(nu * d) * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t ea = xdst ? hipMemcpyAsync(xdst, xsrc, (size_t)xcount * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  const hipError_t eg = grad_s ? hipMemcpyAsync(grad_s, w.gs, (size_t)(nu * d) * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
   const hipError_t es = hipStreamSynchronize(ctx->stream);
   GPX_HIP(eh);
   GPX_HIP(ea);
@@ -574,13 +713,146 @@ int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const d
     for (int k = 0; k < nd; ++k) grad[k] = 0.5 * (2.0 * hr[k] - ht[k]) / hyp[k];
     grad[nd] = 0.5 * ((2.0 * hr[nd] - ht[nd]) / hyp[nd] + msum);
     grad[nd + 1] = 0.5 * (msum - trT);
+    if (loo_value) *loo_value = h[(size_t)2 * nq + 2];
   }
+  return 0;
+}
+
+// Shared body of gpx_fitc_lml_grad / gpx_fitc_lml_grad_inducing (header comment: the formulas, the products and the buffers).
+// logp, grad[nlen + 2] and grad_s[nu x d] (all host) are each nullable here; the entries decide what is required.
+int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                       const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
+  KParams kp;
+  GPX_TRY(fitc_grad_args(f, "fitc_lml_grad", kind, d, hyp, nhyp, X, S, &kp));
+  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int nq = lml_nd(kind, d) + 1;
+  Scratch tmp(ctx);
+  FitcWork w;
+  double *mv, *cv;
+  GPX_TRY(tmp.get(np * 8, &mv));
+  GPX_TRY(tmp.get(np * 8, &cv));
+  GPX_TRY(fitc_work_begin(ctx, f, y, true, nq, d, grad_s != nullptr, tmp, &w));
+  const int64_t ldk = w.ldk, ldt = w.ldt;
+  double *al = w.al, *b1 = w.b1, *Bm = w.Bm, *C1 = w.C1, *ba = w.ba;
+  // m, c = Gi + m
+  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
+                     (const double*)f->ginv, (const double*)w.ssq, n, np, mv, cv);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, mv, n, w.out + 2 * nq));
+  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y - B diag(c), over the consumed copy
+  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
+  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
+  GPX_TRY(launch_gemm(ctx, C1, ldt, w.Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, 4.0 * (double)nup * np, 24.0 * (double)nup * np);
+    hipLaunchKernelGGL(fitc_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
+                       (const double*)Bm, ldk, (const double*)ba, (const double*)al, (const double*)cv, np);
+  }
+  GPX_HIP(hipGetLastError());
+  std::vector<double> hal(logp ? (size_t)n : 0);
+  GPX_TRY(fitc_grad_tail(ctx, f, kp, w, hyp, X, S, grad, grad_s, al, logp ? hal.data() : nullptr, n, nullptr));
   if (logp) {
     double logdet;
     GPX_TRY(fitc_logdet(ctx, f, &logdet));
     *logp = -0.5 * fitc_quad(y, hal.data(), n) - 0.5 * logdet - 0.5 * (double)n * 1.8378770664093454836;  // log 2 pi
   }
   return 0;
+}
+
+// gpx_fitc_loo_grad (header comment: the formulas, the products and the buffers).  After the common set-up b1 is worked five times
+// over (Y C, H Y, B diag(ginv c), then R), H shares T's storage (it is dead before the tail forms T), and Y itself is scaled in
+// place once nothing reads it unscaled any more.
+int fitc_loo_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                       const gpx_mat* S, const double* y, double* logp, double* grad) {
+  KParams kp;
+  GPX_TRY(fitc_grad_args(f, "fitc_loo_grad", kind, d, hyp, nhyp, X, S, &kp));
+  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int nq = lml_nd(kind, d) + 1;
+  Scratch tmp(ctx);
+  FitcWork w;
+  double *rv, *cv, *gc, *ngc, *lp, *yr, *tv, *hy, *ones, *bv, *mv, *ev, *bb, *C2;
+  GPX_TRY(tmp.get(np * 8, &rv));
+  GPX_TRY(tmp.get(np * 8, &cv));
+  GPX_TRY(tmp.get(np * 8, &gc));
+  GPX_TRY(tmp.get(np * 8, &ngc));
+  GPX_TRY(tmp.get(np * 8, &lp));
+  GPX_TRY(tmp.get(nup * 8, &yr));
+  GPX_TRY(tmp.get(np * 8, &tv));
+  GPX_TRY(tmp.get(np * 8, &hy));
+  GPX_TRY(tmp.get(nup * 8, &ones));
+  GPX_TRY(tmp.get(np * 8, &bv));
+  GPX_TRY(tmp.get(np * 8, &mv));
+  GPX_TRY(tmp.get(np * 8, &ev));
+  GPX_TRY(tmp.get(nup * 8, &bb));
+  GPX_TRY(fitc_work_begin(ctx, f, y, true, nq, d, false, tmp, &w));
+  const int64_t ldk = w.ldk, ldt = w.ldt;
+  GPX_TRY(tmp.get(nup * ldt * 8, &C2));
+  double *al = w.al, *b1 = w.b1, *Bm = w.Bm, *Y = w.Y, *C1 = w.C1, *H = w.T, *ba = w.ba;
+  const dim3 gvec((unsigned)((np + 255) / 256)), gmat((unsigned)((np / 2 + 255) / 256), (unsigned)nup);
+  // p, r, c and the value
+  hipLaunchKernelGGL(fitc_loo_terms_kernel, gvec, dim3(256), 0, ctx->stream, (const double*)al, (const double*)f->ginv,
+                     (const double*)w.ssq, (const double*)w.dy, n, np, rv, cv, gc, ngc, (double*)nullptr, (double*)nullptr, lp);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, lp, n, w.out + 2 * nq + 2));
+  // t = Y^T (Y r)
+  GPX_TRY(launch_rowreduce(ctx, Y, ldk, nu, np, rv, yr));
+  GPX_TRY(launch_colreduce(ctx, Y, ldk, nu, np, yr, tv, w.part));
+  // H = (Y C) Y^T;  hy_i = sum_k Y_ki (H Y)_ki: the product, times Y entry by entry, summed down the columns
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, (double)nup * np, 16.0 * (double)nup * np);
+    hipLaunchKernelGGL(scale_cols_to_kernel, gmat, dim3(256), 0, ctx->stream, (const double*)Y, ldk, (const double*)cv,
+                       (const double*)nullptr, b1, ldk, np);
+  }
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_gemm(ctx, b1, ldk, Y, ldk, H, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(launch_gemm(ctx, H, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, (double)nup * np, 24.0 * (double)nup * np);
+    hipLaunchKernelGGL(scale_cols_to_kernel, gmat, dim3(256), 0, ctx->stream, (const double*)b1, ldk, (const double*)nullptr,
+                       (const double*)Y, b1, ldk, np);
+  }
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((nup + 255) / 256)), dim3(256), 0, ctx->stream, ones, nup, 1.0);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_colreduce(ctx, b1, ldk, nu, np, ones, hy, w.part));
+  // b = P r, m = diag M, e = ginv^2 c + m
+  hipLaunchKernelGGL(fitc_loo_mdiag_kernel, gvec, dim3(256), 0, ctx->stream, (const double*)al, (const double*)f->ginv,
+                     (const double*)w.ssq, (const double*)rv, (const double*)cv, (const double*)tv, (const double*)hy, n, np, bv, mv,
+                     ev);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, mv, n, w.out + 2 * nq));
+  // B alpha, B b
+  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
+  GPX_HIP(hipMemsetAsync(bb, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, bv, bb));
+  // C1 = B Y^T;  C2 = (B diag(ginv c)) Y^T - C1 H
+  GPX_TRY(launch_gemm(ctx, Bm, ldk, Y, ldk, C1, ldt, nup, nup, np, true, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, (double)nup * np, 16.0 * (double)nup * np);
+    hipLaunchKernelGGL(scale_cols_to_kernel, gmat, dim3(256), 0, ctx->stream, (const double*)Bm, ldk, (const double*)gc,
+                       (const double*)nullptr, b1, ldk, np);
+  }
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_gemm(ctx, b1, ldk, Y, ldk, C2, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(launch_gemm(ctx, C1, ldt, H, ldt, C2, ldt, nup, nup, nup, false, true, false));
+  // -B P C P = C2 Y + C1 (Y diag(ginv c)) - B diag(ginv^2 c): the first product, then Y <- -Y diag(ginv c) in place and the second
+  // product subtracted from the first (launch_gemm accumulates as C - A B);  R = that + (B alpha) b^T + (B b) alpha^T - B diag(m)
+  GPX_TRY(launch_gemm(ctx, C2, ldt, Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, (double)nup * np, 16.0 * (double)nup * np);
+    hipLaunchKernelGGL(scale_cols_kernel, gmat, dim3(256), 0, ctx->stream, Y, ldk, (const double*)ngc, np);
+  }
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_gemm(ctx, C1, ldt, Y, ldk, b1, ldk, nup, np, nup, false, true, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, 6.0 * (double)nup * np, 24.0 * (double)nup * np);
+    hipLaunchKernelGGL(fitc_loo_r_kernel, gmat, dim3(256), 0, ctx->stream, b1, ldk, (const double*)Bm, ldk, (const double*)ba,
+                       (const double*)bb, (const double*)al, (const double*)bv, (const double*)ev, np);
+  }
+  GPX_HIP(hipGetLastError());
+  return fitc_grad_tail(ctx, f, kp, w, hyp, X, S, grad, nullptr, nullptr, nullptr, 0, logp);
 }
 
 }  // namespace
@@ -711,6 +983,40 @@ int gpx_fitc_lml_grad_inducing(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d,
                                const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
   GPX_ARG(ctx && f && X && S && y && grad_s, "NULL argument");
   return fitc_lml_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, logp, grad, grad_s);
+}
+
+// mean / var (host N, each nullable) = the leave-one-out predictions under the model's own covariance Q + G, *logp (nullable) the
+// sum of their log predictive probabilities (header comment: the formulas).  One nu x nu x N solve (Y), its column sums of
+// squares, alpha; no other product.
+int gpx_fitc_loo(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* mean, double* var, double* logp) {
+  GPX_ARG(ctx && f && y, "NULL argument");
+  const int64_t n = f->n, np = f->np;
+  Scratch tmp(ctx);
+  FitcWork w;
+  double *pm, *pv, *lp;
+  GPX_TRY(tmp.get(np * 8, &pm));
+  GPX_TRY(tmp.get(np * 8, &pv));
+  GPX_TRY(tmp.get(np * 8, &lp));
+  GPX_TRY(fitc_work_begin(ctx, f, y, false, 0, 0, false, tmp, &w));
+  double* none = nullptr;
+  hipLaunchKernelGGL(fitc_loo_terms_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)w.al,
+                     (const double*)f->ginv, (const double*)w.ssq, (const double*)w.dy, n, np, none, none, none, none,
+                     mean ? pm : none, var ? pv : none, lp);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, lp, n, ctx->d_scal));
+  if (mean) GPX_HIP(hipMemcpyAsync(mean, pm, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (var) GPX_HIP(hipMemcpyAsync(var, pv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (logp) GPX_HIP(hipMemcpyAsync(logp, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// *logp (nullable) = L_LOO, the same bits as gpx_fitc_loo's; grad[nlen + 2] = its TRUE derivatives [lengths..., signalSize, noise
+// variance] (header comment: the formulas, the products and the buffers)
+int gpx_fitc_loo_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                      const gpx_mat* S, const double* y, double* logp, double* grad) {
+  GPX_ARG(ctx && f && X && S && y && grad, "NULL argument");
+  return fitc_loo_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, logp, grad);
 }
 
 // mean[j] = k(z_j, X) . coeff (coeff nullable),  var[j] = k(z,z) - k_z^T P k_z (signed; nullable)

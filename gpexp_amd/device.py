@@ -324,6 +324,28 @@ class FitcModel:
                                              C.byref(lp) if want_value else None, dptr(out)))
         return (lp.value if want_value else None), out
 
+    def loo(self, y, want_pred=True):
+        """Leave-one-out predictions under the model's own covariance Q + G (gpx_fitc_loo): (mean (N,), var (N,), L_LOO) -- mean_i /
+        var_i the Gaussian conditional of the observation y_i given all the others, L_LOO the sum of the log predictive
+        probabilities.  Needs the fitted model only, so every kernel is accepted.  `want_pred=False`: (None, None, L_LOO)."""
+        y = as_f64(np.ravel(y))
+        assert y.shape == (self.n,)
+        mean = np.empty(self.n) if want_pred else None
+        var = np.empty(self.n) if want_pred else None
+        lp = C.c_double()
+        check(self.ctx.lib.gpx_fitc_loo(self.ctx.h, self.h, dptr(y), dptr(mean), dptr(var), C.byref(lp)))
+        return mean, var, lp.value
+
+    def loo_grad(self, spec, y):
+        """(L_LOO, its TRUE derivatives [lengths..., signalSize, noise variance]) (gpx_fitc_loo_grad) for `spec` = the kernel the
+        model was fitted with; L_LOO holds the bits `loo` returns."""
+        y = as_f64(np.ravel(y))
+        assert y.shape == (self.n,)
+        out = np.empty(spec.nsums)
+        lp = C.c_double()
+        check(self.ctx.lib.gpx_fitc_loo_grad(self.ctx.h, self.h, *spec.args(), self.X.h, self.S.h, dptr(y), C.byref(lp), dptr(out)))
+        return lp.value, out
+
     def posterior(self, coeff, Z, want_mean=True, want_var=True):
         m = Z.shape[0]
         mean = np.empty(m) if want_mean else None

@@ -490,7 +490,8 @@ class GP:
         reused.  Under a multi-process session every rank runs the same single-GPU call (a block-cyclic factor is made dense
         first)."""
         if self.FITC is not None:
-            raise NotImplementedError("leave-one-out cross-validation needs the dense factor; FITC models are not supported")
+            raise NotImplementedError("looPredict / looLogLike need the dense factor; on a FITC model call fitcLooPredict / "
+                                      "fitcLooLogLike (leave-one-out under the model's own covariance Q + G)")
         nugget = self.noise if noiseIn is None else noiseIn
         X, L, _ = self._factor(pts, nugget, remember=False)
         if self.dropped > 0:
@@ -531,6 +532,55 @@ class GP:
             return out, dict(zip(keys, grad))
         return _dev.loo(ctx, L, y, want_pred=False)[2]
 
+    # ---- leave-one-out for FITC models: under the model's own covariance Q + G, through nu x N matrices only -----------------
+    def _fitc_loo_ready(self, name, dense_name):
+        if self.FITC is None:
+            raise ValueError("%s is the leave-one-out call of FITC models (GP(..., FITC=fraction)); on a dense model use %s"
+                             % (name, dense_name))
+
+    def fitcLooPredict(self, pts, evals):
+        """Leave-one-out predictions of a FITC model under the current hyper-parameters, without refits: (mean (N,), var (N,)).
+
+        The model's prior covariance of the observations is Kt = Q + G -- the matrix `loglikeParams` scores on a FITC model --
+        and leave-one-out is taken UNDER THAT MODEL: mean_i, var_i are the Gaussian conditional of N(0, Kt) for the OBSERVATION
+        evals_i given all the others, mean_i = y_i - alpha_i / P_ii, var_i = 1 / P_ii with the Woodbury precision P and
+        alpha = P y (gpx_fitc_loo).  That equals refitting FITC on the points without x_i, with the same inducing points, and
+        predicting y_i through the model's own cross-covariance Q.  It is NOT what `evaluate` returns at x_i after training
+        without x_i: `evaluate` keeps the reference's convention, the true k(z, X) against P.
+
+        Inducing points as in `loglikeParams`: drawn once, then kept in `fitcnodes`.  Every kernel; no `noiseIn` (per-point
+        noise with FITC is not offered); does not touch the trained state.  O(nu^2 N), nothing N x N.  Under a multi-process
+        session every rank runs the same single-GPU call, like the rest of FITC."""
+        self._fitc_loo_ready("fitcLooPredict", "looPredict")
+        evals = np.asarray(evals, dtype=float)
+        assert len(evals.shape) == 1, "evaluations must be an (N,) array"
+        _, model = self._fitc_model(pts)
+        mean, var, _ = model.loo(evals - self.gpPriorMean(pts))
+        return mean + self.gpPriorMean(pts), var
+
+    def fitcLooLogLike(self, pts, evals, returnDeriv=0):
+        """Leave-one-out log predictive probability sum_i log p(y_i | y_-i) of a FITC model  [, {key: d/d key}], with
+        p(y_i | y_-i) as in `fitcLooPredict` (under the model's own covariance Q + G, not `evaluate`'s convention).
+
+        The dict has the keys of loglikeParams (`kernel.hyperParam` keys + 'noise'); every entry is a TRUE derivative, 'noise'
+        with respect to the noise VARIANCE, exactly as looLogLike's (no factor 2 * noise).  Gradient: squared exponential and
+        isotropic Matern kernels (gpx_fitc_loo_grad: about twice the cost of the FITC likelihood gradient, O(nu^2 N), nothing
+        N x N).  Inducing points as in `loglikeParams`; no `noiseIn`; does not touch the trained state."""
+        self._fitc_loo_ready("fitcLooLogLike", "looLogLike")
+        spec = self.kernel._spec()
+        if returnDeriv == 1 and spec.kind == _dev.K_MEHLER:
+            raise NotImplementedError("no hyper-parameter gradient of the FITC leave-one-out objective for %s (squared "
+                                      "exponential and isotropic Matern kernels only)" % type(self.kernel).__name__)
+        evals = np.asarray(evals, dtype=float)
+        assert len(evals.shape) == 1, "evaluations must be an (N,) array"
+        _, model = self._fitc_model(pts)
+        y = evals - self.gpPriorMean(pts)
+        if returnDeriv == 1:
+            out, grad = model.loo_grad(spec, y)
+            keys = list(self.kernel.hyperParam.keys()) + ['noise']
+            return out, dict(zip(keys, grad))
+        return model.loo(y, want_pred=False)[2]
+
     def getHypParamNames(self):
         return self.kernel.hyperParam.keys()
 
@@ -549,9 +599,10 @@ class GP:
         """Maximise the marginal likelihood over the kernel hyper-parameters (+ noise unless `useNoise` is given);
         bounds default to [max(v/10, 1e-3), min(10 v, 10)], noise to [1e-12, 1] from 1e-5 (gp.py:498-590).
 
-        `objective="loo"` maximises the leave-one-out log predictive probability (looLogLike) instead; with
-        `analyticGradient=True` L-BFGS-B gets its gradient from gpx_loo_grad, whose 'noise' entry already is the derivative
-        w.r.t. the noise variance.  Any other string raises ValueError.
+        `objective="loo"` maximises the leave-one-out log predictive probability instead (looLogLike; on a FITC model
+        fitcLooLogLike, leave-one-out under the model's own covariance); with `analyticGradient=True` L-BFGS-B gets its
+        gradient from gpx_loo_grad (FITC: gpx_fitc_loo_grad), whose 'noise' entry already is the derivative w.r.t. the noise
+        variance.  Any other string raises ValueError.
 
         `analyticGradient=True` (opt-in; squared-exponential and isotropic Matern kernels) hands L-BFGS-B the
         gradient from gpx_lml_grad -- on a FITC model from gpx_fitc_lml_grad -- instead of letting it difference the objective
@@ -573,7 +624,8 @@ class GP:
                 raise ValueError("findOptParamsLogLike: optimizeInducing=True needs analyticGradient=True (nu * d numerical "
                                  "differences per iterate are not offered)")
             if objective != "lml":
-                raise ValueError("findOptParamsLogLike: optimizeInducing=True needs objective='lml' (no FITC leave-one-out)")
+                raise ValueError("findOptParamsLogLike: optimizeInducing=True needs objective='lml' (the leave-one-out "
+                                 "objective has no gradient w.r.t. the inducing-point locations yet)")
         if paramsStart is None:
             paramsStart = copy.deepcopy(self.kernel.hyperParam)
         if paramLowerBounds is None:
@@ -614,11 +666,12 @@ class GP:
                 else:
                     margLogLike = self.loglikeParams(pts, evals, returnDeriv=0)
             elif objective == "loo":
+                looLogLike = self.fitcLooLogLike if self.FITC is not None else self.looLogLike
                 if gradIn.size > 0:
-                    margLogLike, derivs = self.looLogLike(pts, evals, returnDeriv=1)
+                    margLogLike, derivs = looLogLike(pts, evals, returnDeriv=1)
                     gradIn[:] = -np.array([derivs[k] for k in keys])
                 else:
-                    margLogLike = self.looLogLike(pts, evals, returnDeriv=0)
+                    margLogLike = looLogLike(pts, evals, returnDeriv=0)
             elif gradIn.size > 0:
                 margLogLike, derivs = self.loglikeParams(pts, evals, returnDeriv=1)
                 if analyticGradient and 'noise' in derivs and 'noise' in keys:

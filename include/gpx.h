@@ -353,6 +353,41 @@ int gpx_fitc_lml_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const do
  * function of the shape only) and the nu x d result.  Fixed-order reductions, no atomics: two calls agree bit for bit. */
 int gpx_fitc_lml_grad_inducing(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                                const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s);
+/* Leave-one-out cross-validation of a FITC model (none in the reference).  It is taken UNDER THE MODEL'S OWN PRIOR of the
+ * observations, N(0, Kt) with Kt = Q + G -- the covariance whose likelihood gpx_fitc_solve + gpx_fitc_logdet score, with the Woodbury
+ * precision P the model holds: p(y_i | y_-i) is the Gaussian conditional of N(0, Kt), i.e. FITC refitted on X \ {x_i} with the
+ * same inducing points and y_i predicted through the model's own cross-covariance Q.  It is NOT gpx_fitc_posterior at x_i after a
+ * fit without x_i: that call keeps the reference's convention, the TRUE k(z, X) against P.
+ * With Gi = diag(ginv), Y = La^-1 Ks (nu x N), ssq_i = |Y[:, i]|^2 (P = Gi - Y^T Y), alpha = P y:
+ *     p_i = P_ii = ginv_i - ssq_i,     mean_i = y_i - alpha_i / p_i,     var_i = 1 / p_i
+ *     L_LOO = sum_i [ 1/2 log p_i - alpha_i^2 / (2 p_i) ] - N/2 log 2 pi
+ * mean / var: host N, each nullable; *logp (nullable) = L_LOO, its terms formed and summed as gpx_loo does.  Needs the fitted model
+ * only, so every kernel is accepted, Mehler included.  One nu x nu x N triangular solve (Y), its column sums of squares and alpha;
+ * no other product: ~nu^2 N flops, one nu x N work matrix beside the solve's consumed copy of Ks, nothing N x N.  The model is
+ * not modified.  Where some p_i <= 0 or is not finite the call does what gpx_loo does: no test, it succeeds, and that point's
+ * entries and *logp come out as the arithmetic gives them (NaN from log p_i <= 0, a negative var_i). */
+int gpx_fitc_loo(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* mean, double* var, double* logp);
+/* *logp (nullable) = L_LOO, the same bits as gpx_fitc_loo's, and grad[nlen + 2] = its derivatives in gpx_lml_grad's order
+ * [lengths..., signalSize, noise]: TRUE derivatives, the noise entry w.r.t. the noise VARIANCE (no factor 2 * noise) -- the
+ * convention of gpx_loo_grad and gpx_fitc_lml_grad, whose argument rules apply unchanged: (kind, d, hyp) = the kernel the model
+ * was fitted with, X and S its nodes and inducing points (anything else is an argument error), squared exponential and isotropic
+ * Matern only (Mehler is an argument error), the 1e-12 guard on g IGNORED by the derivative.  dL = 1/2 tr(M dKt) with the symmetric
+ * M (N x N, never formed); B = Quu^-1 Kuf:
+ *     r = alpha / p,   b = P r,   c_i = (1 + alpha_i^2 / p_i) / p_i,   C = diag(c)      (c is twice gpx_loo_grad's 1/2 (1 + ..))
+ *     M = alpha b^T + b alpha^T - P C P,      m = diag M = 2 alpha o b - diag(P C P)
+ *     R = B (M - diag m)  (nu x N),   T = R B^T  (nu x nu)
+ *     dL/d theta = 1/2 [ 2 sum R o dKuf - sum T o dK(S,S) + sum_i m_i dk(x_i,x_i) ],    dL/d noise = 1/2 [ sum m - tr T ]
+ * -- the last line, and everything from R on, is gpx_fitc_lml_grad's own code.  Upstream of R only nu-sized objects:
+ *     C1 = B Y^T,   H = Y C Y^T,   C2 = (B diag(ginv o c)) Y^T - C1 H                                        (nu x nu each)
+ *     B P C P       = B diag(ginv^2 o c) - (C1 Y) diag(c o ginv) - C2 Y
+ *     diag(P C P)_i = ginv_i^2 c_i - 2 ginv_i c_i ssq_i + sum_k Y_ki (H Y)_ki
+ *     B alpha b^T + B b alpha^T: two row reductions and a rank-2 update
+ * The two solves of gpx_fitc_lml_grad and seven nu x nu x N products (H, H Y, C1, the scaled B Y^T, C2 Y, C1 (Y diag(c o ginv))
+ * subtracted into C2 Y's result, T) plus one nu^3 (C1 H): ~16 nu^2 N flops, about twice gpx_fitc_lml_grad.  Memory: THREE nu x N
+ * and THREE nu x nu work matrices (H shares T's storage), vectors and the per-tile partial sums; nothing N x N.  The model is not
+ * modified.  p_i <= 0: as gpx_fitc_loo, no test.  All reductions run in a fixed order, no atomics: two calls agree bit for bit. */
+int gpx_fitc_loo_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                      const gpx_mat* S, const double* y, double* logp, double* grad);
 /* GP.evaluate / evaluateVariance with the FITC precision (gp.py:132-145, 246-255): mean (nullable; needs coeff) and the
  * SIGNED variance (nullable) at the M points of Z */
 int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const double* coeff, const gpx_mat* Z,

@@ -7,7 +7,8 @@ Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profil
 
 --kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
 matern52; default se) -- the other entries keep their own kernels.
---out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl).
+--out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl), the `fitc` section its two
+leave-one-out lines (profiles/fitc_loo_frows.jsonl).
 """
 import json
 import os
@@ -195,6 +196,24 @@ if want("fitc"):
            note="gpx_fitc_lml_grad plus dL/dS (nu x d): one more row-wise weighted pass over the nu x N and nu x nu pairs and the sum "
                 "of its per-segment partials; the products are those of gpx_fitc_lml_grad, so the rate is on the same count; "
                 "ratio to gpx_fitc_lml_grad in this run: %.3f" % (t2 / t))
+    m.loo(yf)                                              # warm: pools
+    _, tl = best(lambda: m.loo(yf))
+    flines = [report("gpx_fitc_loo", "N refits through GP.train (the reference has no leave-one-out call)", dict(N=Nf, nu=nu, d=d), tl,
+                     flops=1.0 * Nf * nu * nu,
+                     note="leave-one-out under the model's own covariance Q + G: Y = La^-1 Ks (nu^2 N), its column sums of squares, "
+                          "alpha; ratio to gpx_fitc_lml_grad in this run: %.3f" % (tl / t))]
+    m.loo_grad(sp, yf)                                     # warm: pools
+    _, tlg = best(lambda: m.loo_grad(sp, yf))
+    flines.append(report("gpx_fitc_loo_grad", "none in the reference", dict(N=Nf, nu=nu, d=d, kernel="ARD-SE", nlen=d), tlg,
+                         flops=16.0 * Nf * nu * nu + 2.0 * nu ** 3,
+                         note="the two solves of gpx_fitc_lml_grad (nu^2 N each) and seven nu x nu x N products (H = Y C Y^T, H Y, "
+                              "B Y^T, the scaled B Y^T, C2 Y, C1 Y diag(c ginv), T = R B^T; 2 nu^2 N each), one nu^3 product; then "
+                              "the tiled derivative sums over R and T; gpx_fitc_lml_grad in this run: %.2f ms, ratio %.3f"
+                              % (1e3 * t, tlg / t)))
+    if "--out" in sys.argv:
+        with open(sys.argv[sys.argv.index("--out") + 1], "a") as f:
+            for line in flines:
+                f.write(json.dumps(line) + "\n")
 # ---- f2: refit of the changed rows
 if want("refit"):
     Nr = 4096 if quick else 16384
