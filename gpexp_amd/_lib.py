@@ -58,6 +58,10 @@ _SIGS = {
     "gpx_fitc_loo_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp]),
     "gpx_fitc_posterior": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_dp]),
     "gpx_fitc_dense": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),
+    "gpx_vfe_fit": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, C.c_double, C.POINTER(c_vp)]),
+    "gpx_vfe_bound": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),
+    "gpx_vfe_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "gpx_vfe_posterior": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_dp]),
     "gpx_potrs_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gpx_logdet": (C.c_int, [c_vp, c_vp, c_dp]),
     "gpx_potri": (C.c_int, [c_vp, c_vp, C.POINTER(c_vp)]),

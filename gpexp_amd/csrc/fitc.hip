@@ -59,6 +59,21 @@
 // copy / Y C / H Y / the scaled B / R in turn; B; Y) and THREE nu x nu ones (C1, C2, H then T), vectors and the per-tile partial
 // sums; gpx_fitc_loo: two nu x N buffers and vectors.  Nothing N x N.  p_i <= 0 or not finite: no test, as gpx_loo -- the
 // arithmetic's NaN (log) or negative variance comes back.
+//
+// gpx_vfe_*: Titsias' variational free energy on the same struct.  A VFE model is a gpx_fitc whose G is the CONSTANT noise I
+// (g = noise, ginv = 1 / noise exactly, no 1e-12 guard; Quu keeps the nugget: inducing variables u = f(S) + eps), flagged `vfe`,
+// with one more scalar trres = sum_i (k(x_i,x_i) - Q_ii) reduced in a fixed order at fit time.  Solve, log-determinant, dense and
+// free work on it as they are; with Kt = Q + noise I, P = Kt^-1, alpha = P y:
+//     F = -1/2 y^T alpha - 1/2 log det Kt - N/2 log 2 pi - trres / (2 noise)
+//     R = B (M + I / noise) = (B alpha) alpha^T + (B Y^T) Y      (no diagonal correction),      T = R B^T
+//     dF/d theta = 1/2 [ 2 sum R o dKuf - sum T o dK(S,S) - (N / noise) dk(x,x) ],   dF/d noise = 1/2 [ tr M - tr T ] + trres / (2 noise^2)
+//     dF/ds_u as dL/ds_u above;   tr M = sum_i (alpha_i^2 - 1 / noise + ssq_i)
+// -- fitc_work_begin, C1 = B Ks^T La^-T, C1 Y, one fused rank-one pass (vfe_r_kernel) and fitc_grad_tail, whose noise entry takes its
+// scalar from a slot of its own: the three products and two solves of gpx_fitc_lml_grad, without its diag(c) pass.  Predictor (the
+// optimal variational posterior; k_u = K(S, z), nothing N x M):
+//     mean(z) = k_u^T beta_u,  beta_u = Quu^-1 (Kuf alpha);      var(z) = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2
+// per chunk of candidates one nu x M fill (two with the variance: each solve consumes its right-hand side), two left solves of
+// order nu, two column sums of squares, one weighted column sum and vfe_var_kernel; one device-to-host copy per output per chunk.
 #include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
@@ -76,6 +91,8 @@ struct gpx_fitc {
   double* g;     // diag(K - Q), 1 on the padding   np (device)
   double* ginv;  // 1 / (g + 1e-12), 0 on padding   np (device)
   double sumlogg;
+  int vfe;       // 1: a VFE model (gpx_vfe_fit): g = noise, ginv = 1 / noise, no guard
+  double trres;  // VFE: sum_i (k(x_i,x_i) - Q_ii), fixed order; 0 for FITC
 };
 
 namespace {
@@ -93,6 +110,17 @@ __global__ void fitc_g_kernel(const double* __restrict__ kd, const double* __res
     g[i] = 1.0;
     ginv[i] = 0.0;
   }
+}
+
+// VFE: g[i] = noise, ginv[i] = 1 / noise (no guard), res[i] = kd[i] - qd[i] for i < n; padding: g = 1, ginv = 0, res = 0
+__global__ void vfe_g_kernel(const double* __restrict__ kd, const double* __restrict__ qd, double noise, int64_t n, int64_t np,
+                             double* __restrict__ g, double* __restrict__ ginv, double* __restrict__ res) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  const bool in = i < n;
+  g[i] = in ? noise : 1.0;
+  ginv[i] = in ? 1.0 / noise : 0.0;
+  res[i] = in ? kd[i] - qd[i] : 0.0;
 }
 
 // out[r][c] = -in[r][c] * s[c]
@@ -254,14 +282,14 @@ __global__ __launch_bounds__(256) void fitc_wsum_kernel(KParams kp, const double
                    partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nd + 1) + q);
 }
 
-// m[i] = alpha_i^2 - ginv_i + ssq_i (= M_ii) and c[i] = alpha_i^2 + ssq_i (= ginv_i + m_i) for i < n; both 0 on the padding
+// m[i] = alpha_i^2 - ginv_i + ssq_i (= M_ii) and c[i] (nullable) = alpha_i^2 + ssq_i (= ginv_i + m_i) for i < n; both 0 on the padding
 __global__ __launch_bounds__(256) void fitc_mdiag_kernel(const double* __restrict__ alpha, const double* __restrict__ ginv,
                                                          const double* __restrict__ ssq, int64_t n, int64_t np,
                                                          double* __restrict__ m, double* __restrict__ c) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= np) return;
   const double v = i < n ? fma(alpha[i], alpha[i], ssq[i]) : 0.0;
-  c[i] = v;
+  if (c) c[i] = v;
   m[i] = i < n ? v - ginv[i] : 0.0;
 }
 
@@ -280,6 +308,28 @@ __global__ __launch_bounds__(256) void fitc_r_kernel(double* __restrict__ R, int
   v.x += fma(bu, al.x, -b.x * cv.x);
   v.y += fma(bu, al.y, -b.y * cv.y);
   *reinterpret_cast<double2*>(R + r * ldr + j) = v;
+}
+
+// VFE: R[u][i] += ba[u] alpha[i]  (R holds (B Y^T) Y; rows = blockIdx.y, two columns per thread; `cols` even), as fitc_r_kernel
+// without its diagonal term.  alpha is 0 on the padding columns, so they keep the product's zeros.
+__global__ __launch_bounds__(256) void vfe_r_kernel(double* __restrict__ R, int64_t ldr, const double* __restrict__ ba,
+                                                    const double* __restrict__ alpha, int64_t cols) {
+  const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  const int64_t r = blockIdx.y;
+  if (j >= cols) return;
+  double2 v = *reinterpret_cast<double2*>(R + r * ldr + j);
+  const double2 al = *reinterpret_cast<const double2*>(alpha + j);
+  const double bu = ba[r];
+  v.x = fma(bu, al.x, v.x);
+  v.y = fma(bu, al.y, v.y);
+  *reinterpret_cast<double2*>(R + r * ldr + j) = v;
+}
+
+// VFE predictor epilogue: var[j] = kd[j] - su[j] + sa[j] (signed), j < mc
+__global__ __launch_bounds__(256) void vfe_var_kernel(const double* __restrict__ kd, const double* __restrict__ su,
+                                                      const double* __restrict__ sa, int64_t mc, double* __restrict__ var) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < mc) var[j] = (kd[j] - su[j]) + sa[j];
 }
 
 // ---- leave-one-out: the element-wise and column-wise kernels (the header comment has the formulas) --------------------------------
@@ -568,6 +618,7 @@ double fitc_quad(const double* y, const double* coeff, int64_t n) {
 int64_t fitc_n(const gpx_fitc* f) { return f->n; }
 int64_t fitc_np(const gpx_fitc* f) { return f->np; }
 int64_t fitc_nup(const gpx_fitc* f) { return f->nup; }
+int fitc_is_vfe(const gpx_fitc* f) { return f->vfe; }
 
 // beta^T = (P B)^T for B = np x mcp right-hand sides (row stride mcp; K(X, Z) of one chunk of evaluation points) under the
 // Woodbury precision P = Gi - Ks^T A^-1 Ks (Ks = -Kuf Gi, A = La La^T): the point-derivative routines of the reference read
@@ -597,6 +648,12 @@ namespace {
     }                                                                                          \
   } while (0)
 
+// The FITC-only entries refuse a VFE model, the gpx_vfe_* entries a FITC one; `instead` names the call to use
+#define FITC_KIND(f, want_vfe, what, instead)                                                                              \
+  FITC_ARG(((f)->vfe != 0) == (want_vfe), what,                                                                            \
+           (want_vfe) ? "the model is a FITC model (gpx_fitc_fit), not a VFE model: " instead                              \
+                      : "the model is a VFE model (gpx_vfe_fit), not a FITC model: " instead)
+
 // The argument rules the hyper-parameter gradients share (gpx_fitc_lml_grad*, gpx_fitc_loo_grad; `what` names the entry in the
 // message): a kernel with hyper-parameter derivatives, the one the model was fitted with, and the model's own X and S.
 int fitc_grad_args(const gpx_fitc* f, const char* what, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
@@ -619,6 +676,8 @@ int fitc_grad_args(const gpx_fitc* f, const char* what, int kind, int d, const d
 struct FitcWork {
   int64_t ldk, ldt;
   int nq;
+  bool own_nsum;      // the noise entry's scalar comes from out[2 nq + 3] instead of sum m (VFE: tr M beside the constant -N / noise)
+  double noise_add;   // added to the noise entry (VFE: trres / (2 noise^2))
   double *dy, *du, *al, *part, *ps, *ssq, *b1, *Y;              // every call
   double *ba, *dg, *Bm, *C1, *T, *ppart, *out, *gpart, *gs;     // gradients (gpart, gs: with dL/dS only)
 };
@@ -630,6 +689,8 @@ int fitc_work_begin(gpx_ctx* ctx, const gpx_fitc* f, const double* y, bool grad,
   const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
   const int64_t ldk = w->ldk = f->Ks->ld, ldt = w->ldt = gpx_skew_ld(nup);
   w->nq = nq;
+  w->own_nsum = false;
+  w->noise_add = 0.0;
   w->gpart = w->gs = nullptr;
   const int64_t big = grad && np * ldt > nup * ldk ? np * ldt : nup * ldk;
   GPX_TRY(tmp.get(np * 8, &w->dy));
@@ -648,8 +709,9 @@ int fitc_work_begin(gpx_ctx* ctx, const gpx_fitc* f, const double* y, bool grad,
     GPX_TRY(tmp.get(nup * ldt * 8, &w->C1));
     GPX_TRY(tmp.get(nup * ldt * 8, &w->T));
     GPX_TRY(tmp.get(tiles * nq * 8, &w->ppart));
-    // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T, and the sum of the leave-one-out terms
-    GPX_TRY(tmp.get((2 * nq + 3) * 8, &w->out));
+    // [0, nq): sums against R; [nq, 2 nq): against T; then sum m, tr T, the sum of the leave-one-out terms, and the noise
+    // entry's own scalar (own_nsum)
+    GPX_TRY(tmp.get((2 * nq + 4) * 8, &w->out));
     if (want_s) {   // the per-segment partials of fitc_wgrad (weights R or T, whichever has more segments) and the nu x d result
       const int64_t sr = wgrad_segments(nu, n), st = wgrad_segments(nu, nu);
       GPX_TRY(tmp.get((sr > st ? sr : st) * nu * d * 8, &w->gpart));
@@ -670,7 +732,8 @@ int fitc_work_begin(gpx_ctx* ctx, const gpx_fitc* f, const double* y, bool grad,
   return 0;
 }
 
-// The common tail of the gradients, from R = B (M - diag m) in w.b1 and sum m in w.out[2 nq]:  T = R B^T, the weighted sums against
+// The common tail of the gradients, from R = B (M - diag m) in w.b1 and sum m in w.out[2 nq] (w.own_nsum: the scalar of the noise
+// entry in w.out[2 nq + 3], otherwise sum m serves there too):  T = R B^T, the weighted sums against
 // dKuf and dK(S,S), tr T, dL/dS, the copies and the host assembly.  grad[nlen + 2] and grad_s[nu x d] (host) are each nullable.
 // (xsrc, xdst, xcount): one more device-to-host copy queued with the others (alpha for the marginal likelihood's value).
 int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const FitcWork& w, const double* hyp, const gpx_mat* X,
@@ -696,7 +759,7 @@ int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const Fit
     GPX_TRY(fitc_wgrad(ctx, kp, S, S, T, ldt, w.gpart, 1, w.gs));
   }
   // (the copies land in locals or in the caller's buffers: the stream is drained before any error return, so none is pending then)
-  std::vector<double> h((size_t)(2 * nq + 3));
+  std::vector<double> h((size_t)(2 * nq + 4));
   const hipError_t eh = grad ? hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
   const hipError_t ea = xdst ? hipMemcpyAsync(xdst, xsrc, (size_t)xcount * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
   const hipError_t eg = grad_s ? hipMemcpyAsync(grad_s, w.gs, (size_t)(nu * d) * 8, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
@@ -712,7 +775,7 @@ int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const Fit
     // dK/d cl_k = K0 e_k^2 / cl_k;  dK/d rho = (rho dk/d rho) / rho;  dK/d signalSize = K0 / s and dk(x,x)/d signalSize = 1
     for (int k = 0; k < nd; ++k) grad[k] = 0.5 * (2.0 * hr[k] - ht[k]) / hyp[k];
     grad[nd] = 0.5 * ((2.0 * hr[nd] - ht[nd]) / hyp[nd] + msum);
-    grad[nd + 1] = 0.5 * (msum - trT);
+    grad[nd + 1] = w.own_nsum ? 0.5 * (h[(size_t)2 * nq + 3] - trT) + w.noise_add : 0.5 * (msum - trT);
     if (loo_value) *loo_value = h[(size_t)2 * nq + 2];
   }
   return 0;
@@ -723,6 +786,7 @@ int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const Fit
 int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                        const gpx_mat* S, const double* y, double* logp, double* grad, double* grad_s) {
   KParams kp;
+  FITC_KIND(f, false, "fitc_lml_grad", "call gpx_vfe_grad");
   GPX_TRY(fitc_grad_args(f, "fitc_lml_grad", kind, d, hyp, nhyp, X, S, &kp));
   const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
   const int nq = lml_nd(kind, d) + 1;
@@ -767,6 +831,7 @@ int fitc_lml_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const d
 int fitc_loo_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                        const gpx_mat* S, const double* y, double* logp, double* grad) {
   KParams kp;
+  FITC_KIND(f, false, "fitc_loo_grad", "it has no leave-one-out objective; its objective is gpx_vfe_bound / gpx_vfe_grad");
   GPX_TRY(fitc_grad_args(f, "fitc_loo_grad", kind, d, hyp, nhyp, X, S, &kp));
   const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
   const int nq = lml_nd(kind, d) + 1;
@@ -855,6 +920,56 @@ int fitc_loo_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const d
   return fitc_grad_tail(ctx, f, kp, w, hyp, X, S, grad, nullptr, nullptr, nullptr, 0, logp);
 }
 
+// F from alpha (host) and the model: the one place the VFE value is put together (gpx_vfe_bound and gpx_vfe_grad: the same bits)
+int vfe_value(gpx_ctx* ctx, const gpx_fitc* f, const double* y, const double* alpha, double* bound) {
+  double logdet;
+  GPX_TRY(fitc_logdet(ctx, f, &logdet));
+  *bound = -0.5 * fitc_quad(y, alpha, f->n) - 0.5 * logdet - 0.5 * (double)f->n * 1.8378770664093454836   // log 2 pi
+           - 0.5 * f->trres / f->noise;
+  return 0;
+}
+
+// gpx_vfe_grad (header comment: the formulas).  fitc_lml_grad_impl without the diagonal of M: R = (B alpha) alpha^T + (B Y^T) Y.
+int vfe_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                  const gpx_mat* S, const double* y, double* bound, double* grad, double* grad_s) {
+  KParams kp;
+  FITC_KIND(f, true, "vfe_grad", "call gpx_fitc_lml_grad / gpx_fitc_lml_grad_inducing");
+  GPX_TRY(fitc_grad_args(f, "vfe_grad", kind, d, hyp, nhyp, X, S, &kp));
+  const int64_t n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int nq = lml_nd(kind, d) + 1;
+  Scratch tmp(ctx);
+  FitcWork w;
+  double* mv;
+  GPX_TRY(tmp.get(np * 8, &mv));
+  GPX_TRY(fitc_work_begin(ctx, f, y, true, nq, d, grad_s != nullptr, tmp, &w));
+  const int64_t ldk = w.ldk, ldt = w.ldt;
+  double *al = w.al, *b1 = w.b1, *Bm = w.Bm, *C1 = w.C1, *ba = w.ba;
+  // the two scalars of the tail: sum_i m_i dk(x_i,x_i) with the constant m_i = -1 / noise, and tr M for the noise entry
+  w.own_nsum = true;
+  w.noise_add = 0.5 * f->trres / (f->noise * f->noise);
+  hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(256), 0, ctx->stream, w.out + 2 * nq, (int64_t)1, -(double)n / f->noise);
+  hipLaunchKernelGGL(fitc_mdiag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)al,
+                     (const double*)f->ginv, (const double*)w.ssq, n, np, mv, (double*)nullptr);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_sum(ctx, mv, n, w.out + 2 * nq + 3));
+  // R = (B alpha) alpha^T + (B Ks^T La^-T) Y, over the consumed copy
+  GPX_HIP(hipMemsetAsync(ba, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, Bm, ldk, nu, np, al, ba));
+  GPX_TRY(launch_gemm(ctx, Bm, ldk, f->Ks->p, ldk, C1, ldt, nup, nup, np, true, false, false));
+  GPX_TRY(chol_trsm_right(ctx, f->La->p, f->La->ld, f->La->aux, C1, ldt, nup, nup));
+  GPX_TRY(launch_gemm(ctx, C1, ldt, w.Y, ldk, b1, ldk, nup, np, nup, false, false, false));
+  {
+    ProfScope pr(ctx, GPX_PROF_REDUCE, 2.0 * (double)nup * np, 16.0 * (double)nup * np);
+    hipLaunchKernelGGL(vfe_r_kernel, dim3((unsigned)((np / 2 + 255) / 256), (unsigned)nup), dim3(256), 0, ctx->stream, b1, ldk,
+                       (const double*)ba, (const double*)al, np);
+  }
+  GPX_HIP(hipGetLastError());
+  std::vector<double> hal(bound ? (size_t)n : 0);
+  GPX_TRY(fitc_grad_tail(ctx, f, kp, w, hyp, X, S, grad, grad_s, al, bound ? hal.data() : nullptr, n, nullptr));
+  if (bound) GPX_TRY(vfe_value(ctx, f, y, hal.data(), bound));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -865,12 +980,15 @@ int gpx_fitc_free(gpx_ctx* ctx, gpx_fitc* f) {
   return 0;
 }
 
-int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
-                 double noise, gpx_fitc** out) {
+// Shared body of gpx_fitc_fit / gpx_vfe_fit (vfe: G = noise I and the residual trace; header comment)
+static int fitc_fit_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
+                         double noise, bool vfe, gpx_fitc** out) {
   GPX_ARG(ctx && X && S && out, "NULL argument");
   Held<gpx_fitc, gpx_fitc_free> f(ctx, new gpx_fitc());
   f->Lu = f->Kuf = f->W = f->Ks = f->La = nullptr;
   f->g = f->ginv = nullptr;
+  f->vfe = vfe ? 1 : 0;
+  f->trres = 0.0;
   GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &f->kp));
   if (!(X->cols == d && X->pcols == d && S->cols == d && S->pcols == d && S->rows > 0 && X->rows > 0)) {
     gpx_set_error("fitc: X and the inducing points must be non-empty unpadded (n x d) point sets");
@@ -907,10 +1025,23 @@ int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
   GPX_TRY(gpx_dev_alloc(ctx, f->np * 8, &f->ginv));
   GPX_TRY(launch_colreduce(ctx, f->W->p, f->W->ld, f->nu, f->np, nullptr, qd, part));
   GPX_TRY(launch_kdiag(ctx, kp, X->p, f->n, kd));
-  hipLaunchKernelGGL(fitc_g_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, kd, qd, noise,
-                     f->n, f->np, f->g, f->ginv);
-  hipLaunchKernelGGL(log_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, f->g, f->n, ctx->d_scal);
-  GPX_HIP(hipMemcpyAsync(&f->sumlogg, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (vfe) {
+    // G = noise I;  trres = sum_i (k_ii - Q_ii) over the residuals in index order (launch_sum: one workgroup, fixed tree).  (Both
+    // copies land in the model, which is released only behind a stream synchronisation.)
+    double* res;
+    GPX_TRY(tmp.get(f->np * 8 + 8, &res));
+    hipLaunchKernelGGL(vfe_g_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, kd, qd, noise, f->n, f->np,
+                       f->g, f->ginv, res);
+    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_sum(ctx, res, f->n, res + f->np));
+    GPX_HIP(hipMemcpyAsync(&f->trres, res + f->np, 8, hipMemcpyDeviceToHost, ctx->stream));
+    f->sumlogg = (double)f->n * log(noise);
+  } else {
+    hipLaunchKernelGGL(fitc_g_kernel, dim3((unsigned)((f->np + 255) / 256)), dim3(256), 0, ctx->stream, kd, qd, noise,
+                       f->n, f->np, f->g, f->ginv);
+    hipLaunchKernelGGL(log_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, f->g, f->n, ctx->d_scal);
+    GPX_HIP(hipMemcpyAsync(&f->sumlogg, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
   // Ks = -Kuf Gi;  A = Quu + Kuf Gi Kfu = Quu - Ks Kuf^T;  La = chol(A)
   {
     dim3 grid((unsigned)((f->np / 2 + 255) / 256), (unsigned)f->nup);
@@ -938,6 +1069,18 @@ int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, con
   GPX_HIP(hipGetLastError());
   *out = f.release();
   return 0;
+}
+
+int gpx_fitc_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
+                 double noise, gpx_fitc** out) {
+  return fitc_fit_impl(ctx, kind, d, hyp, nhyp, X, S, noise, false, out);
+}
+
+// a gpx_fitc whose G is noise I, flagged as a VFE model, with trres = sum_i (k(x_i,x_i) - Q_ii)
+int gpx_vfe_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
+                double noise, gpx_fitc** out) {
+  GPX_ARG(noise > 0.0, "vfe: the noise variance must be positive (it is the whole of G and the nugget of Quu)");
+  return fitc_fit_impl(ctx, kind, d, hyp, nhyp, X, S, noise, true, out);
 }
 
 int gpx_fitc_shape(const gpx_fitc* f, int64_t* n, int64_t* nu) {
@@ -990,6 +1133,7 @@ int gpx_fitc_lml_grad_inducing(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d,
 // squares, alpha; no other product.
 int gpx_fitc_loo(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* mean, double* var, double* logp) {
   GPX_ARG(ctx && f && y, "NULL argument");
+  FITC_KIND(f, false, "fitc_loo", "it has no leave-one-out call; its objective is gpx_vfe_bound / gpx_vfe_grad");
   const int64_t n = f->n, np = f->np;
   Scratch tmp(ctx);
   FitcWork w;
@@ -1023,6 +1167,7 @@ int gpx_fitc_loo_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const do
 int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const double* coeff, const gpx_mat* Z,
                        double* mean, double* var) {
   GPX_ARG(ctx && f && X && Z, "NULL argument");
+  FITC_KIND(f, false, "fitc_posterior", "call gpx_vfe_posterior");
   GPX_ARG(X->rows == f->n && X->cols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d, "point sets do not match");
   GPX_ARG(mean == nullptr || coeff != nullptr, "coeff is required for the mean");
   const int64_t M = Z->rows, d = f->kp.d, np = f->np, nup = f->nup;
@@ -1066,6 +1211,99 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
       GPX_HIP(hipStreamSynchronize(ctx->stream));
       for (int64_t j = 0; j < mc; ++j) var[j0 + j] = hk[(size_t)j] - h1[(size_t)j] + h2[(size_t)j];
     }
+  }
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// *bound = F: alpha (gpx_fitc_solve's reductions and solve), the two log-determinants and trres; B is not formed
+int gpx_vfe_bound(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* bound) {
+  GPX_ARG(ctx && f && y && bound, "NULL argument");
+  FITC_KIND(f, true, "vfe_bound", "call gpx_fitc_solve + gpx_fitc_logdet");
+  std::vector<double> hal((size_t)f->n);
+  GPX_TRY(gpx_fitc_solve(ctx, f, y, hal.data(), nullptr));
+  return vfe_value(ctx, f, y, hal.data(), bound);
+}
+
+// *bound = F (gpx_vfe_bound's bits), grad[nlen + 2] = its TRUE derivatives [lengths..., signalSize, noise variance], grad_s[nu x d]
+// = dF/dS: each nullable, at least one given (header comment: the formulas)
+int gpx_vfe_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                 const gpx_mat* S, const double* y, double* bound, double* grad, double* grad_s) {
+  GPX_ARG(ctx && f && X && S && y, "NULL argument");
+  GPX_ARG(bound || grad || grad_s, "NULL argument: at least one of bound, grad and grad_s is required");
+  return vfe_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, bound, grad, grad_s);
+}
+
+// mean[j] = k_u(z_j)^T beta_u (coeff = alpha required),  var[j] = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2 (signed); each nullable
+int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double* mean,
+                      double* var) {
+  GPX_ARG(ctx && f && S && Z, "NULL argument");
+  FITC_KIND(f, true, "vfe_posterior", "call gpx_fitc_posterior");
+  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
+          "point sets do not match");
+  GPX_ARG(mean == nullptr || coeff != nullptr, "coeff is required for the mean");
+  const int64_t M = Z->rows, d = f->kp.d, n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  if (M == 0 || (!mean && !var)) return 0;
+  KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
+  const int64_t mcmax = eval_chunk(nup);
+  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
+  // from order 2048 the solves go through the explicit block inverses, out of place (as the dense posterior)
+  const bool oop = var && nup >= 2048;
+  Scratch tmp(ctx);   // its scope exit is the synchronisation the host results wait for
+  double *B1, *B2 = nullptr, *Wo = nullptr, *part, *pm = nullptr, *su = nullptr, *sa = nullptr, *kd = nullptr, *pv = nullptr;
+  double *dc = nullptr, *bu = nullptr, *ps = nullptr;
+  GPX_TRY(tmp.get(nup * ldb_alloc * 8, &B1));
+  GPX_TRY(tmp.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
+  if (var) {
+    GPX_TRY(tmp.get(nup * ldb_alloc * 8, &B2));
+    if (oop) GPX_TRY(tmp.get(nup * ldb_alloc * 8, &Wo));
+    GPX_TRY(tmp.get(mc_alloc * 8, &su));
+    GPX_TRY(tmp.get(mc_alloc * 8, &sa));
+    GPX_TRY(tmp.get(mc_alloc * 8, &kd));
+    GPX_TRY(tmp.get(mc_alloc * 8, &pv));
+  }
+  if (mean) {
+    // beta_u = Quu^-1 (Kuf alpha): one row reduction over Kuf and both sweeps against chol(Quu); 0 on the padding
+    GPX_TRY(tmp.get(mc_alloc * 8, &pm));
+    GPX_TRY(tmp.get(np * 8, &dc));
+    GPX_TRY(tmp.get(nup * 8, &bu));
+    GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
+    GPX_HIP(hipMemsetAsync(dc, 0, (size_t)np * 8, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(dc, coeff, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
+    GPX_TRY(launch_rowreduce(ctx, f->Kuf->p, f->Kuf->ld, nu, np, dc, bu));
+    GPX_TRY(chol_potrs(ctx, f->Lu, bu, ps));
+  }
+  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
+    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
+    const double* Zc = Z->p + j0 * d;
+    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B1, nup, mcp, ldb));
+    if (mean) {
+      GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, bu, pm, part));
+      GPX_HIP(hipMemcpyAsync(mean + j0, pm, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (!var) continue;
+    // each solve consumes its right-hand side: a second fill (cheaper than a copy, as in the fit)
+    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B2, nup, mcp, ldb));
+    if (oop) {
+      GPX_TRY(chol_trsm_left_oop(ctx, f->Lu, B1, ldb, Wo, ldb, mcp));
+      GPX_TRY(launch_colreduce(ctx, Wo, ldb, nu, mcp, nullptr, su, part));
+      GPX_TRY(chol_trsm_left_oop(ctx, f->La, B2, ldb, Wo, ldb, mcp));
+      GPX_TRY(launch_colreduce(ctx, Wo, ldb, nu, mcp, nullptr, sa, part));
+    } else {
+      GPX_TRY(chol_trsm_left(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, B1, ldb, nup, mcp));
+      GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, nullptr, su, part));
+      GPX_TRY(chol_trsm_left(ctx, f->La->p, f->La->ld, f->La->aux, B2, ldb, nup, mcp));
+      GPX_TRY(launch_colreduce(ctx, B2, ldb, nu, mcp, nullptr, sa, part));
+    }
+    GPX_TRY(launch_kdiag(ctx, f->kp, Zc, mc, kd));
+    hipLaunchKernelGGL(vfe_var_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)kd,
+                       (const double*)su, (const double*)sa, mc, pv);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpyAsync(var + j0, pv, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   GPX_HIP(hipStreamSynchronize(ctx->stream));
   return 0;

@@ -435,6 +435,7 @@ struct gpx_fitc;
 int64_t fitc_n(const gpx_fitc* f);
 int64_t fitc_np(const gpx_fitc* f);
 int64_t fitc_nup(const gpx_fitc* f);
+int fitc_is_vfe(const gpx_fitc* f);   // 1: fitted by gpx_vfe_fit (the FITC-only entries refuse it)
 int fitc_solve_beta_t(gpx_ctx* ctx, const gpx_fitc* f, const double* B, int64_t mcp, double* Bt, double* U);
 
 // reduce.hip

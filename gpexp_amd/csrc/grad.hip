@@ -683,12 +683,16 @@ int gpx_var_grad_newpt(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhy
 int gpx_fitc_var_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                       const gpx_mat* Z, const double* noise_deriv, const double* eval_bias, const double* dk_bias, double* out) {
   GPX_ARG(f != nullptr, "fitc model is NULL");
+  GPX_ARG(!fitc_is_vfe(f), "fitc_var_grad: the model is a VFE model (gpx_vfe_fit), not a FITC model: the point derivatives of its "
+                           "variance are not offered; its predictor is gpx_vfe_posterior");
   return var_grad_impl(ctx, kind, d, hyp, nhyp, nullptr, f, X, Z, noise_deriv, eval_bias, dk_bias, out);
 }
 
 int gpx_fitc_var_grad_newpt(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                             const gpx_mat* Z, double* out) {
   GPX_ARG(f != nullptr, "fitc model is NULL");
+  GPX_ARG(!fitc_is_vfe(f), "fitc_var_grad_newpt: the model is a VFE model (gpx_vfe_fit), not a FITC model: the point derivatives of "
+                           "its variance are not offered; its predictor is gpx_vfe_posterior");
   return var_grad_newpt_impl(ctx, kind, d, hyp, nhyp, nullptr, f, X, Z, out);
 }
 

@@ -384,6 +384,51 @@ class FitcModel:
             pass
 
 
+class VfeModel(FitcModel):
+    """Device-resident VFE model (gpx_vfe_*): a FITC model whose G is noise * I, with Titsias' variational free energy as its
+    objective and the optimal variational posterior as its predictor.  `solve`, `logdet` and `dense` are FitcModel's; its
+    FITC-only calls (`lml_grad`, `loo`, `loo_grad`, `var_grad*`) are refused by the library with the call to use instead."""
+
+    def __init__(self, ctx, spec, X, S, noise):
+        self.ctx, self.X, self.S = ctx, X, S
+        self.h = None
+        h = c_vp()
+        check(ctx.lib.gpx_vfe_fit(ctx.h, *spec.args(), X.h, S.h, float(noise), C.byref(h)))
+        self.h = h
+        self.n = X.shape[0]
+
+    def bound(self, y):
+        """F, the variational lower bound on the log marginal likelihood of y (gpx_vfe_bound)."""
+        y = as_f64(np.ravel(y))
+        assert y.shape == (self.n,)
+        out = C.c_double()
+        check(self.ctx.lib.gpx_vfe_bound(self.ctx.h, self.h, dptr(y), C.byref(out)))
+        return out.value
+
+    def grad(self, spec, y, want_value=True, want_inducing=False):
+        """(F, its TRUE derivatives [lengths..., signalSize, noise variance][, dF/dS (nu, d)]) (gpx_vfe_grad) for `spec` = the
+        kernel the model was fitted with; F holds the bits `bound` returns.  want_value=False: None in its place."""
+        y = as_f64(np.ravel(y))
+        assert y.shape == (self.n,)
+        out = np.empty(spec.nsums)
+        lp = C.c_double()
+        gs = np.empty((self.S.shape[0], spec.d)) if want_inducing else None
+        check(self.ctx.lib.gpx_vfe_grad(self.ctx.h, self.h, *spec.args(), self.X.h, self.S.h, dptr(y),
+                                        C.byref(lp) if want_value else None, dptr(out), dptr(gs)))
+        res = ((lp.value if want_value else None), out)
+        return res + (gs,) if want_inducing else res
+
+    def posterior(self, coeff, Z, want_mean=True, want_var=True):
+        """(mean, signed variance) of the latent function at Z (gpx_vfe_posterior): k_u^T Quu^-1 Kuf coeff with coeff = alpha from
+        `solve`, and k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2."""
+        m = Z.shape[0]
+        mean = np.empty(m) if want_mean else None
+        var = np.empty(m) if want_var else None
+        co = as_f64(coeff) if want_mean else None
+        check(self.ctx.lib.gpx_vfe_posterior(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, dptr(mean), dptr(var)))
+        return mean, var
+
+
 def potrs(ctx, L, y):
     y = as_f64(y)
     out = np.empty_like(y)

@@ -26,6 +26,11 @@ chol(Quu), Kuf, G and chol(Quu + Kuf G^-1 Kfu) on the device (gpx_fitc_*); predi
 N x N `covarianceMatrix` / `precisionMatrix` are only built when read.  The reference compares `self.fitcnodes == None`,
 which raises for an ndarray, so there a GP instance survives only ONE FITC operation; here refits simply reuse
 `fitcnodes`.  `generateSamples` stays out of scope.
+
+VFE (none in the reference): `GP(kernel, noise, FITC=fraction, sparse="vfe")` keeps the same inducing points but scores and predicts
+with Titsias' variational free energy (gpx_vfe_*): `loglikeParams` / `computeLogLike` return the lower bound F, with its
+gradients, `evaluate` / `evaluateVariance` the optimal variational posterior of the latent function -- not FITC's convention of
+the true k(z, X) against the Woodbury precision.  Quu keeps the noise nugget, as in the FITC model.
 """
 import copy
 import warnings
@@ -52,8 +57,15 @@ class GP:
     pts = None
     FITC = None
     fitcnodes = None
+    sparse = "fitc"   # which sparse model FITC=fraction builds: "fitc" or "vfe"
 
     def __init__(self, kernel_in, noiseIn, **kwargs):
+        sparse = kwargs.get('sparse', 'fitc')
+        if sparse not in ('fitc', 'vfe'):
+            raise ValueError("GP: sparse must be 'fitc' or 'vfe', not %r" % (sparse,))
+        if sparse == 'vfe' and kwargs.get('FITC') is None:
+            raise ValueError("GP: sparse='vfe' needs FITC=fraction (the share of the nodes drawn as inducing points)")
+        self.sparse = sparse
         try:
             self.kernel = copy.deepcopy(kernel_in)
         except Exception:
@@ -261,7 +273,17 @@ class GP:
         self._draw_fitcnodes(nodes)
         ctx = _dev.context()
         X = _dev.points(ctx, nodes)
-        return X, _dev.FitcModel(ctx, self.kernel._spec(), X, _dev.points(ctx, self.fitcnodes), float(self.noise))
+        Model = _dev.VfeModel if self._vfe() else _dev.FitcModel
+        return X, Model(ctx, self.kernel._spec(), X, _dev.points(ctx, self.fitcnodes), float(self.noise))
+
+    def _vfe(self):
+        return self.FITC is not None and self.sparse == 'vfe'
+
+    def _not_on_vfe(self, what):
+        if self._vfe():
+            raise NotImplementedError("%s is not offered on a VFE model (GP(..., sparse='vfe')): its objective is "
+                                      "loglikeParams (the variational bound), its predictor evaluate(compvar=0/1) / "
+                                      "evaluateVariance" % what)
 
     def _draw_fitcnodes(self, nodes):
         """The inducing points, unless set already: a random subset of the nodes (gp.py:186-189)."""
@@ -309,6 +331,8 @@ class GP:
     def evaluate(self, newpt, compvar=0):
         """Posterior mean at `newpt`; compvar=1 also |variance| (gp.py:145), compvar=2 the full covariance."""
         assert newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
+        if compvar == 2:
+            self._not_on_vfe("evaluate(compvar=2), the full posterior covariance,")
         ctx = _dev.context()
         spec = self.kernel._spec()
         Z = _dev.points(ctx, newpt)
@@ -359,6 +383,8 @@ class GP:
         """Shape checks and the kernel gate of the point-derivative routines.  `referenceOnly` (the reference-named methods):
         only the kernels whose `derivative` the reference defines; False (varianceGradient / varianceGradientWRTnewpt, the
         IVAR gradient): also the kernels with a `pointDerivative` -- the isotropic Matern kernels."""
+        self._not_on_vfe("the point derivative of the posterior variance (evaluateVarianceDerivative, evaluateVarianceDerivWRTnewpt, "
+                         "varianceGradient*, costFunctionGP_IVAR.derivative)")
         assert self.pts is not None, "must specify training points before running this"
         assert newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
         if not self._has_factor() and self._fitc is None:
@@ -436,17 +462,34 @@ class GP:
 
         `inducingDeriv=True` (FITC models, with returnDeriv=1): the dict gains the key 'fitcnodes' after 'noise', the (nu, d)
         TRUE derivative of the value w.r.t. the inducing-point locations `self.fitcnodes` (gpx_fitc_lml_grad_inducing, the same
-        call that gives the other entries).  ValueError on a dense model, with a per-point `noiseIn` or with returnDeriv=0."""
+        call that gives the other entries).  ValueError on a dense model, with a per-point `noiseIn` or with returnDeriv=0.
+
+        On a VFE model (sparse="vfe") the value is Titsias' lower bound F on the log marginal likelihood (gpx_vfe_bound) and the
+        dict, with the same keys and conventions, its derivatives (gpx_vfe_grad); `noiseIn` raises NotImplementedError."""
         evals = np.asarray(evals, dtype=float)
         if inducingDeriv and (self.FITC is None or noiseIn is not None or returnDeriv != 1):
             raise ValueError("loglikeParams: inducingDeriv=True needs a FITC model without noiseIn (the dense likelihood has no "
                              "inducing points) and returnDeriv=1")
+        if noiseIn is not None:
+            self._not_on_vfe("per-point noise (noiseIn)")
         if self.FITC is not None and noiseIn is None:
             spec = self.kernel._spec()
             if returnDeriv == 1 and spec.kind == _dev.K_MEHLER:
-                raise NotImplementedError("no hyper-parameter gradient of the FITC likelihood for %s (squared exponential "
-                                          "and isotropic Matern kernels only)" % type(self.kernel).__name__)
+                raise NotImplementedError("no hyper-parameter gradient of the %s for %s (squared exponential "
+                                          "and isotropic Matern kernels only)"
+                                          % ("VFE bound" if self._vfe() else "FITC likelihood", type(self.kernel).__name__))
             _, model = self._fitc_model(pts)
+            if self._vfe():
+                # gpx_vfe_bound / gpx_vfe_grad: the variational lower bound F and its TRUE derivatives, 'noise' scaled as below
+                if returnDeriv != 1:
+                    return model.bound(evals)
+                keys = list(self.kernel.hyperParam.keys()) + ['noise']
+                res = model.grad(spec, evals, want_inducing=bool(inducingDeriv))
+                outD = dict(zip(keys, res[1]))
+                outD['noise'] *= self.noise * 2.0
+                if inducingDeriv:
+                    outD['fitcnodes'] = res[2]
+                return res[0], outD
             quad = model.solve(evals)[1]
             out = -0.5 * quad - 0.5 * model.logdet() - len(evals) / 2.0 * np.log(2.0 * np.pi)
             if returnDeriv == 1:
@@ -489,6 +532,7 @@ class GP:
         loglikeParams: the trained state is not touched, and right after `train` on the same points the kept factor is
         reused.  Under a multi-process session every rank runs the same single-GPU call (a block-cyclic factor is made dense
         first)."""
+        self._not_on_vfe("looPredict / looLogLike (leave-one-out)")
         if self.FITC is not None:
             raise NotImplementedError("looPredict / looLogLike need the dense factor; on a FITC model call fitcLooPredict / "
                                       "fitcLooLogLike (leave-one-out under the model's own covariance Q + G)")
@@ -534,6 +578,7 @@ class GP:
 
     # ---- leave-one-out for FITC models: under the model's own covariance Q + G, through nu x N matrices only -----------------
     def _fitc_loo_ready(self, name, dense_name):
+        self._not_on_vfe("%s (leave-one-out)" % name)
         if self.FITC is None:
             raise ValueError("%s is the leave-one-out call of FITC models (GP(..., FITC=fraction)); on a dense model use %s"
                              % (name, dense_name))
@@ -614,9 +659,14 @@ class GP:
         noise (unless useNoise), vec(S)] jointly, one gpx_fitc_fit and one gpx_fitc_lml_grad_inducing per iterate.  S starts
         at `self.fitcnodes` (drawn as usual if None) and stays inside `inducingBounds` = (lower (d,), upper (d,)), default the
         bounding box of `pts`.  On return `self.fitcnodes` holds the optimised points; the returned dict has no entry for
-        them."""
+        them.
+
+        On a VFE model (sparse="vfe") the objective is the variational bound, the one to trust with `optimizeInducing=True`: it
+        never rewards piled-up inducing points or a collapsing noise.  objective="loo" raises NotImplementedError there."""
         if objective not in ("lml", "loo"):
             raise ValueError("findOptParamsLogLike: objective must be 'lml' or 'loo', not %r" % (objective,))
+        if objective == "loo":
+            self._not_on_vfe("objective='loo'")
         if optimizeInducing:
             if self.FITC is None:
                 raise ValueError("findOptParamsLogLike: optimizeInducing=True needs a FITC model (GP(..., FITC=fraction))")

@@ -402,6 +402,46 @@ int gpx_fitc_var_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const do
 int gpx_fitc_var_grad_newpt(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                             const gpx_mat* Z, double* out);
 
+/* ---- VFE: Titsias' variational free energy on the same inducing-point model (none in the reference) --------------------------
+ * A lower bound on the exact log marginal likelihood that never decreases when an inducing point is added -- the objective to
+ * trust with the joint search over hyper-parameters, noise and inducing-point locations, where FITC's likelihood rewards
+ * piled-up inducing points and a collapsing noise.  Conventions are this library's: the inducing block keeps the nugget exactly
+ * as the FITC model does, Quu = K(S,S) + noise I (Titsias' construction with inducing variables u = f(S) + eps, eps ~ N(0, noise I),
+ * so the bound property holds unchanged), Kuf = K(S,X), B = Quu^-1 Kuf, Q = Kfu B.  With Kt = Q + noise I, P = Kt^-1, alpha = P y
+ * and q_i = Q_ii:
+ *     F = -1/2 y^T alpha - 1/2 log det Kt - N/2 log 2 pi - (1 / (2 noise)) sum_i (k(x_i,x_i) - q_i)
+ * A VFE model is a gpx_fitc whose G is noise I (g = noise, ginv = 1 / noise exactly, no 1e-12 guard), flagged as such, with one
+ * more scalar trres = sum_i (k_ii - q_i) reduced in a fixed order at fit time.  gpx_fitc_solve, gpx_fitc_logdet, gpx_fitc_dense,
+ * gpx_fitc_shape and gpx_fitc_free work on it as they are.  The FITC-only entries (gpx_fitc_lml_grad*, gpx_fitc_loo*,
+ * gpx_fitc_posterior, gpx_fitc_var_grad*) refuse a VFE model with an argument error that names the call to use, and the gpx_vfe_*
+ * entries refuse a FITC model the same way.  noise <= 0 is an argument error.
+ * Gradient.  M = alpha alpha^T - P (never formed), Y = La^-1 Ks, P = I / noise - Y^T Y, ssq_i = |Y[:, i]|^2:
+ *     R = B (M + I / noise) = (B alpha) alpha^T + (B Y^T) Y      (nu x N; no diagonal correction, unlike FITC),      T = R B^T
+ *     dF/d theta = 1/2 [ 2 sum R o dKuf - sum T o dK(S,S) + sum_i m_i dk(x_i,x_i) ]    with m_i = -1 / noise
+ *     dF/d noise = 1/2 [ tr M - tr T ] + trres / (2 noise^2),     tr M = sum_i (alpha_i^2 - 1 / noise + ssq_i)
+ *     dF/ds_u    = sum_i R[u][i] dk(s_u,x_i)/ds_u - sum_v 1/2 (T[u][v] + T[v][u]) dk(s_u,s_v)/ds_u
+ * -- the first and third lines are gpx_fitc_lml_grad's own code from R on.  The same three nu x nu x N products and two solves as
+ * gpx_fitc_lml_grad, one element-wise pass fewer.  Fixed-order reductions, no atomics: two calls agree bit for bit.
+ * Predictor: the optimal variational posterior of the latent f at z, with k_u = K(S, z) -- NOT gpx_fitc_posterior's convention (the
+ * reference's true k(z, X) against the Woodbury precision, O(nu N) per point); O(nu^2) per point, nothing N x M is formed:
+ *     mean(z) = k_u^T beta_u,   beta_u = B alpha = Quu^-1 (Kuf alpha);      var(z) = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2  (>= 0 in exact arithmetic) */
+/* a gpx_fitc whose G is noise I, flagged as a VFE model; noise <= 0 is an argument error */
+int gpx_vfe_fit(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S, double noise,
+                gpx_fitc** out);
+/* *bound = F (the solve, the two log-determinants and trres; B is not formed).  y: host, N. */
+int gpx_vfe_bound(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* bound);
+/* *bound = F (the bits gpx_vfe_bound returns), grad[nlen + 2] = its TRUE derivatives [lengths..., signalSize, noise VARIANCE] (no
+ * factor 2 * noise), grad_s[u*d + l] = dF / dS[u][l] (host, nu x d): each nullable, at least one given.  The argument rules of
+ * gpx_fitc_lml_grad: (kind, d, hyp) = the kernel the model was fitted with, X and S its nodes and inducing points, squared
+ * exponential and isotropic Matern only (Mehler is an argument error).  The model is not modified. */
+int gpx_vfe_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
+                 const double* y, double* bound, double* grad, double* grad_s);
+/* mean (nullable; needs coeff = alpha from gpx_fitc_solve, host N) and the SIGNED variance (nullable) at the M points of Z; every
+ * kernel kind.  S = the model's inducing points.  Chunked over Z under GPX_CROSS_BYTES (a nu x chunk matrix), a point's values the
+ * same bits whatever the chunking; one device-to-host copy per output per chunk. */
+int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double* mean,
+                      double* var);
+
 /* ---- measurement ------------------------------------------------------------------------------- */
 /* when enabled every kernel launch of a class is bracketed by HIP events on the launch stream */
 int gpx_profile_enable(gpx_ctx* ctx, int on);

@@ -9,6 +9,7 @@ Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profil
 matern52; default se) -- the other entries keep their own kernels.
 --out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl), the `fitc` section its two
 leave-one-out lines (profiles/fitc_loo_frows.jsonl).
+--vfe-out: where the `fitc` section appends its gpx_vfe_* lines (default profiles/vfe_frows.jsonl).
 """
 import json
 import os
@@ -214,6 +215,55 @@ if want("fitc"):
         with open(sys.argv[sys.argv.index("--out") + 1], "a") as f:
             for line in flines:
                 f.write(json.dumps(line) + "\n")
+    # VFE on the same shape and inducing points (gpx_vfe_*; appended to profiles/vfe_frows.jsonl).  The FITC calls it is compared
+    # with are timed again here, interleaved, five repetitions each: (min, max) of both sides go into the note.
+    def spread(f, reps=5):
+        ts = []
+        for _ in range(reps):
+            ts.append(best(f, reps=1)[1])
+        return min(ts), max(ts)
+
+    mv, tvf = best(lambda: dev.VfeModel(ctx, sp, Xfd, Sd, 0.1), reps=2)
+    _, tff = best(lambda: dev.FitcModel(ctx, sp, Xfd, Sd, 0.1), reps=2)
+    vlines = [report("gpx_vfe_fit", "none in the reference (FITC is its only sparse model)", dict(N=Nf, nu=nu, d=d), tvf,
+                     flops=2.0 * nu ** 3 / 3.0 + 2.0 * Nf * nu * nu,
+                     note="gpx_fitc_fit with G = noise I and the residual trace sum_i (k_ii - Q_ii): the same two factorisations and "
+                          "two nu x nu x N products; gpx_fitc_fit in this run: %.2f ms, ratio %.3f" % (1e3 * tff, tvf / tff))]
+    mv.grad(sp, yf)                                        # warm: pools, block inverses of Lu and La
+    (tg0, tg1), (tf0, tf1) = spread(lambda: mv.grad(sp, yf)), spread(lambda: m.lml_grad(sp, yf))
+    vlines.append(report("gpx_vfe_grad", "none in the reference", dict(N=Nf, nu=nu, d=d, kernel="ARD-SE", nlen=d), tg0,
+                         flops=8.0 * Nf * nu * nu + 1.0 * nu ** 3,
+                         note="the two solves and three nu x nu x N products of gpx_fitc_lml_grad, R = (B alpha) alpha^T + (B Y^T) Y "
+                              "by one fused rank-one pass (no diag(c) pass); five runs each: gpx_vfe_grad %.2f..%.2f ms, "
+                              "gpx_fitc_lml_grad %.2f..%.2f ms, ratio of the minima %.3f"
+                              % (1e3 * tg0, 1e3 * tg1, 1e3 * tf0, 1e3 * tf1, tg0 / tf0)))
+    mv.grad(sp, yf, want_inducing=True)
+    (ts0, ts1), (tfs0, tfs1) = (spread(lambda: mv.grad(sp, yf, want_inducing=True)),
+                                spread(lambda: m.lml_grad(sp, yf, want_inducing=True)))
+    vlines.append(report("gpx_vfe_grad (with dF/dS)", "none in the reference", dict(N=Nf, nu=nu, d=d, kernel="ARD-SE", nlen=d), ts0,
+                         flops=8.0 * Nf * nu * nu + 1.0 * nu ** 3,
+                         note="gpx_vfe_grad plus dF/dS (nu x d): the row-wise weighted pass of gpx_fitc_lml_grad_inducing; five runs "
+                              "each: %.2f..%.2f ms, gpx_fitc_lml_grad_inducing %.2f..%.2f ms, ratio of the minima %.3f; ratio to "
+                              "gpx_vfe_grad %.3f" % (1e3 * ts0, 1e3 * ts1, 1e3 * tfs0, 1e3 * tfs1, ts0 / tfs0, ts0 / tg0)))
+    Mz = 4096 if quick else 16384
+    Zd = dev.points(ctx, rng.uniform(-1, 1, (Mz, d)))
+    cv, cf_ = mv.solve(yf)[0], m.solve(yf)[0]
+    mv.posterior(cv, Zd); m.posterior(cf_, Zd)             # warm: pools
+    (tp0, tp1), (tq0, tq1) = spread(lambda: mv.posterior(cv, Zd)), spread(lambda: m.posterior(cf_, Zd))
+    fv, ff = 2.0 * nu * nu * Mz, 2.0 * nu * Nf * Mz + 1.0 * nu * nu * Mz
+    vlines.append(report("gpx_vfe_posterior", "none in the reference", dict(N=Nf, nu=nu, M=Mz, d=d), tp0, flops=fv,
+                         note="mean and variance: two nu x M fills, two left solves of order nu (nu^2 M each), two column sums of "
+                              "squares, one weighted column sum; five runs: %.2f..%.2f ms.  gpx_fitc_posterior at the same M in this "
+                              "run (one M x N fill, the M x nu x N product 2 nu N M, one right solve nu^2 M = %.3e flop): "
+                              "%.2f..%.2f ms, %.1f TF/s; ratio of the minima %.4f (roofline count ratio %.4f)"
+                              % (1e3 * tp0, 1e3 * tp1, ff, 1e3 * tq0, 1e3 * tq1, ff / tq0 / 1e12, tp0 / tq0, fv / ff)))
+    del mv
+    out_vfe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vfe_frows.jsonl")
+    if "--vfe-out" in sys.argv:
+        out_vfe = sys.argv[sys.argv.index("--vfe-out") + 1]
+    with open(out_vfe, "a") as f:
+        for line in vlines:
+            f.write(json.dumps(line) + "\n")
 # ---- f2: refit of the changed rows
 if want("refit"):
     Nr = 4096 if quick else 16384
