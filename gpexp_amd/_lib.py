@@ -62,6 +62,10 @@ _SIGS = {
     "gpx_vfe_bound": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),
     "gpx_vfe_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp, c_dp]),
     "gpx_vfe_posterior": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_dp]),
+    "gpx_vfe_acq": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, c_dp, c_ip, c_dp]),
+    "gpx_vfe_acq_grad": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, c_dp, c_dp]),
+    "gpx_vfe_acq_batch": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, c_i64, c_ip,
+                                    c_dp, c_dp, c_dp]),
     "gpx_potrs_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gpx_logdet": (C.c_int, [c_vp, c_vp, c_dp]),
     "gpx_potri": (C.c_int, [c_vp, c_vp, C.POINTER(c_vp)]),

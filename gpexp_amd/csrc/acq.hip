@@ -21,6 +21,8 @@
 //     Matern32  dk/dz   = -sig (3 / rho^2) e^-t (z - x)             t = sqrt(3) |z - x| / rho
 //     Matern52  dk/dz   = -sig (5 / (3 rho^2)) (1 + t) e^-t (z - x)  t = sqrt(5) |z - x| / rho
 // all smooth at z = x.  Where var == 0 exactly, a and b are NaN, and so is the gradient row.
+// The same three calls on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad, gpx_vfe_acq_batch) are at the end of this file: the cost
+// formula, the epilogue, the arg-min and -- as further instantiations -- the gradient, pick and batch kernels are these.
 #include "gpx_device.h"
 #include <math.h>
 
@@ -60,8 +62,9 @@ __device__ __forceinline__ double acq_cost(int acq, double param, double mu, dou
   return c;
 }
 
-// values epilogue of one chunk [j0, j0 + mc): var = kd - ssq, the cost (written to cost[j0 + j]), the gradient coefficients
-// (a, b) per candidate of the chunk (coef, nullable) and one arg-min partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].
+// values epilogue of one chunk [j0, j0 + mc): var = kd - ssq (ssq == NULL: kd IS the signed variance -- the VFE predictor's), the
+// cost (written to cost[j0 + j]), the gradient coefficients (a, b) per candidate of the chunk (coef, nullable) and one arg-min
+// partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].
 __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double param, const double* __restrict__ mean,
                                                                const double* __restrict__ kd, const double* __restrict__ ssq,
                                                                int64_t mc, int64_t j0, double* __restrict__ cost,
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double p
   VI v{0.0, -1};
   if (j < mc) {
     double a, b;
-    const double c = acq_cost(acq, param, mean[j], kd[j] - ssq[j], &a, &b);
+    const double c = acq_cost(acq, param, mean[j], ssq ? kd[j] - ssq[j] : kd[j], &a, &b);
     cost[j0 + j] = c;
     if (coef) {
       coef[2 * j] = a;
@@ -109,11 +112,14 @@ __global__ __launch_bounds__(256) void acq_argmin_kernel(const double* __restric
 //     SE   f = k(z, x_j),              const_l = 1 / cl_l^2 = scale_l^2
 //     M32  f = e^-t,                   const   = sig scale^2
 //     M52  f = (1 + t) e^-t,           const   = sig scale^2 / 3
-template <int KIND, int DMAX>
+// TWO (gpx_vfe_acq_grad): X = the inducing points, alpha = beta_u, and the weight of b is gamma = betaT - betaT2, the difference of
+// the two transposed backward solves (Quu^-1 k_u and A^-1 k_u, row m each), taken here: gamma is never stored.
+template <int KIND, int DMAX, bool TWO>
 __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double* __restrict__ X, int64_t n,
                                                        const double* __restrict__ Zc, const double* __restrict__ betaT,
-                                                       int64_t ldt, const double* __restrict__ alpha,
-                                                       const double* __restrict__ coef, double* __restrict__ out) {
+                                                       const double* __restrict__ betaT2, int64_t ldt,
+                                                       const double* __restrict__ alpha, const double* __restrict__ coef,
+                                                       double* __restrict__ out) {
   __shared__ double red[256];
   const int64_t mm = blockIdx.x;
   const int d = kp.d, t = threadIdx.x;
@@ -125,10 +131,12 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double*
     s1[l] = 0.0;
   }
   const double* __restrict__ bt = betaT + mm * ldt;
+  const double* __restrict__ bt2 = TWO ? betaT2 + mm * ldt : nullptr;
   for (int64_t j = t; j < n; j += 256) {
     double diff[DMAX];
     const double f = radial_pair<KIND, DMAX>(kp, X + j * d, zs, diff);   // diff = x_j - z
-    const double w = fma(ca, alpha[j], cb * bt[j]) * f;
+    const double bj = TWO ? bt[j] - bt2[j] : bt[j];
+    const double w = fma(ca, alpha[j], cb * bj) * f;
 #pragma unroll
     for (int l = 0; l < DMAX; ++l) s1[l] = fma(w, diff[l], s1[l]);
   }
@@ -145,11 +153,19 @@ __global__ __launch_bounds__(256) void acq_grad_kernel(KParams kp, const double*
   }
 }
 
+// betaT2 == NULL: the dense instantiation; else the VFE one (TWO)
 int launch_acq_grad(gpx_ctx* ctx, const KParams& kp, const double* X, int64_t n, const double* Zc, int64_t mc,
-                    const double* betaT, int64_t ldt, const double* alpha, const double* coef, double* out) {
-#define GPX_CALL(K_, DM_)                                                                                                 \
-  hipLaunchKernelGGL((acq_grad_kernel<K_, DM_>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X, n, Zc, betaT, ldt, \
-                     alpha, coef, out)
+                    const double* betaT, const double* betaT2, int64_t ldt, const double* alpha, const double* coef,
+                    double* out) {
+#define GPX_CALL(K_, DM_)                                                                                                     \
+  do {                                                                                                                        \
+    if (betaT2)                                                                                                               \
+      hipLaunchKernelGGL((acq_grad_kernel<K_, DM_, true>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X, n, Zc, betaT, \
+                         betaT2, ldt, alpha, coef, out);                                                                      \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((acq_grad_kernel<K_, DM_, false>), dim3((unsigned)mc), dim3(256), 0, ctx->stream, kp, X, n, Zc, betaT, \
+                         betaT2, ldt, alpha, coef, out);                                                                      \
+  } while (0)
   GPX_RADIAL_DISPATCH(kp.kind, kp.d, GPX_CALL);
 #undef GPX_CALL
   GPX_HIP(hipGetLastError());
@@ -216,7 +232,7 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     else GPX_TRY(chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np));
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
                  8.0 * ((double)n * (double)mc + (double)n * d));
-    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, np, pal, pcoef, pgrad + j0 * d));
+    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, nullptr, np, pal, pcoef, pgrad + j0 * d));
   }
   if (best || best_cost) {
     ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
@@ -260,6 +276,8 @@ __global__ __launch_bounds__(256) void acq_batch_v_kernel(const double* __restri
 
 // pick `cur` = candidate s: its column of W_C (w, np), its coordinates along the earlier picks (uc, cur), the pick's scalars,
 // and the mask.  Reads mu / v / U only: the state is changed by the NEXT acq_batch_kernel.
+// VFE (gpx_vfe_acq_batch): Wc = Wa (nup rows), v = t, delta = noise + t_s -- never tiny, the pick is always live; kd is not read.
+template <bool VFE>
 __global__ __launch_bounds__(256) void acq_pick_kernel(const double* __restrict__ Wc, int64_t ld, int64_t np, int64_t s,
                                                        const double* __restrict__ U, int64_t ldu, int cur,
                                                        const double* __restrict__ mu, const double* __restrict__ v,
@@ -270,13 +288,13 @@ __global__ __launch_bounds__(256) void acq_pick_kernel(const double* __restrict_
   if (i < np) w[i] = Wc[i * ld + s];
   if (i < cur) uc[i] = U[i * ldu + s];
   if (i == 0) {
-    const double delta = v[s] + noise, mus = mu[s];
+    const double delta = VFE ? noise + v[s] : v[s] + noise, mus = mu[s];
     const double ys = lie == GPX_LIE_BELIEVER ? mus : lie_value;
     sc[SC_DELTA] = delta;
     sc[SC_MU] = mus;
     sc[SC_LIE] = ys;
     if (track_best && ys > sc[SC_PARAM]) sc[SC_PARAM] = ys;
-    sc[SC_LIVE] = delta > 1e-13 * kd[s] ? 1.0 : 0.0;
+    sc[SC_LIVE] = VFE || delta > 1e-13 * kd[s] ? 1.0 : 0.0;
     mask[s] = 1;
   }
 }
@@ -284,11 +302,15 @@ __global__ __launch_bounds__(256) void acq_pick_kernel(const double* __restrict_
 // One pass over the candidates: (upd) condition mu, v on the pick `cur` = candidate s and store its row U[cur]; then the costs
 // under the mask (NaN for a picked candidate) and one arg-min partial per block.  Only j < M is touched: the padding columns of
 // W_C / U never enter a result.
+// VFE (gpx_vfe_acq_batch): hdot = Wa[:, s]^T Wa enters with the opposite sign and alone (no k(c_s, c_j): the observation acts through
+// the inducing variables), v holds t_j = |Wa[:, j]|^2 and the variance scored is rfix[j] + t_j.
+template <bool VFE>
 __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq, const double* __restrict__ Cp, int64_t M,
                                                             int upd, int64_t s, int cur, const double* __restrict__ sc,
                                                             const double* __restrict__ uc, const double* __restrict__ hdot,
                                                             double* __restrict__ U, int64_t ldu, double* __restrict__ mu,
-                                                            double* __restrict__ v, const int* __restrict__ mask,
+                                                            double* __restrict__ v, const double* __restrict__ rfix,
+                                                            const int* __restrict__ mask,
                                                             double* __restrict__ cost, double* __restrict__ part_c,
                                                             int64_t* __restrict__ part_i) {
   __shared__ double shc[ACQ_EPI];
@@ -301,7 +323,7 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
       double u = 0.0;
       if (sc[SC_LIVE] != 0.0) {   // (uniform)
         const double rs = 1.0 / sqrt(sc[SC_DELTA]);
-        double acc = kpair(kp, Cp + s * kp.d, Cp + j * kp.d) - hdot[j];
+        double acc = VFE ? hdot[j] : kpair(kp, Cp + s * kp.d, Cp + j * kp.d) - hdot[j];
         for (int r = 0; r < cur; ++r) acc = fma(-uc[r], U[(int64_t)r * ldu + j], acc);
         u = acc * rs;
         m = fma(u, (sc[SC_LIE] - sc[SC_MU]) * rs, m);
@@ -312,7 +334,7 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
       U[(int64_t)cur * ldu + j] = u;
     }
     double a, b;
-    double c = acq_cost(acq, sc[SC_PARAM], m, var, &a, &b);
+    double c = acq_cost(acq, sc[SC_PARAM], m, VFE ? rfix[j] + var : var, &a, &b);
     if (mask[j]) c = __builtin_nan("");
     cost[j] = c;
     if (c == c) best = VI{c, j};
@@ -390,9 +412,9 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
   for (int64_t t = 0; t < q; ++t) {
     {
       ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
-      hipLaunchKernelGGL(acq_batch_kernel, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M, t > 0 ? 1 : 0,
-                         s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
-                         (const int*)pmask, pcost, ppc, ppi);
+      hipLaunchKernelGGL(acq_batch_kernel<false>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M,
+                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
+                         (const double*)nullptr, (const int*)pmask, pcost, ppc, ppi);
       hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
                          pbc, pbi);
     }
@@ -409,7 +431,7 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
     out_idx[t] = s;
     if (out_cost) out_cost[t] = c;
     if (t + 1 == q && !out_lie) break;
-    hipLaunchKernelGGL(acq_pick_kernel, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
+    hipLaunchKernelGGL(acq_pick_kernel<false>, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
                        (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
                        psc, puc, pw, pmask);
     GPX_HIP(hipGetLastError());
@@ -421,6 +443,207 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
 }
 
 }  // namespace
+
+// ---- the same three calls on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad, gpx_vfe_acq_batch; argument checks: fitc.hip) -------------
+// Notation of fitc.hip: S the nu inducing points, Quu = K(S,S) + noise I = Lu Lu^T, A = Quu + Kuf Kfu / noise = La La^T,
+// beta_u = Quu^-1 Kuf alpha, k_u(z) = K(S, z);  mean = k_u^T beta_u,  var = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2.
+//
+// Values: vfe_posterior_chunk (gpx_vfe_posterior's own per-chunk step), then acq_epilogue_kernel on the signed variance it leaves and
+// acq_argmin_kernel.  Gradient, with (a, b) from that epilogue:
+//     gamma(z) = Quu^-1 k_u - A^-1 k_u,     grad_z A = sum_u dk(z, s_u)/dz (a beta_u[u] - 2 b gamma(z)[u])
+// The two forward solves of the values stay (Wu = Lu^-1 k_u, Wa = La^-1 k_u: FOUR nu x chunk buffers instead of two or three), each
+// is transposed and swept backward from the right (Wu^T Lu^-1, Wa^T La^-1: acq_impl's pattern, the nu-axis contiguous per
+// candidate; chol_trsm_right_n at every order -- no branch of its own at order 4096), and acq_grad_kernel<.., TWO> reads both
+// rows and takes their difference in its one pass over the inducing points.
+int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                 double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
+  FitcView fv;
+  fitc_view(f, &fv);
+  const int64_t nu = fv.nu, nup = fv.nup, M = Z->rows, d = fv.kp->d;
+  const bool grad = grad_host != nullptr;
+  KParams kpz = *fv.kp;   // the candidates may reach beyond the training domain
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
+  const int64_t mcmax = gpx_eval_chunk(nup);
+  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const bool oop = nup >= 2048;   // the predictor's rule
+  const int64_t bytesB = nup * gpx_skew_ld(mc_alloc) * 8, bytes_out = mc_alloc * 8;
+  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+  double *B1, *B2, *Wu = nullptr, *Wa = nullptr, *part, *pm, *su, *sa, *kd, *pv, *bu, *pcost, *ppc, *pbc;
+  double *pcoef = nullptr, *pgrad = nullptr;
+  int64_t *ppi, *pbi;
+  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
+  GPX_TRY(sc.get(bytesB, &B1));
+  GPX_TRY(sc.get(bytesB, &B2));
+  if (oop || grad) GPX_TRY(sc.get(bytesB, &Wu));
+  if (grad) GPX_TRY(sc.get(bytesB, &Wa));
+  GPX_TRY(sc.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
+  GPX_TRY(sc.get(bytes_out, &pm));
+  GPX_TRY(sc.get(bytes_out, &su));
+  GPX_TRY(sc.get(bytes_out, &sa));
+  GPX_TRY(sc.get(bytes_out, &kd));
+  GPX_TRY(sc.get(bytes_out, &pv));
+  GPX_TRY(sc.get(M * 8, &pcost));
+  GPX_TRY(sc.get(nparts * 8, &ppc));
+  GPX_TRY(sc.get(nparts * 8, &ppi));
+  GPX_TRY(sc.get(8, &pbc));
+  GPX_TRY(sc.get(8, &pbi));
+  if (grad) {
+    GPX_TRY(sc.get(2 * bytes_out, &pcoef));
+    GPX_TRY(sc.get(M * d * 8, &pgrad));
+  }
+  GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
+  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
+    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
+    const double* Zc = Z->p + j0 * d;
+    // values only: both out-of-place solutions land in the one buffer, as in gpx_vfe_posterior
+    GPX_TRY(vfe_posterior_chunk(ctx, f, kpz, S, Zc, mc, B1, B2, oop ? Wu : nullptr, oop ? (grad ? Wa : Wu) : nullptr, bu, pm, su,
+                                sa, kd, pv, part));
+    {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 4.0 * (double)mc);
+      hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
+                         param, (const double*)pm, (const double*)pv, (const double*)nullptr, mc, j0, pcost, pcoef, ppc, ppi);
+      GPX_HIP(hipGetLastError());
+    }
+    if (!grad) continue;
+    // (Quu^-1 k_u)^T = Wu^T Lu^-1 and (A^-1 k_u)^T = Wa^T La^-1 (mcp x nup, row stride nup), in the two buffers the forward
+    // solutions do not occupy
+    const double *solU = oop ? Wu : B1, *solA = oop ? Wa : B2;
+    double *Tu = oop ? B1 : Wu, *Ta = oop ? B2 : Wa;
+    GPX_TRY(launch_transpose(ctx, solU, nup, mcp, ldb, Tu, nup));
+    GPX_TRY(chol_trsm_right_n(ctx, fv.Lu->p, fv.Lu->ld, fv.Lu->aux, Tu, nup, mcp, nup));
+    GPX_TRY(launch_transpose(ctx, solA, nup, mcp, ldb, Ta, nup));
+    GPX_TRY(chol_trsm_right_n(ctx, fv.La->p, fv.La->ld, fv.La->aux, Ta, nup, mcp, nup));
+    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nu * (double)mc * (6.0 * (double)d + 26.0),
+                 8.0 * (2.0 * (double)nu * (double)mc + (double)nu * d));
+    GPX_TRY(launch_acq_grad(ctx, kpz, S->p, nu, Zc, mc, Tu, Ta, nup, bu, pcoef, pgrad + j0 * d));
+  }
+  if (best || best_cost) {
+    ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
+    hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                       pbc, pbi);
+    GPX_HIP(hipGetLastError());
+    if (best) GPX_HIP(hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (grad_host) GPX_HIP(hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
+}
+
+// q-point batch on a VFE model whose inducing points and hyper-parameters stay fixed.  One more observation at c_s changes A to
+// A + k_u(c_s) k_u(c_s)^T / noise and nothing else (Quu, and with it r_j = k(c_j,c_j) - |Lu^-1 k_u(c_j)|^2, stays), so the refit is a
+// rank-one recurrence in the inducing space.  State: Wa = La^-1 K(S, C) (nup x Mp, the only matrix kept), mu, r, t_j = |Wa[:, j]|^2,
+// the rows U[t].  Per pick
+//     v_j = r_j + t_j;   delta = noise + t_s  (NOT v_s + noise);   y_s = mu_s (believer) or the caller's constant
+//     u_j = (Wa[:, s]^T Wa[:, j] - sum_{r<t} U[r][s] U[r][j]) / sqrt(delta),   U[t] = u
+//     mu_j += u_j (y_s - mu_s) / sqrt(delta),   t_j -= u_j^2,   param = max(param, y_s) when track_best
+// delta >= noise > 0 (gpx_vfe_fit refuses noise <= 0): the tiny-pivot rule of the dense path (delta <= 1e-13 k(c_s, c_s): u = 0) has
+// no counterpart here, every pick conditions.  The only nu x M pass per pick is h = Wa[:, s]^T Wa (launch_colreduce, fixed order);
+// acq_pick_kernel<true> / acq_batch_kernel<true> do the rest.  The set-up walks the candidates in gpx_vfe_acq's chunks with
+// gpx_vfe_acq's launches, so row 0 of the costs holds its bits; the Lu solve of a chunk is transient (one nup x chunk buffer; out of
+// place it lands in the chunk's columns of Wa, which the La solve then overwrites).
+int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
+                       double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
+                       double* out_lie, double* all_costs) {
+  FitcView fv;
+  fitc_view(f, &fv);
+  const int64_t nu = fv.nu, nup = fv.nup, M = Cm->rows, d = fv.kp->d;
+  const int64_t Mp = gpx_round_up(M, GPX_TILE), ld = gpx_skew_ld(Mp);
+  KParams kpz = *fv.kp;
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Cm));
+  const bool oop = nup >= 2048;
+  const int64_t mcmax = gpx_eval_chunk(nup);
+  const int64_t mcw = Mp < mcmax ? Mp : mcmax, ldb = gpx_skew_ld(mcw);
+  const int64_t bytesM = Mp * 8;
+  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+  const int64_t nw = nup > q ? nup : q;
+  double *pW, *pB, *pU, *bu, *pmu, *pt, *pr, *pkd, *phd, *ppart, *pcost, *ppc, *pbc, *psc, *puc, *pw;
+  int64_t *ppi, *pbi;
+  int* pmask;
+  Scratch sc(ctx);
+  const dim3 gEpi((unsigned)nparts), gPick((unsigned)((nw + 255) / 256));
+  GPX_TRY(sc.get(nup * ld * 8, &pW));
+  GPX_TRY(sc.get(nup * ldb * 8, &pB));
+  GPX_TRY(sc.get(q * Mp * 8, &pU));
+  GPX_TRY(sc.get(bytesM, &pmu));
+  GPX_TRY(sc.get(bytesM, &pt));
+  GPX_TRY(sc.get(bytesM, &pr));
+  GPX_TRY(sc.get(bytesM, &pkd));
+  GPX_TRY(sc.get(bytesM, &phd));    // |Lu^-1 k_u|^2 at the set-up, then h of every pick
+  GPX_TRY(sc.get(colreduce_partial_elems(nup, Mp) * 8 + 8, &ppart));
+  GPX_TRY(sc.get(M * 8, &pcost));
+  GPX_TRY(sc.get(nparts * 8, &ppc));
+  GPX_TRY(sc.get(nparts * 8, &ppi));
+  GPX_TRY(sc.get(8, &pbc));
+  GPX_TRY(sc.get(8, &pbi));
+  GPX_TRY(sc.get(SC_N * 8, &psc));
+  GPX_TRY(sc.get(q * 8, &puc));
+  GPX_TRY(sc.get(nw * 8, &pw));
+  GPX_TRY(sc.get(Mp * 4, &pmask));
+  GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
+  double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
+  GPX_HIP(hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream));
+  // ---- set-up: gpx_vfe_acq's chunks.  Not vfe_posterior_chunk: the La solve lands in the resident Wa with ITS row stride ----
+  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
+    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
+    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldc = gpx_skew_ld(mcp);
+    const double* Cc = Cm->p + j0 * d;
+    double* Wc = pW + j0;
+    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, pB, nup, mcp, ldc));
+    GPX_TRY(launch_colreduce(ctx, pB, ldc, nu, mcp, bu, pmu + j0, ppart));
+    if (oop) {
+      GPX_TRY(chol_trsm_left_oop(ctx, fv.Lu, pB, ldc, Wc, ld, mcp));
+      GPX_TRY(launch_colreduce(ctx, Wc, ld, nu, mcp, nullptr, phd + j0, ppart));
+      GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, pB, nup, mcp, ldc));
+      GPX_TRY(chol_trsm_left_oop(ctx, fv.La, pB, ldc, Wc, ld, mcp));
+    } else {
+      GPX_TRY(chol_trsm_left(ctx, fv.Lu->p, fv.Lu->ld, fv.Lu->aux, pB, ldc, nup, mcp));
+      GPX_TRY(launch_colreduce(ctx, pB, ldc, nu, mcp, nullptr, phd + j0, ppart));
+      GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, Wc, nup, mcp, ld));
+      GPX_TRY(chol_trsm_left(ctx, fv.La->p, fv.La->ld, fv.La->aux, Wc, ld, nup, mcp));
+    }
+    GPX_TRY(launch_colreduce(ctx, Wc, ld, nu, mcp, nullptr, pt + j0, ppart));
+    GPX_TRY(launch_kdiag(ctx, *fv.kp, Cc, mc, pkd + j0));
+  }
+  hipLaunchKernelGGL(acq_batch_v_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
+                     (const double*)phd, M, pr);
+  GPX_HIP(hipGetLastError());
+  // ---- the picks ----
+  int64_t s = -1;
+  for (int64_t t = 0; t < q; ++t) {
+    {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
+      hipLaunchKernelGGL(acq_batch_kernel<true>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kpz, acq, (const double*)Cm->p, M,
+                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)phd, pU, Mp, pmu,
+                         pt, (const double*)pr, (const int*)pmask, pcost, ppc, ppi);
+      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
+                         pbc, pbi);
+    }
+    double c = 0.0;
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (all_costs) GPX_HIP(hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipStreamSynchronize(ctx->stream));
+    if (s < 0 || s >= M) {
+      gpx_set_error("vfe acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
+      return -1;
+    }
+    out_idx[t] = s;
+    if (out_cost) out_cost[t] = c;
+    if (t + 1 == q && !out_lie) break;
+    hipLaunchKernelGGL(acq_pick_kernel<true>, gPick, dim3(256), 0, ctx->stream, (const double*)pW, ld, nup, s, (const double*)pU,
+                       Mp, (int)t, (const double*)pmu, (const double*)pt, (const double*)nullptr, fv.noise, lie, lie_value,
+                       track_best, psc, puc, pw, pmask);
+    GPX_HIP(hipGetLastError());
+    if (out_lie) GPX_HIP(hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (t + 1 == q) break;
+    GPX_TRY(launch_colreduce(ctx, pW, ld, nu, Mp, pw, phd, ppart));
+  }
+  return 0;
+}
 
 extern "C" {
 

@@ -74,6 +74,9 @@
 //     mean(z) = k_u^T beta_u,  beta_u = Quu^-1 (Kuf alpha);      var(z) = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2
 // per chunk of candidates one nu x M fill (two with the variance: each solve consumes its right-hand side), two left solves of
 // order nu, two column sums of squares, one weighted column sum and vfe_var_kernel; one device-to-host copy per output per chunk.
+// That per-chunk step is vfe_posterior_chunk, shared with the acquisition costs on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad: their
+// bodies and gpx_vfe_acq_batch's are in acq.hip beside the kernels they share with the dense calls; the entries and their argument
+// checks are here, where the struct is).
 #include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
@@ -619,6 +622,52 @@ int64_t fitc_n(const gpx_fitc* f) { return f->n; }
 int64_t fitc_np(const gpx_fitc* f) { return f->np; }
 int64_t fitc_nup(const gpx_fitc* f) { return f->nup; }
 int fitc_is_vfe(const gpx_fitc* f) { return f->vfe; }
+void fitc_view(const gpx_fitc* f, FitcView* v) { *v = FitcView{&f->kp, f->n, f->nu, f->np, f->nup, f->noise, f->Lu, f->La}; }
+
+// beta_u = Quu^-1 (Kuf alpha): one row reduction over Kuf and both sweeps against chol(Quu); 0 on the padding
+int vfe_beta_u(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& tmp, double** bu_out) {
+  const int64_t np = f->np, nup = f->nup;
+  double *dc, *bu, *ps;
+  GPX_TRY(tmp.get(np * 8, &dc));
+  GPX_TRY(tmp.get(nup * 8, &bu));
+  GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
+  GPX_HIP(hipMemsetAsync(dc, 0, (size_t)np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(dc, coeff, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(launch_rowreduce(ctx, f->Kuf->p, f->Kuf->ld, f->nu, np, dc, bu));
+  GPX_TRY(chol_potrs(ctx, f->Lu, bu, ps));
+  *bu_out = bu;
+  return 0;
+}
+
+// (gpx_internal.h: the contract)
+int vfe_posterior_chunk(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kpz, const gpx_mat* S, const double* Zc, int64_t mc,
+                        double* B1, double* B2, double* Wu, double* Wa, const double* bu, double* pm, double* su, double* sa,
+                        double* kd, double* pv, double* part) {
+  const int64_t nu = f->nu, nup = f->nup;
+  const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
+  GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B1, nup, mcp, ldb));
+  if (bu) GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, bu, pm, part));
+  if (!B2) return 0;
+  // each solve consumes its right-hand side: a second fill (cheaper than a copy, as in the fit)
+  GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B2, nup, mcp, ldb));
+  if (Wu) {
+    GPX_TRY(chol_trsm_left_oop(ctx, f->Lu, B1, ldb, Wu, ldb, mcp));
+    GPX_TRY(launch_colreduce(ctx, Wu, ldb, nu, mcp, nullptr, su, part));
+    GPX_TRY(chol_trsm_left_oop(ctx, f->La, B2, ldb, Wa, ldb, mcp));
+    GPX_TRY(launch_colreduce(ctx, Wa, ldb, nu, mcp, nullptr, sa, part));
+  } else {
+    GPX_TRY(chol_trsm_left(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, B1, ldb, nup, mcp));
+    GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, nullptr, su, part));
+    GPX_TRY(chol_trsm_left(ctx, f->La->p, f->La->ld, f->La->aux, B2, ldb, nup, mcp));
+    GPX_TRY(launch_colreduce(ctx, B2, ldb, nu, mcp, nullptr, sa, part));
+  }
+  GPX_TRY(launch_kdiag(ctx, f->kp, Zc, mc, kd));
+  hipLaunchKernelGGL(vfe_var_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)kd,
+                     (const double*)su, (const double*)sa, mc, pv);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
 
 // beta^T = (P B)^T for B = np x mcp right-hand sides (row stride mcp; K(X, Z) of one chunk of evaluation points) under the
 // Woodbury precision P = Gi - Ks^T A^-1 Ks (Ks = -Kuf Gi, A = La La^T): the point-derivative routines of the reference read
@@ -1242,7 +1291,7 @@ int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
   GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
           "point sets do not match");
   GPX_ARG(mean == nullptr || coeff != nullptr, "coeff is required for the mean");
-  const int64_t M = Z->rows, d = f->kp.d, n = f->n, nu = f->nu, np = f->np, nup = f->nup;
+  const int64_t M = Z->rows, d = f->kp.d, nup = f->nup;
   if (M == 0 || (!mean && !var)) return 0;
   KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
@@ -1253,7 +1302,7 @@ int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
   const bool oop = var && nup >= 2048;
   Scratch tmp(ctx);   // its scope exit is the synchronisation the host results wait for
   double *B1, *B2 = nullptr, *Wo = nullptr, *part, *pm = nullptr, *su = nullptr, *sa = nullptr, *kd = nullptr, *pv = nullptr;
-  double *dc = nullptr, *bu = nullptr, *ps = nullptr;
+  double* bu = nullptr;
   GPX_TRY(tmp.get(nup * ldb_alloc * 8, &B1));
   GPX_TRY(tmp.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
   if (var) {
@@ -1265,48 +1314,62 @@ int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
     GPX_TRY(tmp.get(mc_alloc * 8, &pv));
   }
   if (mean) {
-    // beta_u = Quu^-1 (Kuf alpha): one row reduction over Kuf and both sweeps against chol(Quu); 0 on the padding
     GPX_TRY(tmp.get(mc_alloc * 8, &pm));
-    GPX_TRY(tmp.get(np * 8, &dc));
-    GPX_TRY(tmp.get(nup * 8, &bu));
-    GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
-    GPX_HIP(hipMemsetAsync(dc, 0, (size_t)np * 8, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(dc, coeff, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
-    GPX_TRY(launch_rowreduce(ctx, f->Kuf->p, f->Kuf->ld, nu, np, dc, bu));
-    GPX_TRY(chol_potrs(ctx, f->Lu, bu, ps));
+    GPX_TRY(vfe_beta_u(ctx, f, coeff, tmp, &bu));
   }
   for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
     const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
-    const double* Zc = Z->p + j0 * d;
-    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B1, nup, mcp, ldb));
-    if (mean) {
-      GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, bu, pm, part));
-      GPX_HIP(hipMemcpyAsync(mean + j0, pm, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (!var) continue;
-    // each solve consumes its right-hand side: a second fill (cheaper than a copy, as in the fit)
-    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B2, nup, mcp, ldb));
-    if (oop) {
-      GPX_TRY(chol_trsm_left_oop(ctx, f->Lu, B1, ldb, Wo, ldb, mcp));
-      GPX_TRY(launch_colreduce(ctx, Wo, ldb, nu, mcp, nullptr, su, part));
-      GPX_TRY(chol_trsm_left_oop(ctx, f->La, B2, ldb, Wo, ldb, mcp));
-      GPX_TRY(launch_colreduce(ctx, Wo, ldb, nu, mcp, nullptr, sa, part));
-    } else {
-      GPX_TRY(chol_trsm_left(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, B1, ldb, nup, mcp));
-      GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, nullptr, su, part));
-      GPX_TRY(chol_trsm_left(ctx, f->La->p, f->La->ld, f->La->aux, B2, ldb, nup, mcp));
-      GPX_TRY(launch_colreduce(ctx, B2, ldb, nu, mcp, nullptr, sa, part));
-    }
-    GPX_TRY(launch_kdiag(ctx, f->kp, Zc, mc, kd));
-    hipLaunchKernelGGL(vfe_var_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)kd,
-                       (const double*)su, (const double*)sa, mc, pv);
-    GPX_HIP(hipGetLastError());
-    GPX_HIP(hipMemcpyAsync(var + j0, pv, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_TRY(vfe_posterior_chunk(ctx, f, kpz, S, Z->p + j0 * d, mc, B1, B2, Wo, Wo, bu, pm, su, sa, kd, pv, part));
+    if (mean) GPX_HIP(hipMemcpyAsync(mean + j0, pm, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (var) GPX_HIP(hipMemcpyAsync(var + j0, pv, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   GPX_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+// The argument rules of gpx_vfe_acq / gpx_vfe_acq_grad / gpx_vfe_acq_batch (their bodies: acq.hip)
+static int vfe_acq_args(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq,
+                        const char* what) {
+  GPX_ARG(ctx && f && S && Z && coeff, "NULL argument");
+  FITC_KIND(f, true, what, "the batched acquisition costs are offered on VFE models only");
+  GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
+  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
+          "point sets do not match");
+  return 0;
+}
+
+int gpx_vfe_acq(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                double* cost, int64_t* best, double* best_cost) {
+  GPX_TRY(vfe_acq_args(ctx, f, S, coeff, Z, acq, "vfe_acq"));
+  if (Z->rows == 0) {
+    if (best) *best = -1;
+    if (best_cost) *best_cost = __builtin_nan("");
+    return 0;
+  }
+  return vfe_acq_impl(ctx, f, S, coeff, Z, acq, param, cost, best, best_cost, nullptr);
+}
+
+int gpx_vfe_acq_grad(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                     double* cost, double* grad) {
+  GPX_ARG(grad != nullptr, "grad is NULL");
+  GPX_TRY(vfe_acq_args(ctx, f, S, coeff, Z, acq, "vfe_acq_grad"));
+  FITC_ARG(f->kp.kind == GPX_K_SE || f->kp.kind == GPX_K_MATERN32 || f->kp.kind == GPX_K_MATERN52, "vfe_acq_grad",
+           "acquisition gradients exist for the stationary kernels (SE, Matern 3/2, Matern 5/2) only: the Mehler kernel's "
+           "prior variance depends on the point");
+  if (Z->rows == 0) return 0;
+  return vfe_acq_impl(ctx, f, S, coeff, Z, acq, param, cost, nullptr, nullptr, grad);
+}
+
+int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* C, int acq, double param,
+                      int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie,
+                      double* all_costs) {
+  GPX_ARG(out_idx != nullptr, "out_idx is NULL");
+  GPX_ARG(lie == GPX_LIE_BELIEVER || lie == GPX_LIE_CONSTANT, "lie must be GPX_LIE_BELIEVER or GPX_LIE_CONSTANT");
+  GPX_TRY(vfe_acq_args(ctx, f, S, coeff, C, acq, "vfe_acq_batch"));
+  GPX_ARG(q >= 1, "need at least one pick");
+  GPX_ARG(q <= C->rows, "more picks than candidates");
+  return vfe_acq_batch_impl(ctx, f, S, coeff, C, acq, param, track_best != 0, lie, lie_value, q, out_idx, out_cost, out_lie,
+                            all_costs);
 }
 
 // Dense Q + G and P (host, n x n row-major, each nullable): the reference's covarianceMatrix / precisionMatrix attributes.

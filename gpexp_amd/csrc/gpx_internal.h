@@ -437,6 +437,32 @@ int64_t fitc_np(const gpx_fitc* f);
 int64_t fitc_nup(const gpx_fitc* f);
 int fitc_is_vfe(const gpx_fitc* f);   // 1: fitted by gpx_vfe_fit (the FITC-only entries refuse it)
 int fitc_solve_beta_t(gpx_ctx* ctx, const gpx_fitc* f, const double* B, int64_t mcp, double* Bt, double* U);
+// fitc.hip: what acq.hip needs of a VFE model
+struct FitcView {
+  const KParams* kp;
+  int64_t n, nu, np, nup;
+  double noise;
+  gpx_mat *Lu, *La;
+};
+void fitc_view(const gpx_fitc* f, FitcView* v);
+// *bu (nup doubles from `tmp`, 0 on the padding) = beta_u = Quu^-1 (Kuf coeff); coeff: host, n
+int vfe_beta_u(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& tmp, double** bu);
+// One chunk Zc (mc points) of the VFE predictor -- the ONE sequence behind gpx_vfe_posterior, gpx_vfe_acq and gpx_vfe_acq_grad, so
+// that their values agree by construction.  With mcp = mc rounded up to 128 and row stride gpx_skew_ld(mcp):
+//   B1 = K(S, Zc) (nup x mcp);   pm = B1^T bu   (bu == NULL: no mean);   B2 == NULL: the mean only.  Else B2 = K(S, Zc) again (each
+//   solve consumes its right-hand side), Lu^-1 B1 and La^-1 B2 in place (Wu == NULL) or through the block inverses into Wu and Wa
+//   (which may be ONE buffer when the solutions are not wanted afterwards);   su, sa = their column sums of squares;
+//   kd = k(z, z);   pv = (kd - su) + sa.
+// kpz: the model's kernel re-centred on S and Z.  Asynchronous.
+int vfe_posterior_chunk(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kpz, const gpx_mat* S, const double* Zc, int64_t mc,
+                        double* B1, double* B2, double* Wu, double* Wa, const double* bu, double* pm, double* su, double* sa,
+                        double* kd, double* pv, double* part);
+// acq.hip: the bodies of gpx_vfe_acq / gpx_vfe_acq_grad (grad_host != NULL) and gpx_vfe_acq_batch, behind fitc.hip's argument checks
+int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                 double* cost_host, int64_t* best, double* best_cost, double* grad_host);
+int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
+                       double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
+                       double* out_lie, double* all_costs);
 
 // reduce.hip
 // out[j] = sum_i B[i][j] * v[i]   (v == nullptr: sum_i B[i][j]^2), i < rows, j < pcols; deterministic

@@ -428,6 +428,41 @@ class VfeModel(FitcModel):
         check(self.ctx.lib.gpx_vfe_posterior(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, dptr(mean), dptr(var)))
         return mean, var
 
+    def acq(self, coeff, Z, kind, param, want_costs=True):
+        """Bayesian-optimisation costs of the M candidates Z on this model (gpx_vfe_acq), coeff = alpha from `solve`: what `acq`
+        returns -- (first arg-min among the non-NaN costs or -1, its cost, costs (M,) or None)."""
+        costs = np.empty(Z.shape[0]) if want_costs else None
+        best, best_cost = c_i64(), C.c_double()
+        co = as_f64(coeff) if coeff is not None else None
+        check(self.ctx.lib.gpx_vfe_acq(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, int(kind), float(param), dptr(costs),
+                                       C.byref(best), C.byref(best_cost)))
+        return best.value, best_cost.value, costs
+
+    def acq_grad(self, coeff, Z, kind, param):
+        """(costs (M,), d cost_m / d z_m (M, d)) of the M candidates Z (gpx_vfe_acq_grad); the costs hold `acq`'s bits."""
+        m, d = Z.shape
+        costs = np.empty(m)
+        grad = np.empty((m, d))
+        co = as_f64(coeff) if coeff is not None else None
+        check(self.ctx.lib.gpx_vfe_acq_grad(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, int(kind), float(param), dptr(costs),
+                                            dptr(grad)))
+        return costs, grad
+
+    def acq_batch(self, coeff, Cpts, kind, param, track_best, lie, lie_value, q, want_all=False):
+        """q picks of batch acquisition (gpx_vfe_acq_batch): every pick is scored on the model refitted, with the same inducing
+        points, on the data grown by the earlier picks' believed values.  What `acq_batch` returns: (indices (q,) int64, winner
+        costs (q,), believed values (q,)[, all costs q x M])."""
+        q = int(q)
+        idx = np.empty(max(q, 0), dtype=np.int64)
+        cost = np.empty(max(q, 0))
+        lies = np.empty(max(q, 0))
+        allc = np.empty((max(q, 0), Cpts.shape[0])) if want_all else None
+        co = as_f64(coeff) if coeff is not None else None
+        check(self.ctx.lib.gpx_vfe_acq_batch(self.ctx.h, self.h, self.S.h, dptr(co), Cpts.h, int(kind), float(param),
+                                             int(bool(track_best)), int(lie), float(lie_value), q, idx.ctypes.data_as(_lib.c_ip),
+                                             dptr(cost), dptr(lies), dptr(allc)))
+        return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
+
 
 def potrs(ctx, L, y):
     y = as_f64(y)

@@ -461,6 +461,38 @@ def firstMinIndex(costs):
     return int(ok[np.argmin(c[ok])])
 
 
+class _AcqCalls(object):
+    """The three batched device calls on the trained model of a GP, the model's own arguments bound -- the one place that tells
+    the model kinds apart:
+      dense  gpx_acq / gpx_acq_grad / gpx_acq_batch on the Cholesky factor, the training points and the coefficients;
+      VFE    VfeModel.acq / acq_grad / acq_batch on the device model (its inducing points are the model's) and the coefficients;
+      FITC   none: `_costFuncBO._dense` raises NotImplementedError before one is asked for."""
+
+    def __init__(self, ctx, gp):
+        self.ctx, self.gp = ctx, gp
+        sparse = getattr(gp, "_fitc", None)
+        self.vfe = sparse if sparse is not None and gp._vfe() else None
+
+    def acq(self, Z, kind, param, want_costs=True):
+        gp = self.gp
+        if self.vfe is not None:
+            return self.vfe.acq(gp.coeff, Z, kind, param, want_costs=want_costs)
+        return _dev.acq(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, kind, param, want_costs=want_costs)
+
+    def acq_grad(self, Z, kind, param):
+        gp = self.gp
+        if self.vfe is not None:
+            return self.vfe.acq_grad(gp.coeff, Z, kind, param)
+        return _dev.acq_grad(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, kind, param)
+
+    def acq_batch(self, C, kind, param, track, lie, lieValue, q, want_all=False):
+        gp = self.gp
+        if self.vfe is not None:
+            return self.vfe.acq_batch(gp.coeff, C, kind, param, track, lie, lieValue, q, want_all=want_all)
+        return _dev.acq_batch(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, C, float(gp.noise), kind, param, track, lie,
+                              lieValue, q, want_all=want_all)
+
+
 class _costFuncBO(costFunctionBase):
     """Shared part of the three Bayesian-optimisation costs.
 
@@ -468,10 +500,11 @@ class _costFuncBO(costFunctionBase):
     on (xTrain, yTrain) -- the caller's GP is left untouched (the copy's refit replaces its handles, gp.py) -- and `evaluate` scores
     the LAST row of its argument only, through a single-row GP.evaluate(compvar=1) and scipy.stats.
 
-    Batched forms on the device (the new capability; dense models only -- a GP built with FITC=... raises NotImplementedError):
-      evaluateBatch(candidates)    (M,) costs                                gpx_acq
-      bestCandidate(candidates)    (first arg-min among the non-NaN costs or -1, its cost)   gpx_acq
-      derivativeBatch(candidates)  (M, d): row m = d cost_m / d candidate_m   gpx_acq_grad
+    Batched forms on the device (the new capability; dense models and VFE models, GP(..., FITC=fraction, sparse="vfe") -- a GP built
+    with FITC=... alone raises NotImplementedError):
+      evaluateBatch(candidates)    (M,) costs                                gpx_acq / gpx_vfe_acq
+      bestCandidate(candidates)    (first arg-min among the non-NaN costs or -1, its cost)   gpx_acq / gpx_vfe_acq
+      derivativeBatch(candidates)  (M, d): row m = d cost_m / d candidate_m   gpx_acq_grad / gpx_vfe_acq_grad
       derivative(trainPoints)      (d,): the gradient for the last row
     Under a multi-process launch these run replicated: every rank makes the same deterministic single-GPU call on the factor."""
 
@@ -497,8 +530,9 @@ class _costFuncBO(costFunctionBase):
 
     def _dense(self, candidates):
         gp = self.gaussianProcess
-        if gp._fitc is not None or not gp._has_factor():
-            raise NotImplementedError("batched acquisition costs need the dense Cholesky factor (GP built with FITC=... has none)")
+        if (gp._fitc is not None and not gp._vfe()) or (gp._fitc is None and not gp._has_factor()):
+            raise NotImplementedError("batched acquisition costs need the dense Cholesky factor (GP built with FITC=... has none) "
+                                      "or a VFE model (GP(..., FITC=fraction, sparse='vfe'))")
         # the device forms mean = K(Z, X) coeff: the zero prior mean of the base class (gp.py:73)
         assert type(gp).gpPriorMean is _GP.gpPriorMean and "gpPriorMean" not in vars(gp), \
             "batched acquisition costs assume the base class's zero gpPriorMean"
@@ -511,18 +545,18 @@ class _costFuncBO(costFunctionBase):
     def evaluateBatch(self, candidates):
         """(M,) costs of the candidates (rows), one device call."""
         ctx, gp, Z = self._dense(candidates)
-        return _dev.acq(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param())[2]
+        return _AcqCalls(ctx, gp).acq(Z, self._acq, self._param())[2]
 
     def bestCandidate(self, candidates):
         """(index, cost): the first index of the minimum among the non-NaN costs (-1 and NaN when every cost is NaN)."""
         ctx, gp, Z = self._dense(candidates)
-        best, cost, _ = _dev.acq(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param(), want_costs=False)
+        best, cost, _ = _AcqCalls(ctx, gp).acq(Z, self._acq, self._param(), want_costs=False)
         return best, cost
 
     def evaluateBatchWithDerivative(self, candidates):
         """((M,) costs, (M, d) gradients), one device call."""
         ctx, gp, Z = self._dense(candidates)
-        return _dev.acq_grad(ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, self._acq, self._param())
+        return _AcqCalls(ctx, gp).acq_grad(Z, self._acq, self._param())
 
     def derivativeBatch(self, candidates):
         """(M, d): row m = d cost_m / d candidate_m -- the true derivative of evaluateBatch (squared exponential, Matern 3/2 and
@@ -563,8 +597,10 @@ class _costFuncBO(costFunctionBase):
         the largest believed value from pick to pick; kappa / a given fBest stay.
 
         Returns (indices (nPoints,) int64, costs (nPoints,)): costs[t] is the winner's cost at pick t; with returnAllCosts=True also
-        allCosts (nPoints, M), row t = the costs pick t was chosen from (NaN at the candidates picked before).  Dense models only; the
-        cost object and its GP are not modified.  Under a multi-process launch the call runs replicated: every rank makes the same
+        allCosts (nPoints, M), row t = the costs pick t was chosen from (NaN at the candidates picked before).  The cost object and
+        its GP are not modified.  Dense models and VFE models; on a VFE model (gpx_vfe_acq_batch) every refit of the loop keeps the
+        inducing points and hyper-parameters, so a pick enters through the inducing variables only (delta = noise + |La^-1 k_u(c_s)|^2)
+        -- the refit with fixed inducing points, not conditioning the predictor with v_s + noise.  Under a multi-process launch the call runs replicated: every rank makes the same
         deterministic single-GPU call on the factor."""
         kindLie, lieValue = self._lie(lie)
         q = int(nPoints)
@@ -572,21 +608,27 @@ class _costFuncBO(costFunctionBase):
         n, m = gp.pts.shape[0], C.shape[0]
         if q > m:
             raise ValueError("selectBatch: %d points asked of %d candidates" % (q, m))
-        spec, noise, param, track = gp.kernel._spec(), float(gp.noise), self._param(), self._trackBest()
+        calls, param, track = _AcqCalls(ctx, gp), self._param(), self._trackBest()
         if not hasattr(ctx, "_hbm_bytes"):
             ctx._hbm_bytes = ctx.info()["hbm_bytes"]
-        resident = 8.0 * (m + 128) * (n + q + 512)              # W_C, the picks' rows (+ padding)
-        transient = 8.0 * (m + 128) * (n + 512) if n >= 1920 else 0.0   # set-up: the cross matrix the out-of-place solve consumes
-        if resident + transient + 8.0 * n * n > 0.8 * ctx._hbm_bytes:
+        if calls.vfe is not None:
+            nup = -(-gp.fitcnodes.shape[0] // 128) * 128
+            resident = 8.0 * (m + 128) * (nup + q)              # Wa = La^-1 K(S, C), the picks' rows
+            transient = 8.0 * (m + 128) * nup                   # set-up: the chunk the Lu solve consumes
+            fits = resident + transient <= 0.8 * ctx._hbm_bytes
+        else:
+            resident = 8.0 * (m + 128) * (n + q + 512)              # W_C, the picks' rows (+ padding)
+            transient = 8.0 * (m + 128) * (n + 512) if n >= 1920 else 0.0   # set-up: the cross matrix the out-of-place solve consumes
+            fits = resident + transient + 8.0 * n * n <= 0.8 * ctx._hbm_bytes
+        if not fits:
             return self._selectBatchRefit(candidates, q, kindLie, lieValue, param, track, returnAllCosts)
-        out = _dev.acq_batch(ctx, spec, gp._L, gp._X, gp.coeff, C, noise, self._acq, param, track, kindLie, lieValue, q,
-                             want_all=returnAllCosts)
+        out = calls.acq_batch(C, self._acq, param, track, kindLie, lieValue, q, want_all=returnAllCosts)
         idx, costs, allc = out[0], out[1], (out[3] if returnAllCosts else None)
         return (idx, costs, allc) if returnAllCosts else (idx, costs)
 
     def _selectBatchRefit(self, candidates, q, kindLie, lieValue, param, track, returnAllCosts):
         """selectBatch when the resident state does not fit beside the factor: the refit loop it replaces, with the existing calls
-        (gpx_acq chunks the candidates)."""
+        (gpx_acq / gpx_vfe_acq chunk the candidates).  On a VFE model every refit keeps the inducing points (`fitcnodes` is set)."""
         candidates = np.asarray(candidates, dtype=float)
         ctx = _dev.context()
         g2 = copy.copy(self.gaussianProcess)
@@ -595,7 +637,7 @@ class _costFuncBO(costFunctionBase):
         for t in range(q):
             if t > 0:
                 g2.train(X, y)
-            c = _dev.acq(ctx, g2.kernel._spec(), g2._L, g2._X, g2.coeff, _dev.points(ctx, candidates), self._acq, param)[2]
+            c = _AcqCalls(ctx, g2).acq(_dev.points(ctx, candidates), self._acq, param)[2]
             c[idx] = np.nan
             j = firstMinIndex(c)
             if j < 0:
@@ -703,8 +745,8 @@ def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rboun
     if len(candidates) == 0:
         raise ValueError("optimizeAcquisition: no candidate lies inside the bounds")
     ctx, gp, Z = costFunction._dense(candidates)
-    spec = gp.kernel._spec()
-    best, bestCost, costs = _dev.acq(ctx, spec, gp._L, gp._X, gp.coeff, Z, costFunction._acq, costFunction._param())
+    calls = _AcqCalls(ctx, gp)
+    best, bestCost, costs = calls.acq(Z, costFunction._acq, costFunction._param())
     if best < 0:
         raise ValueError("optimizeAcquisition: every candidate's cost is NaN")
     # starts: the nStarts best candidates (NaN costs last, ties in index order), duplicates of a chosen row skipped
@@ -721,15 +763,14 @@ def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rboun
 
     def objective(x):
         P = np.ascontiguousarray(np.reshape(x, (k, d)))
-        c, g = _dev.acq_grad(ctx, spec, gp._L, gp._X, gp.coeff, _dev.points(ctx, P), costFunction._acq, costFunction._param())
+        c, g = calls.acq_grad(_dev.points(ctx, P), costFunction._acq, costFunction._param())
         if not np.all(np.isfinite(c)) or not np.all(np.isfinite(g)):   # (var == 0 exactly: steer the line search away)
             return 1e300, np.zeros(k * d)
         return float(np.sum(c)), g.ravel()
 
     x = _bfgs(objective, x0, bounds=bounds, maxiter=int(maxiter))[0]
     P = np.clip(np.reshape(x, (k, d)), lb, ub)
-    j, c = _dev.acq(ctx, spec, gp._L, gp._X, gp.coeff, _dev.points(ctx, P), costFunction._acq, costFunction._param(),
-                    want_costs=False)[:2]
+    j, c = calls.acq(_dev.points(ctx, P), costFunction._acq, costFunction._param(), want_costs=False)[:2]
     if j >= 0 and c < bestCost:
         return P[j:j + 1].copy(), float(c), int(inside[best])
     return candidates[best:best + 1].copy(), float(bestCost), int(inside[best])

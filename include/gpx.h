@@ -442,6 +442,44 @@ int gpx_vfe_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double*
 int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double* mean,
                       double* var);
 
+/* ---- Bayesian-optimisation costs on a VFE model ----------------------------------------------------------------------------------
+ * gpx_acq / gpx_acq_grad / gpx_acq_batch for the model gpx_vfe_fit built: the kernel parameters are the model's (no (kind, d, hyp)
+ * arguments), S its inducing points, coeff = alpha from gpx_fitc_solve (host N, required).  Notation: Quu = K(S,S) + noise I =
+ * Lu Lu^T, A = Quu + Kuf Kfu / noise = La La^T, beta_u = Quu^-1 Kuf alpha, k_u(z) = K(S, z).  A FITC model is refused with an
+ * argument error (VFE models only); every kernel kind is accepted except where stated.
+ *
+ * gpx_vfe_acq: per chunk of Z the mean and the signed variance exactly as gpx_vfe_posterior forms them, then gpx_acq's own cost
+ * formula, epilogue and arg-min.  cost / best / best_cost: as gpx_acq (each nullable; *best the FIRST arg-min among the non-NaN
+ * costs, -1 when all are NaN, whatever the chunking under GPX_CROSS_BYTES). */
+int gpx_vfe_acq(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                double* cost, int64_t* best, double* best_cost);
+/* grad (host M x d): grad[m*d + l] = d cost_m / d z_m[l], the true derivative of gpx_vfe_acq's values; cost (host M, nullable) holds
+ * gpx_vfe_acq's bits.  With a = dA/dmu, b = dA/dvar (gpx_acq_grad's table) and k(z, z) constant:
+ *     gamma(z) = Quu^-1 k_u(z) - A^-1 k_u(z)                                   (a nu-vector per candidate)
+ *     grad_z A = sum_u dk(z, s_u)/dz (a beta_u[u] - 2 b gamma(z)[u])
+ * NaN rows where var == 0 exactly.  Per chunk the two forward solves of the values are reused, each gets its backward sweep
+ * (Lu^-T, La^-T: nu^2 chunk flops each), and ONE pass over the nu inducing points per candidate takes the difference of the two
+ * and the weighted sum.  Squared exponential, Matern 3/2 and 5/2; a Mehler model is an argument error. */
+int gpx_vfe_acq_grad(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
+                     double* cost, double* grad);
+/* q-point batch selection on a VFE model whose inducing points and hyper-parameters stay fixed: the loop "cost on the grown data;
+ * bestCandidate; append the pick with its believed value", where every refit is gpx_vfe_fit on X + picks with the SAME S.  One
+ * more observation at c_s changes A to A + k_u(c_s) k_u(c_s)^T / noise and nothing else, so the refit is a rank-one recurrence in
+ * the inducing space.  Resident state: Wa = La^-1 K(S, C) (nu x M, the only matrix kept), mu_j = k_u(c_j)^T beta_u,
+ * r_j = k(c_j, c_j) - |Lu^-1 k_u(c_j)|^2 (fixed for the whole call; the Lu solve is transient), t_j = |Wa[:, j]|^2, the rows U[t].
+ * Pick t = 0 .. q-1:
+ *     v_j = r_j + t_j;  cost_j = A(mu_j, v_j; param), NaN for the candidates already picked;  s = first arg-min among the non-NaN costs
+ *     delta = noise + t_s          (NOT v_s + noise: the observation enters through the inducing variables only)
+ *     y_s = mu_s (GPX_LIE_BELIEVER) or lie_value (GPX_LIE_CONSTANT)
+ *     u_j = (Wa[:, s]^T Wa[:, j] - sum_{r<t} U[r][s] U[r][j]) / sqrt(delta);   U[t] = u
+ *     mu_j += u_j (y_s - mu_s) / sqrt(delta);   t_j -= u_j^2;   param = max(param, y_s) when track_best != 0
+ * delta >= noise > 0: gpx_acq_batch's tiny-pivot rule has no counterpart.  Per pick one pass over Wa (8 nu M bytes); all
+ * reductions in a fixed order (two runs agree bit for bit); row 0 of all_costs holds gpx_vfe_acq's bits.  Outputs and errors as
+ * gpx_acq_batch. */
+int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* C, int acq, double param,
+                      int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie,
+                      double* all_costs);
+
 /* ---- measurement ------------------------------------------------------------------------------- */
 /* when enabled every kernel launch of a class is bracketed by HIP events on the launch stream */
 int gpx_profile_enable(gpx_ctx* ctx, int on);

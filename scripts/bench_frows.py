@@ -257,8 +257,73 @@ if want("fitc"):
                               "run (one M x N fill, the M x nu x N product 2 nu N M, one right solve nu^2 M = %.3e flop): "
                               "%.2f..%.2f ms, %.1f TF/s; ratio of the minima %.4f (roofline count ratio %.4f)"
                               % (1e3 * tp0, 1e3 * tp1, ff, 1e3 * tq0, 1e3 * tq1, ff / tq0 / 1e12, tp0 / tq0, fv / ff)))
+    # Bayesian-optimisation costs on the VFE model (gpx_vfe_acq / gpx_vfe_acq_grad / gpx_vfe_acq_batch) against what a user had
+    # before them, timed in this run, ALTERNATING, five runs each: for the values and the arg-min the predictor, the host costs
+    # (scipy.stats, as costFuncEI.evaluate forms them) and firstMinIndex; for the batch q refits on the grown data with the same
+    # inducing points, each scored that way.  The gradient had no counterpart.
+    import scipy.stats as spstats
+    from gpexp_amd.experimentalDesign import firstMinIndex
+
+    def alternate(f, g, reps=5):
+        tf, tg = [], []
+        for _ in range(reps):
+            tf.append(best(f, reps=1)[1])
+            tg.append(best(g, reps=1)[1])
+        return (min(tf), max(tf)), (min(tg), max(tg))
+
+    def host_ei(model, coeff, fbest, pts):
+        mean, var = model.posterior(coeff, pts)
+        s = np.sqrt(np.abs(var))
+        g = (fbest - mean) / s
+        costs = -s * (g * spstats.norm.cdf(g) + spstats.norm.pdf(g))
+        return firstMinIndex(costs), costs
+
+    fb, qb = float(np.max(yf)), 8
+    mv.acq(cv, Zd, dev.ACQ_EI, fb); mv.acq_grad(cv, Zd, dev.ACQ_EI, fb)    # warm: pools
+    (ta0, ta1), (th0, th1) = alternate(lambda: mv.acq(cv, Zd, dev.ACQ_EI, fb), lambda: host_ei(mv, cv, fb, Zd))
+    vlines.append(report("gpx_vfe_acq", "gpx_vfe_posterior + the costs on the host (scipy.stats) + firstMinIndex",
+                         dict(N=Nf, nu=nu, M=Mz, d=d, acq="EI"), ta0, flops=fv,
+                         note="gpx_vfe_posterior's per-chunk step, then the cost epilogue and the arg-min on the device: M costs and "
+                              "the winner reach the host instead of mean and variance; five runs each, alternating: %.2f..%.2f ms, "
+                              "the predictor + host costs + firstMinIndex %.2f..%.2f ms, ratio of the minima %.3f"
+                              % (1e3 * ta0, 1e3 * ta1, 1e3 * th0, 1e3 * th1, ta0 / th0)))
+    tg0_, tg1_ = spread(lambda: mv.acq_grad(cv, Zd, dev.ACQ_EI, fb))
+    vlines.append(report("gpx_vfe_acq_grad", "none (no gradient of a cost on a VFE model before)", dict(N=Nf, nu=nu, M=Mz, d=d, acq="EI"),
+                         tg0_, flops=2.0 * fv,
+                         note="the values, then both forward solves transposed and swept backward (nu^2 M each) and one fused pass "
+                              "over the nu inducing points per candidate; five runs: %.2f..%.2f ms; ratio to gpx_vfe_acq in this "
+                              "run %.3f" % (1e3 * tg0_, 1e3 * tg1_, tg0_ / ta0)))
+    Zhost = rng.uniform(-1, 1, (Mz, d))
+    Zb = dev.points(ctx, Zhost)
+
+    def refit_batch():
+        Xa, ya, picks = Xf, yf, []
+        for t in range(qb):
+            model = mv if t == 0 else dev.VfeModel(ctx, sp, dev.points(ctx, Xa), Sd, 0.1)
+            coeff = cv if t == 0 else model.solve(ya)[0]
+            mean, var = model.posterior(coeff, Zb)
+            s = np.sqrt(np.abs(var))
+            g = (max(fb, float(np.max(ya))) - mean) / s
+            costs = -s * (g * spstats.norm.cdf(g) + spstats.norm.pdf(g))
+            costs[picks] = np.nan
+            j = firstMinIndex(costs)
+            picks.append(j)
+            Xa, ya = np.vstack((Xa, Zhost[j:j + 1])), np.append(ya, mean[j])
+        return picks
+
+    mv.acq_batch(cv, Zb, dev.ACQ_EI, fb, True, dev.LIE_BELIEVER, 0.0, qb)       # warm: pools
+    picks_dev = mv.acq_batch(cv, Zb, dev.ACQ_EI, fb, True, dev.LIE_BELIEVER, 0.0, qb)[0].tolist()
+    picks_ref = refit_batch()
+    (tb0, tb1), (tr0, tr1) = alternate(lambda: mv.acq_batch(cv, Zb, dev.ACQ_EI, fb, True, dev.LIE_BELIEVER, 0.0, qb), refit_batch)
+    vlines.append(report("gpx_vfe_acq_batch", "q refits with the same inducing points (gpx_vfe_fit + gpx_fitc_solve + gpx_vfe_posterior "
+                         "+ host costs per pick)", dict(N=Nf, nu=nu, M=Mz, q=qb, d=d, acq="EI", lie="believer"), tb0,
+                         flops=fv,
+                         note="set-up as gpx_vfe_acq with Wa = La^-1 K(S, C) kept (2 nu^2 M flop: the count the rate is on), then per pick "
+                              "ONE pass over Wa (8 nu M bytes, the weighted column reduction); five runs each, alternating: %.2f..%.2f ms, the refit "
+                              "loop %.2f..%.2f ms, ratio of the minima %.4f; picks equal to the refit loop's: %s"
+                              % (1e3 * tb0, 1e3 * tb1, 1e3 * tr0, 1e3 * tr1, tb0 / tr0, picks_dev == picks_ref)))
     del mv
-    out_vfe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vfe_frows.jsonl")
+    out_vfe =os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vfe_frows.jsonl")
     if "--vfe-out" in sys.argv:
         out_vfe = sys.argv[sys.argv.index("--vfe-out") + 1]
     with open(out_vfe, "a") as f:
