@@ -288,6 +288,64 @@ int launch_transpose(gpx_ctx* ctx, const double* in, int64_t rows, int64_t cols,
   return 0;
 }
 
+// The greedy-variance loop of gpx_greedy_var.  out_d (host, M doubles; optional): the conditional variances the LAST pick was chosen
+// from -- d after the row steps of picks 0 .. nsel - 2 (the last pick conditions nothing) -- for gpx_dbg_greedy_var_scores.
+static int greedy_var_run(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* Cm, const double* w,
+                          const int64_t* keep, int64_t nkeep, int64_t nsel, int64_t* out_idx, double* out_d) {
+  GPX_ARG(ctx && Cm && out_idx, "NULL argument");
+  GPX_ARG(nkeep >= 0 && nsel >= nkeep && (nkeep == 0 || keep), "bad keep/nsel");
+  KParams kp;
+  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
+  GPX_ARG(Cm->cols == d && Cm->pcols == d, "point sets must be unpadded (n x d)");
+  const int64_t M = Cm->rows;
+  GPX_ARG(M > 0, "no candidates");
+  for (int64_t i = 0; i < nkeep; ++i) GPX_ARG(keep[i] >= 0 && keep[i] < M, "keep index out of range");
+  if (nsel == 0) return 0;
+  Scratch sc(ctx);
+  const int nb = (int)(((M + 255) / 256) < 1024 ? ((M + 255) / 256) : 1024);
+  void *pW, *pd0, *pd1, *pprior, *psel, *ppv, *ppi, *pw = nullptr;
+  GPX_TRY(sc.get(nsel * M * 8, &pW));
+  GPX_TRY(sc.get(M * 8, &pd0));
+  GPX_TRY(sc.get(M * 8, &pd1));
+  GPX_TRY(sc.get(M * 8, &pprior));
+  GPX_TRY(sc.get(nsel * 8, &psel));
+  GPX_TRY(sc.get(nb * 8, &ppv));
+  GPX_TRY(sc.get(nb * 8, &ppi));
+  if (w) {
+    GPX_TRY(sc.get(M * 8, &pw));
+    GPX_HIP(hipMemcpyAsync(pw, w, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (nkeep > 0) GPX_HIP(hipMemcpyAsync(psel, keep, (size_t)nkeep * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, (double*)pprior));
+  GPX_HIP(hipMemcpyAsync(pd0, pprior, (size_t)M * 8, hipMemcpyDeviceToDevice, ctx->stream));
+  double* din = (double*)pd0;
+  double* dout = (double*)pd1;
+  const dim3 gridM((unsigned)((M + 255) / 256));
+  {
+    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)M * nsel * nsel, 0.0);
+    for (int64_t cur = 0; cur < nsel; ++cur) {
+      if (cur >= nkeep) {
+        hipLaunchKernelGGL(argmax_stage1, dim3(nb), dim3(256), 0, ctx->stream, din, (const double*)pw, M, (double*)ppv,
+                           (int64_t*)ppi);
+        hipLaunchKernelGGL(argmax_stage2, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppv, (const int64_t*)ppi,
+                           nb, (int64_t*)psel, (int)cur);
+      }
+      if (cur + 1 < nsel) {  // the last pick needs no further conditioning
+        hipLaunchKernelGGL(greedy_row_kernel, gridM, dim3(256), 0, ctx->stream, kp, Cm->p, M, (const int64_t*)psel,
+                           (int)cur, (double*)pW, M, (const double*)pprior, (const double*)din, dout);
+        double* t = din;
+        din = dout;
+        dout = t;
+      }
+    }
+  }
+  GPX_HIP(hipGetLastError());
+  GPX_HIP(hipMemcpyAsync(out_idx, psel, (size_t)nsel * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_d) GPX_HIP(hipMemcpyAsync(out_d, din, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 extern "C" {
 
 int gpx_kernel_eval(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const double* A, int64_t na,
@@ -369,57 +427,17 @@ int gpx_potri(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP) { return gpx_potri
 
 int gpx_greedy_var(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* Cm, const double* w,
                    const int64_t* keep, int64_t nkeep, int64_t nsel, int64_t* out_idx) {
-  GPX_ARG(ctx && Cm && out_idx, "NULL argument");
-  GPX_ARG(nkeep >= 0 && nsel >= nkeep && (nkeep == 0 || keep), "bad keep/nsel");
-  KParams kp;
-  GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
-  GPX_ARG(Cm->cols == d && Cm->pcols == d, "point sets must be unpadded (n x d)");
-  const int64_t M = Cm->rows;
-  GPX_ARG(M > 0, "no candidates");
-  for (int64_t i = 0; i < nkeep; ++i) GPX_ARG(keep[i] >= 0 && keep[i] < M, "keep index out of range");
-  if (nsel == 0) return 0;
-  Scratch sc(ctx);
-  const int nb = (int)(((M + 255) / 256) < 1024 ? ((M + 255) / 256) : 1024);
-  void *pW, *pd0, *pd1, *pprior, *psel, *ppv, *ppi, *pw = nullptr;
-  GPX_TRY(sc.get(nsel * M * 8, &pW));
-  GPX_TRY(sc.get(M * 8, &pd0));
-  GPX_TRY(sc.get(M * 8, &pd1));
-  GPX_TRY(sc.get(M * 8, &pprior));
-  GPX_TRY(sc.get(nsel * 8, &psel));
-  GPX_TRY(sc.get(nb * 8, &ppv));
-  GPX_TRY(sc.get(nb * 8, &ppi));
-  if (w) {
-    GPX_TRY(sc.get(M * 8, &pw));
-    GPX_HIP(hipMemcpyAsync(pw, w, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (nkeep > 0) GPX_HIP(hipMemcpyAsync(psel, keep, (size_t)nkeep * 8, hipMemcpyHostToDevice, ctx->stream));
-  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, (double*)pprior));
-  GPX_HIP(hipMemcpyAsync(pd0, pprior, (size_t)M * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  double* din = (double*)pd0;
-  double* dout = (double*)pd1;
-  const dim3 gridM((unsigned)((M + 255) / 256));
-  {
-    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)M * nsel * nsel, 0.0);
-    for (int64_t cur = 0; cur < nsel; ++cur) {
-      if (cur >= nkeep) {
-        hipLaunchKernelGGL(argmax_stage1, dim3(nb), dim3(256), 0, ctx->stream, din, (const double*)pw, M, (double*)ppv,
-                           (int64_t*)ppi);
-        hipLaunchKernelGGL(argmax_stage2, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppv, (const int64_t*)ppi,
-                           nb, (int64_t*)psel, (int)cur);
-      }
-      if (cur + 1 < nsel) {  // the last pick needs no further conditioning
-        hipLaunchKernelGGL(greedy_row_kernel, gridM, dim3(256), 0, ctx->stream, kp, Cm->p, M, (const int64_t*)psel,
-                           (int)cur, (double*)pW, M, (const double*)pprior, (const double*)din, dout);
-        double* t = din;
-        din = dout;
-        dout = t;
-      }
-    }
-  }
-  GPX_HIP(hipGetLastError());
-  GPX_HIP(hipMemcpyAsync(out_idx, psel, (size_t)nsel * 8, hipMemcpyDeviceToHost, ctx->stream));
-  GPX_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
+  return greedy_var_run(ctx, kind, d, hyp, nhyp, Cm, w, keep, nkeep, nsel, out_idx, nullptr);
+}
+
+// debug (gpx_debug.h): the conditional variances pick number nkeep is chosen from, after conditioning on keep[0 .. nkeep) in that
+// order -- gpx_greedy_var with nsel = nkeep + 1, whose one free pick is dropped and whose last d vector comes back
+int gpx_dbg_greedy_var_scores(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* Cm, const int64_t* keep,
+                              int64_t nkeep, double* out_d) {
+  GPX_ARG(out_d != nullptr, "NULL argument");
+  GPX_ARG(nkeep >= 0, "bad keep");
+  std::vector<int64_t> idx((size_t)nkeep + 1);
+  return greedy_var_run(ctx, kind, d, hyp, nhyp, Cm, nullptr, keep, nkeep, nkeep + 1, idx.data(), out_d);
 }
 
 int gpx_greedy_ivar_step(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L,

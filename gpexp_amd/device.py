@@ -551,6 +551,16 @@ def greedy_var(ctx, spec, Cpts, nsel, keep=(), weights=None):
     return out
 
 
+def dbg_greedy_var_scores(ctx, spec, Cpts, keep=()):
+    """(M,) conditional variances that pick number len(keep) of greedy_var is chosen from, after conditioning on `keep` in that
+    order (test hook, gpx_dbg_greedy_var_scores; no keep: the prior)."""
+    keep = np.ascontiguousarray(np.asarray(list(keep), dtype=np.int64))
+    out = np.empty(Cpts.shape[0])
+    check(ctx.lib.gpx_dbg_greedy_var_scores(ctx.h, *spec.args(), Cpts.h, keep.ctypes.data_as(_lib.c_ip), int(keep.size),
+                                            dptr(out)))
+    return out
+
+
 def greedy_ivar_step(ctx, spec, L, X, Cpts, Z, noise, want_costs=True):
     m = Cpts.shape[0]
     costs = np.empty(m) if want_costs else None

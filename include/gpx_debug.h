@@ -74,6 +74,12 @@ int gpx_dbg_event_elapsed(gpx_ctx* ctx, int id0, int id1, double* ms);
    done; shader clocks; 28 / 29: the constant 100 MHz clock at start / end).  fast = 1: round 5's diagonal step, 0: the general one throughout.  scripts/probe_leaf.py. */
 int gpx_dbg_leaf_stamps(gpx_ctx* ctx, gpx_mat* K, int fast, int64_t* out30);
 
+/* The conditional variances d[c] (host, M doubles) that pick number nkeep of gpx_greedy_var would be chosen from, after
+   conditioning on keep[0 .. nkeep) in that order (nkeep == 0: the prior): the launches and buffers of gpx_greedy_var itself, which
+   returns indices only.  tests/test_gpu_design_replay.py compares them with a from-scratch extended-precision recurrence. */
+int gpx_dbg_greedy_var_scores(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* C, const int64_t* keep,
+                              int64_t nkeep, double* out_d /* host M */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,12 @@ def _greedy_var(n):
     return ctx, lambda: dev.greedy_var(ctx, spec, Z, 4)
 
 
+def _dbg_greedy_var_scores(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    return ctx, lambda: dev.dbg_greedy_var_scores(ctx, spec, Z, keep=[5, 200, 17])
+
+
 def _loo(n):
     from gpexp_amd import device as dev
     ctx, spec, X, L, y, alpha, Z, Xh = model(n)
@@ -195,6 +201,7 @@ ENTRIES = [
     ("acq_batch", _acq_batch, 300),
     ("ivar_grad", _ivar_grad, 300), ("var_grad_newpt", _var_grad_newpt, 300),
     ("lml_grad", _lml_grad, 300), ("mi_greedy", _mi_greedy, 300), ("greedy_var", _greedy_var, 300),
+    ("dbg_greedy_var_scores", _dbg_greedy_var_scores, 300),
     ("loo", _loo, 300), ("loo_grad", _loo_grad, 300),
     ("fitc_fit+fitc_solve", _fitc, 300),
 ]
