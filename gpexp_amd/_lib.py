@@ -170,6 +170,13 @@ _SIGS = {
     "gpx_var_grad_newpt": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_vp, c_dp]),
     "gpx_fitc_var_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp, c_dp]),
     "gpx_fitc_var_grad_newpt": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp]),
+    "gpx_vfe_design_create": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, C.c_double, c_vp, C.POINTER(c_vp)]),
+    "gpx_vfe_design_pin": (C.c_int, [c_vp, c_vp, c_vp]),
+    "gpx_vfe_design_eval": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp]),
+    "gpx_vfe_design_shape": (C.c_int, [c_vp, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64)]),
+    "gpx_vfe_design_free": (C.c_int, [c_vp, c_vp]),
+    "gpx_vfe_var_grad": (C.c_int, [c_vp, c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_vp, c_dp]),
+    "gpx_vfe_var_grad_newpt": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_dp]),
     "gpx_profile_enable": (C.c_int, [c_vp, C.c_int]),
     "gpx_profile_reset": (C.c_int, [c_vp]),
     "gpx_profile_get": (C.c_int, [c_vp, C.c_int, c_ip, c_dp, c_dp, c_dp]),

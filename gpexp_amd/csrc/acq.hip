@@ -38,6 +38,11 @@ __device__ __forceinline__ double acq_cost(int acq, double param, double mu, dou
   const double s = sqrt(fabs(var));
   const double sg = var > 0.0 ? 1.0 : (var < 0.0 ? -1.0 : 0.0);
   double c, a, b;
+  if (acq == GPX_ACQ_VARIANCE) {   // the variance itself (gpx_vfe_var_grad_newpt): smooth through var == 0
+    *a_out = 0.0;
+    *b_out = 1.0;
+    return var;
+  }
   if (acq == GPX_ACQ_UCB) {
     c = -(mu - param * s);
     a = -1.0;
@@ -491,7 +496,12 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
     GPX_TRY(sc.get(2 * bytes_out, &pcoef));
     GPX_TRY(sc.get(M * d * 8, &pgrad));
   }
-  GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
+  if (coeff) {
+    GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
+  } else {   // (GPX_ACQ_VARIANCE: no mean; its weight a is 0)
+    GPX_TRY(sc.get(nup * 8, &bu));
+    GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
+  }
   for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
     const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
     const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);

@@ -623,6 +623,13 @@ int64_t fitc_np(const gpx_fitc* f) { return f->np; }
 int64_t fitc_nup(const gpx_fitc* f) { return f->nup; }
 int fitc_is_vfe(const gpx_fitc* f) { return f->vfe; }
 void fitc_view(const gpx_fitc* f, FitcView* v) { *v = FitcView{&f->kp, f->n, f->nu, f->np, f->nup, f->noise, f->Lu, f->La}; }
+// what vfe_design.hip shares with the model: the factorisation with its pivot report, and the row pass of dL/dS
+int fitc_factor(gpx_ctx* ctx, gpx_mat* K, const char* what) { return factor_in_place(ctx, K, what); }
+int64_t fitc_wgrad_partial_elems(int64_t na, int64_t nb, int d) { return wgrad_segments(na, nb) * na * d; }
+int fitc_wgrad_rows(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat* B, const double* Mw, int64_t ld, double* ppart,
+                    double* out) {
+  return fitc_wgrad(ctx, kp, A, B, Mw, ld, ppart, 0, out);
+}
 
 // beta_u = Quu^-1 (Kuf alpha): one row reduction over Kuf and both sweeps against chol(Quu); 0 on the padding
 int vfe_beta_u(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& tmp, double** bu_out) {
@@ -1370,6 +1377,32 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
   GPX_ARG(q <= C->rows, "more picks than candidates");
   return vfe_acq_batch_impl(ctx, f, S, coeff, C, acq, param, track_best != 0, lie, lie_value, q, out_idx, out_cost, out_lie,
                             all_costs);
+}
+
+// Point-wise derivatives of the variational variance (bodies: vfe_design.hip; the argument checks are here, where the struct is)
+int gpx_vfe_var_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
+                     const gpx_mat* S, const gpx_mat* Z, double* out) {
+  GPX_ARG(ctx && f && X && S && Z && out, "NULL argument");
+  FITC_KIND(f, true, "vfe_var_grad", "call gpx_fitc_var_grad");
+  FITC_ARG(kind != GPX_K_MEHLER, "vfe_var_grad",
+           "point derivatives exist for the squared exponential and the isotropic Materns only, not for the Mehler kernel");
+  KParams kp;
+  GPX_TRY(fitc_grad_args(f, "vfe_var_grad", kind, d, hyp, nhyp, X, S, &kp));
+  GPX_ARG(Z->cols == d && Z->pcols == d, "point sets do not match");
+  if (Z->rows == 0) return 0;
+  return vfe_var_grad_impl(ctx, f, X, S, Z, out);
+}
+
+int gpx_vfe_var_grad_newpt(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* out) {
+  GPX_ARG(ctx && f && S && Z && out, "NULL argument");
+  FITC_KIND(f, true, "vfe_var_grad_newpt", "call gpx_fitc_var_grad_newpt");
+  FITC_ARG(f->kp.kind == GPX_K_SE || f->kp.kind == GPX_K_MATERN32 || f->kp.kind == GPX_K_MATERN52, "vfe_var_grad_newpt",
+           "point derivatives exist for the squared exponential and the isotropic Materns only, not for the Mehler kernel");
+  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
+          "point sets do not match");
+  if (Z->rows == 0) return 0;
+  // gpx_vfe_acq_grad's own sequence with (a, b) = (0, 1): grad_z var = -2 sum_u dk(z, s_u)/dz gamma(z)[u]
+  return vfe_acq_impl(ctx, f, S, nullptr, Z, GPX_ACQ_VARIANCE, 0.0, nullptr, nullptr, nullptr, out);
 }
 
 // Dense Q + G and P (host, n x n row-major, each nullable): the reference's covarianceMatrix / precisionMatrix attributes.

@@ -457,7 +457,20 @@ int vfe_beta_u(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& tm
 int vfe_posterior_chunk(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kpz, const gpx_mat* S, const double* Zc, int64_t mc,
                         double* B1, double* B2, double* Wu, double* Wa, const double* bu, double* pm, double* su, double* sa,
                         double* kd, double* pv, double* part);
-// acq.hip: the bodies of gpx_vfe_acq / gpx_vfe_acq_grad (grad_host != NULL) and gpx_vfe_acq_batch, behind fitc.hip's argument checks
+// fitc.hip: what vfe_design.hip shares with the models.  fitc_factor: chol_potrf in place (leaf inverses in K->aux) with the
+// context's pivot policy; a bad pivot is returned (> 0) with a message that reads `what`.  fitc_wgrad_rows: the row pass of dL/dS,
+//   out[u][l] (na x d, device) = sum_c Mw[u][c] dk(a_u, b_c)/da_u[l]      (the TRUE derivative; weights Mw: na x nb, row stride ld)
+// in a fixed order; ppart: fitc_wgrad_partial_elems(na, nb, d) doubles of scratch.
+int fitc_factor(gpx_ctx* ctx, gpx_mat* K, const char* what);
+int64_t fitc_wgrad_partial_elems(int64_t na, int64_t nb, int d);
+int fitc_wgrad_rows(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat* B, const double* Mw, int64_t ld, double* ppart,
+                    double* out);
+// vfe_design.hip: the body of gpx_vfe_var_grad, behind fitc.hip's argument checks
+int vfe_var_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const gpx_mat* S, const gpx_mat* Z, double* out);
+// acq.hip: the bodies of gpx_vfe_acq / gpx_vfe_acq_grad (grad_host != NULL) and gpx_vfe_acq_batch, behind fitc.hip's argument checks.
+// acq = GPX_ACQ_VARIANCE (internal, not in gpx.h): the "cost" is the signed variance itself, (a, b) = (0, 1), so the gradient is
+// d var(z)/dz (gpx_vfe_var_grad_newpt); coeff may then be NULL (beta_u = 0).
+#define GPX_ACQ_VARIANCE (-1)
 int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
                  double* cost_host, int64_t* best, double* best_cost, double* grad_host);
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,

@@ -463,6 +463,57 @@ class VfeModel(FitcModel):
                                              dptr(cost), dptr(lies), dptr(allc)))
         return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
 
+    def design_var_grad(self, spec, X, S, Z):
+        """(N*d, M) matrix d var(z_m) / d X[k][l] of the variational variance (gpx_vfe_var_grad), in `var_grad`'s layout: TRUE
+        derivatives, the inducing points held fixed.  `spec`, X, S = the kernel, nodes and inducing points of the model."""
+        out = np.empty((self.n * spec.d, Z.shape[0]))
+        check(self.ctx.lib.gpx_vfe_var_grad(self.ctx.h, self.h, *spec.args(), X.h, S.h, Z.h, dptr(out)))
+        return out
+
+    def design_var_grad_newpt(self, S, Z):
+        """(M*d,) vector d var(z_m) / d z_m of the variational variance (gpx_vfe_var_grad_newpt): TRUE derivatives."""
+        out = np.empty(Z.shape[0] * Z.shape[1])
+        check(self.ctx.lib.gpx_vfe_var_grad_newpt(self.ctx.h, self.h, S.h, Z.h, dptr(out)))
+        return out
+
+
+class VfeDesign:
+    """Device-resident state of IVAR design on a VFE model (gpx_vfe_design_*): chol(Quu), the Gram matrix of the Monte-Carlo points
+    in the inducing space and A0 = Quu + (the pinned points' part of A).  Built from the kernel, the inducing points S, the noise
+    and the Monte-Carlo points Z alone -- no observations enter the integrated variance."""
+
+    def __init__(self, ctx, spec, S, noise, Z):
+        self.ctx, self.d = ctx, spec.d
+        self.h = None
+        h = c_vp()
+        check(ctx.lib.gpx_vfe_design_create(ctx.h, *spec.args(), S.h, float(noise), Z.h, C.byref(h)))
+        self.h = h
+
+    def pin(self, Xp):
+        """Replace the pinned set by the points Xp (a DeviceMatrix point set; None or 0 rows: nothing pinned)."""
+        check(self.ctx.lib.gpx_vfe_design_pin(self.ctx.h, self.h, Xp.h if Xp is not None else None))
+
+    def eval(self, Xf, want_grad=True):
+        """(signed IVAR of pinned + free points, its (b, d) gradient w.r.t. the free points Xf or None) from one device call."""
+        cost = C.c_double()
+        grad = np.empty((Xf.shape[0], self.d)) if want_grad else None
+        check(self.ctx.lib.gpx_vfe_design_eval(self.ctx.h, self.h, Xf.h, C.byref(cost), dptr(grad)))
+        return cost.value, grad
+
+    def shape(self):
+        """(inducing points, Monte-Carlo points, points currently pinned)"""
+        nu, m, p = c_i64(), c_i64(), c_i64()
+        check(self.ctx.lib.gpx_vfe_design_shape(self.h, C.byref(nu), C.byref(m), C.byref(p)))
+        return nu.value, m.value, p.value
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.ctx.lib.gpx_vfe_design_free(self.ctx.h, self.h)
+            self.h = None
+        except Exception:
+            pass
+
 
 def potrs(ctx, L, y):
     y = as_f64(y)

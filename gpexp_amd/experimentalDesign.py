@@ -39,7 +39,7 @@ NLOPT = False
 __all__ = ["costFunctionBase", "costFunctionGP_IVAR", "costFunctionGP_MI", "ExperimentalDesign",
            "ExperimentalDesignDerivative", "performGreedyVarExperimentalDesign",
            "performGreedyMIExperimentalDesign", "greedyIVARStep", "performGreedyIVARExperimentalDesign", "costFuncGPUCbound",
-           "costFuncPI", "costFuncEI", "optimizeAcquisition", "np"]
+           "costFuncPI", "costFuncEI", "optimizeAcquisition", "costFunctionVFE_IVAR", "np"]
 
 
 class costFunctionBase(object):
@@ -158,6 +158,101 @@ class costFunctionGP_IVAR(costFunctionBase):
             g[r0 * self.space.dimension:] = _dev.ivar_grad_rows(_dev.context(), gp.kernel._spec(), gp._L, gp._X, self._mc(), W, r0)
             return g
         return _dev.ivar_grad(_dev.context(), gp.kernel._spec(), gp._L, gp._X, self._mc(), nd, W=W)
+
+
+class costFunctionVFE_IVAR(costFunctionGP_IVAR):
+    """costFunctionGP_IVAR on a VFE model (GP(..., FITC=fraction, sparse="vfe")), computed in the inducing space (gpx_vfe_design_*):
+    the design enters the variational variance through a nu x nu matrix only and the MC points through one nu x nu Gram matrix,
+    so a cost / gradient evaluation is O(nu^3 + nu^2 b) for b free points -- independent of the number of MC points and, with
+    `pinnedPoints` (the batch driver), of the pinned count.  The gradient is the TRUE derivative of the signed cost, with the
+    inducing points `gaussianProcess.fitcnodes` held fixed (squared exponential and isotropic Matern; Mehler: the cost only).
+
+    The inducing points must be set before the cost is built: a design loop must not draw them from its own first iterate, and the
+    batch driver rebuilds the cost every batch.  The class does NOT refit or touch its GP copy -- there is no
+    addNodesAndComputeCovariance per iterate; the copy only supplies the kernel, the noise and the inducing points.  The device state
+    (gpx_vfe_design_create: built lazily) is rebuilt when `mcPoints`, `fitcnodes`, the kernel's hyper-parameters or `noise` change
+    (compared by value), and `reset()` drops it.  One entry of (cost, gradient) is kept, keyed on the bytes of the design: an
+    optimiser's cost / gradient pair at the same design is one device call.  Per-point noise (`space.noiseFunc`) is not offered."""
+
+    def __init__(self, gaussianProcess, nInputs, space, version=1, **kwargs):
+        if not (isinstance(gaussianProcess, _GP) and gaussianProcess._vfe()):
+            raise ValueError("costFunctionVFE_IVAR needs a VFE model (GP(..., FITC=fraction, sparse='vfe')); on a dense or FITC "
+                             "model use costFunctionGP_IVAR")
+        if gaussianProcess.fitcnodes is None:
+            raise ValueError("costFunctionVFE_IVAR: set gaussianProcess.fitcnodes (the inducing points) first -- a design loop "
+                             "must not draw them from its own first iterate")
+        super(costFunctionVFE_IVAR, self).__init__(gaussianProcess, nInputs, space, version, **kwargs)
+        self.pinnedPoints = 0
+
+    def reset(self):
+        """Drop the device state (and the parent's); the next evaluation rebuilds it."""
+        super(costFunctionVFE_IVAR, self).reset()
+        self._state = None     # (VfeDesign, pinned block or None)
+        self._state_key = None
+        self._last = None      # (bytes of the design, signed cost, flat gradient or None)
+
+    def _design(self):
+        gp = self.gaussianProcess
+        spec = gp.kernel._spec()
+        S = np.ascontiguousarray(gp.fitcnodes, dtype=float)
+        Z = np.ascontiguousarray(self._mcPoints, dtype=float)
+        key = self._state_key
+        same = (self._state is not None and key[0] == spec.kind and np.array_equal(key[1], spec.hyp) and key[2] == float(gp.noise)
+                and np.array_equal(key[3], S) and np.array_equal(key[4], Z))
+        if not same:
+            self._state = self._last = None    # (the old state goes back to the pool before the new one is made)
+            ctx = _dev.context()
+            self._state = [_dev.VfeDesign(ctx, spec, _dev.points(ctx, S), float(gp.noise), _dev.points(ctx, Z)), None]
+            self._state_key = (spec.kind, spec.hyp.copy(), float(gp.noise), S.copy(), Z.copy())
+        return self._state
+
+    def _eval(self, inputPoints, want_grad):
+        assert inputPoints.shape == (self.numInputs, self.space.dimension), \
+            ("inputPoints are the wrong size: ", inputPoints.shape)
+        if self.space.noiseFunc is not None:
+            raise NotImplementedError("costFunctionVFE_IVAR: per-point noise (space.noiseFunc) is not offered -- a VFE model has "
+                                      "one noise variance")
+        X = np.ascontiguousarray(inputPoints, dtype=float)
+        state = self._design()
+        r0 = int(self.pinnedPoints)
+        if not 0 <= r0 < X.shape[0]:
+            raise ValueError("costFunctionVFE_IVAR: pinnedPoints = %d leaves no free point among %d" % (r0, X.shape[0]))
+        key = (r0, X.tobytes())
+        if self._last is not None and self._last[0] == key and (self._last[2] is not None or not want_grad):
+            return self._last[1], self._last[2]
+        ctx = _dev.context()
+        pinned = X[:r0].copy()
+        if state[1] is None or not np.array_equal(state[1], pinned):
+            state[0].pin(_dev.points(ctx, pinned) if r0 > 0 else None)
+            state[1] = pinned
+        cost, g = state[0].eval(_dev.points(ctx, X[r0:]), want_grad=want_grad)
+        grad = None
+        if want_grad:
+            grad = np.zeros(X.size)
+            grad[r0 * X.shape[1]:] = np.asarray(g, dtype=float).ravel()
+        self._last = (key, cost, grad)
+        return cost, grad
+
+    def _has_gradient(self):
+        return self.gaussianProcess.kernel._spec().kind != _dev.K_MEHLER
+
+    def evaluate(self, inputPoints):
+        """|IVAR(design = inputPoints)|.  The gradient is computed in the same device call (where the kernel has one) and kept for
+        a `derivative` at the same design."""
+        return np.abs(self._eval(inputPoints, self._has_gradient())[0])
+
+    def derivative(self, inputPoints):
+        """d (signed IVAR) / d design coordinates, flattened (N*d,); the entries of the `pinnedPoints` leading points are ZEROS (the
+        parent's contract for pinned points)."""
+        if not self._has_gradient():
+            raise NotImplementedError("costFunctionVFE_IVAR.derivative: %s has no point derivative here (squared exponential and "
+                                      "isotropic Matern only)" % type(self.gaussianProcess.kernel).__name__)
+        return self._eval(inputPoints, True)[1].copy()
+
+    def evaluateWithDerivative(self, inputPoints):
+        """(|IVAR|, gradient of the signed IVAR) from one device call."""
+        g = self.derivative(inputPoints)
+        return np.abs(self._last[1]), g
 
 
 class costFunctionGP_MI(costFunctionBase):
@@ -344,7 +439,7 @@ class ExperimentalDesignGreedyWithDerivatives(ExperimentalDesignDerivative):
             nPointsPrev = nPointsAdded - self.nPointsBatch
             lbounds[0:nPointsPrev * self.nDims] = points.reshape((nPointsPrev * self.nDims))
             rbounds[0:nPointsPrev * self.nDims] = points.reshape((nPointsPrev * self.nDims))
-            currCost = costFunctionGP_IVAR(cf.gaussianProcess, nPointsAdded, cf.space, cf.version, mcPoints=cf.mcPoints)
+            currCost = type(cf)(cf.gaussianProcess, nPointsAdded, cf.space, cf.version, mcPoints=cf.mcPoints)
             currCost.pinnedPoints = nPointsPrev          # (large designs: cost and gradient touch the new batch's rows only)
             expCurr = ExperimentalDesignDerivative(currCost, nPointsAdded, self.nDims)
             expCurr.freeVariablesOnly = getattr(self, "freeVariablesOnly", False)

@@ -283,7 +283,8 @@ class GP:
         if self._vfe():
             raise NotImplementedError("%s is not offered on a VFE model (GP(..., sparse='vfe')): its objective is "
                                       "loglikeParams (the variational bound), its predictor evaluate(compvar=0/1) / "
-                                      "evaluateVariance" % what)
+                                      "evaluateVariance; the point derivatives of its variance are vfeVarianceGradient / "
+                                      "vfeVarianceGradientWRTnewpt, IVAR design on it costFunctionVFE_IVAR" % what)
 
     def _draw_fitcnodes(self, nodes):
         """The inducing points, unless set already: a random subset of the nodes (gp.py:186-189)."""
@@ -445,6 +446,34 @@ class GP:
         with the conventions of varianceGradient (reference's for squared exponential / 1-D Mehler, true for Matern)."""
         self._point_derivative_ready(newpt, referenceOnly=False)
         return self._var_grad_newpt(newpt)
+
+    # ---- the same two derivatives on a VFE model: of the variational variance, inducing points held fixed ------------------------
+    def _vfe_point_derivative_ready(self, name, newpt):
+        if not self._vfe():
+            raise ValueError("%s is the point derivative of the variational variance of VFE models (GP(..., FITC=fraction, "
+                             "sparse='vfe')); on a dense or FITC model use varianceGradient / varianceGradientWRTnewpt" % name)
+        if self.kernel._spec().kind == _dev.K_MEHLER:
+            raise NotImplementedError("%s: %s has no point derivative here (squared exponential and isotropic Matern only)"
+                                      % (name, type(self.kernel).__name__))
+        if self.pts is None or self._fitc is None:
+            raise NotImplementedError("%s needs a fitted model: set the nodes first (addNodesAndComputeCovariance / train)" % name)
+        assert newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
+
+    def vfeVarianceGradient(self, newpt):
+        """out[k*d+l, j] = d var(newpt_j) / d pts[k, l], (N*d, M) in evaluateVarianceDerivative's layout, of the variational
+        posterior variance `evaluateVariance` returns on a VFE model (gpx_vfe_var_grad).  TRUE derivatives for every kernel -- no
+        doubled signalSize for the squared exponential -- with `fitcnodes` held fixed, also where a node coincides with one.
+        ValueError on a dense or FITC model, NotImplementedError for a Mehler kernel or before any nodes are set."""
+        self._vfe_point_derivative_ready("vfeVarianceGradient", newpt)
+        ctx = _dev.context()
+        return self._fitc.design_var_grad(self.kernel._spec(), self._fitc.X, self._fitc.S, _dev.points(ctx, newpt))
+
+    def vfeVarianceGradientWRTnewpt(self, newpt):
+        """d var(newpt_i) / d newpt_i, flattened (M*d,), of the variational posterior variance (gpx_vfe_var_grad_newpt): TRUE
+        derivatives, `fitcnodes` held fixed.  Errors as vfeVarianceGradient."""
+        self._vfe_point_derivative_ready("vfeVarianceGradientWRTnewpt", newpt)
+        ctx = _dev.context()
+        return self._fitc.design_var_grad_newpt(self._fitc.S, _dev.points(ctx, newpt))
 
     def generateSamples(self, x, noise=1e-10):
         raise NotImplementedError("generateSamples (SVD sampling, gp.py:343-371) is outside the GPU hot path")

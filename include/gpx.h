@@ -480,6 +480,50 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
                       int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie,
                       double* all_costs);
 
+/* ---- IVAR design on a VFE model, in the inducing space (none in the reference) -----------------------------------------------------
+ * With k_u(.) = K(S, .), Quu = K(S,S) + noise I = Lu Lu^T and, for design points X, A = Quu + sum_i k_u(x_i) k_u(x_i)^T / noise =
+ * La La^T, the variational variance is var(z) = k(z,z) - k_u(z)^T Quu^-1 k_u(z) + k_u(z)^T A^-1 k_u(z): the design enters through the
+ * nu x nu matrix A only and the M Monte-Carlo points Z through one Gram matrix Gz = K(S,Z) K(Z,S) / M.  With kbar = mean_z k(z,z):
+ *     IVAR(X)       = kbar - tr(Lu^-1 Gz Lu^-T) + tr(La^-1 Gz La^-T)                                   (signed, not clamped)
+ *     dIVAR/dx_i[l] = -(2 / noise) sum_u H[u][i] dk(x_i, s_u)/dx_i[l],      H = A^-1 Gz A^-1 K(S,X)
+ * dk is the TRUE derivative (the table of gpx_fitc_lml_grad_inducing and gpx_vfe_acq_grad; for the squared exponential too: no doubled
+ * signalSize).  The inducing points are constants of the function, also where a design point coincides with one (the derivative of
+ * every radial kernel is zero and smooth there).  No observations are involved: the state is built from the kernel, S, the noise and
+ * Z alone.
+ * gpx_vfe_design_create: Lu, Gz, A0 = Quu stay on the device (three nu x nu matrices) with kbar and c0 = tr(Lu^-1 Gz Lu^-T).  Gz is
+ *   accumulated over chunks of Z under GPX_CROSS_BYTES (one nu x chunk matrix, as gpx_vfe_posterior), the chunks added in index order,
+ *   then scaled and mirrored: 2 nu^2 M flops; another chunking may differ in the last bits of Gz (another summation order).  Every
+ *   kernel kind.  noise <= 0, M < 1, nu < 1: argument errors.  S is copied; Z is not kept.
+ * gpx_vfe_design_pin: REPLACES the pinned set (it does not accumulate): A0 = Quu + K(S,Xp) K(Xp,S) / noise, 2 nu^2 p flops.  Xp NULL or
+ *   of 0 rows: nothing pinned.
+ * gpx_vfe_design_eval: the cost of (pinned points + the b >= 1 free points Xf) and, when grad != NULL (host b x d, grad[i*d + l]), its
+ *   gradient w.r.t. Xf.  A = A0 + P P^T / noise with P = K(S,Xf), La = chol(A) (gpx_potrf's path and pivot policy: a bad pivot is
+ *   returned > 0), Y1 = La^-1 Gz La^-T, cost = kbar - c0 + tr Y1; gradient: V = La^-1 P, H = La^-T (Y1 V) -- A^-1 Gz A^-1 is not formed --
+ *   and one row pass over the b x nu pairs.  nu^3 / 3 + 2 nu^3 + 2 nu^2 b flops, with the gradient 6 nu^2 b + (6 d + 25) b nu more:
+ *   independent of M and of the pinned count.  Work memory: two nu x nu matrices (three from order 2048) and two nu x b ones.  The
+ *   gradient exists for the squared exponential and the Materns; on a Mehler state grad != NULL is an argument error that names the
+ *   kernel (the cost works).  The state is not modified.
+ * Fixed-order reductions, no atomics: two calls with the same arguments return the same bits. */
+typedef struct gpx_vfe_design gpx_vfe_design;
+int gpx_vfe_design_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* S, double noise, const gpx_mat* Z,
+                          gpx_vfe_design** out);
+int gpx_vfe_design_pin(gpx_ctx* ctx, gpx_vfe_design* ds, const gpx_mat* Xp);
+int gpx_vfe_design_eval(gpx_ctx* ctx, const gpx_vfe_design* ds, const gpx_mat* Xf, double* cost, double* grad);
+/* each output nullable: inducing points, Monte-Carlo points, points currently pinned */
+int gpx_vfe_design_shape(const gpx_vfe_design* ds, int64_t* nu, int64_t* m, int64_t* pinned);
+int gpx_vfe_design_free(gpx_ctx* ctx, gpx_vfe_design* ds);
+/* Point-wise derivatives of the variational variance of a fitted VFE model (a FITC model is refused with the call to use instead:
+ * gpx_fitc_var_grad / gpx_fitc_var_grad_newpt); squared exponential and Materns only; TRUE derivatives, S held fixed.
+ * gpx_vfe_var_grad: out (host, (N d) x M): out[(k*d + l)*M + j] = d var(z_j)/dx_k[l] = -(2 / noise) E[k][j] D_l[k][j] with C = A^-1 K(S,Z)
+ *   (two sweeps with the model's La), E = K(X,S) C, D_l = (dK(X,S)/dx[l]) C.  (kind, d, hyp), X, S: the model's, as gpx_vfe_grad.  Chunked
+ *   over Z under GPX_CROSS_BYTES; (d + 1) products of 2 N nu chunk flops per chunk; bound by the copy of its 8 N d M bytes to the host,
+ *   as gpx_var_grad.
+ * gpx_vfe_var_grad_newpt: out (host, M x d): out[j*d + l] = d var(z_j)/dz_j[l] = -2 sum_u dk(z_j,s_u)/dz_j[l] gamma(z_j)[u], gamma =
+ *   Quu^-1 k_u - A^-1 k_u: gpx_vfe_acq_grad's own sequence with (a, b) = (0, 1). */
+int gpx_vfe_var_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X, const gpx_mat* S,
+                     const gpx_mat* Z, double* out);
+int gpx_vfe_var_grad_newpt(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* out);
+
 /* ---- measurement ------------------------------------------------------------------------------- */
 /* when enabled every kernel launch of a class is bracketed by HIP events on the launch stream */
 int gpx_profile_enable(gpx_ctx* ctx, int on);

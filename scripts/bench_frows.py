@@ -3,7 +3,7 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo] [--kernel se,matern52] [--out FILE]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo,vfedesign] [--kernel se,matern52] [--out FILE]
 
 --kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
 matern52; default se) -- the other entries keep their own kernels.
@@ -501,3 +501,73 @@ if want("loo"):
         with open(sys.argv[sys.argv.index("--out") + 1], "a") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+# ---- vfedesign: IVAR design on a VFE model in the inducing space (gpx_vfe_design_*; none in the reference).  The cost is compared
+# with the path that existed before it -- gpx_vfe_fit on the N design points, then gpx_vfe_posterior's variances at the M MC points and
+# a host mean: what costFunctionGP_IVAR.evaluate does on a VFE model -- at the same shapes in this run, ALTERNATING, seven samples of
+# ten calls each (min..max per call).  The gradient had no predecessor: its time stands against the flop model.
+# --vfedesign-out: where the lines go (default profiles/vfe_design_frows.json).
+if want("vfedesign"):
+    from gpExp.kernels import KernelIsoMatern
+    nuv, Mv, Nv, pinv = (512, 8192, 1024, 960) if quick else (1024, 32768, 4096, 4032)
+    dv, bv = 8, Nv - pinv
+    rv = np.random.default_rng(1024)
+    kspv = KernelIsoMatern(1.5, 1.0, dv, nu=2.5)._spec()
+    Xv, Zv = rv.uniform(-1, 1, (Nv, dv)), rv.uniform(-1, 1, (Mv, dv))
+    Sv = Xv[rv.permutation(Nv)[:nuv]].copy()
+    Xd, Sd, Zd = dev.points(ctx, Xv), dev.points(ctx, Sv), dev.points(ctx, Zv)
+    Xpd, Xfd_ = dev.points(ctx, Xv[:pinv]), dev.points(ctx, Xv[pinv:])
+
+    def per_call(f, calls=10):
+        def run():
+            for _ in range(calls):
+                out = f()
+            return out
+        return run
+
+    def samples(f, g=None, reps=7, calls=10):
+        """(min, max) seconds per call of f (and of g, alternating with it)."""
+        tf, tg = [], []
+        for _ in range(reps):
+            tf.append(best(per_call(f, calls), reps=1)[1] / calls)
+            if g is not None:
+                tg.append(best(per_call(g, calls), reps=1)[1] / calls)
+        return ((min(tf), max(tf)), (min(tg), max(tg))) if g is not None else (min(tf), max(tf))
+
+    def old_cost():
+        return float(np.mean(dev.VfeModel(ctx, kspv, Xd, Sd, 0.05).posterior(None, Zd, want_mean=False)[1]))
+
+    size = dict(nu=nuv, M=Mv, N=Nv, d=dv, kernel="Matern-5/2")
+    dev.VfeDesign(ctx, kspv, Sd, 0.05, Zd)                    # warm: pools, code objects
+    c0, c1 = samples(lambda: dev.VfeDesign(ctx, kspv, Sd, 0.05, Zd), calls=3)
+    ds = dev.VfeDesign(ctx, kspv, Sd, 0.05, Zd)
+    vd = [report("gpx_vfe_design_create", "none in the reference", size, c0, flops=2.0 * nuv * nuv * Mv + 7.0 * nuv ** 3 / 3.0,
+                 note="chol(Quu), Gz by SYRK over the chunks of Z (2 nu^2 M), the two-sided solve for c0; %.2f..%.2f ms" % (1e3 * c0, 1e3 * c1))]
+    model = nuv ** 3 * (1.0 / 3.0 + 2.0)
+    old_model = 2.0 * nuv * nuv * Nv + nuv ** 3 / 3.0 + 2.0 * nuv * nuv * Mv
+    for label, pinned, Xe, b in (("all %d free" % Nv, None, Xd, Nv), ("%d pinned + %d free" % (pinv, bv), Xpd, Xfd_, bv)):
+        ds.pin(pinned)
+        new, old = ds.eval(Xe, want_grad=False)[0], old_cost()            # warm both sides, and the values agree
+        assert abs(new - old) <= 1e-8, (new, old)
+        (n0, n1), (o0, o1) = samples(lambda: ds.eval(Xe, want_grad=False), old_cost)
+        vd.append(report("gpx_vfe_design_eval (cost, %s)" % label, "gpx_vfe_fit + gpx_vfe_posterior + host mean", dict(size, b=b), n0,
+                         flops=model + 2.0 * nuv * nuv * b,
+                         note="alternating with the earlier path, seven samples of ten calls: new %.3f..%.3f ms, earlier %.3f..%.3f ms, "
+                              "ratio earlier / new of the minima %.2f (flop model %.3e against %.3e: %.2f); |difference of the "
+                              "values| %.1e" % (1e3 * n0, 1e3 * n1, 1e3 * o0, 1e3 * o1, o0 / n0, model + 2.0 * nuv * nuv * b,
+                                                old_model, old_model / (model + 2.0 * nuv * nuv * b), abs(new - old))))
+        ds.eval(Xe)
+        g0, g1 = samples(lambda: ds.eval(Xe))
+        rows = (6.0 * dv + 25.0) * b * nuv
+        vd.append(report("gpx_vfe_design_eval (cost + gradient, %s)" % label, "none in the reference", dict(size, b=b), g0,
+                         flops=model + 8.0 * nuv * nuv * b + rows,
+                         note="nu^3/3 + 2 nu^3 + 2 nu^2 b for the cost, 6 nu^2 b + the row pass's (6 d + 25) b nu = %.3e more; seven samples "
+                              "of ten calls: %.3f..%.3f ms; over the cost alone in this run: %.2f x" % (rows, 1e3 * g0, 1e3 * g1, g0 / n0)))
+    p0, p1 = samples(lambda: ds.pin(Xpd))
+    vd.append(report("gpx_vfe_design_pin", "none in the reference", dict(size, pinned=pinv), p0, flops=2.0 * nuv * nuv * pinv,
+                     note="once per batch: %.3f..%.3f ms" % (1e3 * p0, 1e3 * p1)))
+    path = sys.argv[sys.argv.index("--vfedesign-out") + 1] if "--vfedesign-out" in sys.argv else \
+        os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vfe_design_frows.json")
+    with open(path, "w") as f:
+        json.dump(vd, f, indent=1)
+        f.write("\n")
