@@ -22,7 +22,11 @@
 //     Matern52  dk/dz   = -sig (5 / (3 rho^2)) (1 + t) e^-t (z - x)  t = sqrt(5) |z - x| / rho
 // all smooth at z = x.  Where var == 0 exactly, a and b are NaN, and so is the gradient row.
 // The same three calls on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad, gpx_vfe_acq_batch) are at the end of this file: the cost
-// formula, the epilogue, the arg-min and -- as further instantiations -- the gradient, pick and batch kernels are these.
+// formula, the epilogue, the arg-min and -- as further instantiations -- the gradient, pick and batch kernels are these.  So is the
+// host code around them: AcqOut is the result side of the candidate-wise calls (scratch, epilogue launch, arg-min, copies) and
+// AcqBatchState + acq_batch_picks the pick loop of the q-batch calls; acq_impl / vfe_acq_impl and acq_batch_impl /
+// vfe_acq_batch_impl hold what differs -- the posterior chunk with its transposes and backward solves, and the set-up that fills
+// the resident W.  Every forward solve of a cross matrix goes through chol_cross_solve (chol.hip: the one in-place / out-of-place rule).
 #include "gpx_device.h"
 #include <math.h>
 
@@ -177,6 +181,53 @@ int launch_acq_grad(gpx_ctx* ctx, const KParams& kp, const double* X, int64_t n,
   return 0;
 }
 
+// The result side of the candidate-wise calls, dense (acq_impl) and VFE (vfe_acq_impl): the costs of all M candidates, one arg-min
+// partial per ACQ_EPI of them, the winner's slots and -- for a gradient -- the (a, b) of one chunk and the M x d result.
+struct AcqOut {
+  int64_t M = 0, d = 0, nparts = 0;
+  double *cost = nullptr, *part_c = nullptr, *best_c = nullptr, *coef = nullptr, *grad = nullptr;
+  int64_t *part_i = nullptr, *best_i = nullptr;
+
+  int take(Scratch& sc, int64_t M_, int64_t mc_alloc, int64_t d_, bool want_grad) {
+    M = M_;
+    d = d_;
+    nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+    GPX_TRY(sc.get(M * 8, &cost));
+    GPX_TRY(sc.get(nparts * 8, &part_c));
+    GPX_TRY(sc.get(nparts * 8, &part_i));
+    GPX_TRY(sc.get(8, &best_c));
+    GPX_TRY(sc.get(8, &best_i));
+    if (want_grad) {
+      GPX_TRY(sc.get(2 * mc_alloc * 8, &coef));
+      GPX_TRY(sc.get(M * d * 8, &grad));
+    }
+    return 0;
+  }
+  // the chunk [j0, j0 + mc): ssq == NULL: kd IS the signed variance (the VFE predictor's); prof_bytes: the caller's own bracket
+  int epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* kd, const double* ssq, int64_t mc, int64_t j0,
+               double prof_bytes) {
+    ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, prof_bytes);
+    hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
+                       param, mean, kd, ssq, mc, j0, cost, coef, part_c, part_i);
+    GPX_HIP(hipGetLastError());
+    return 0;
+  }
+  // the arg-min over all chunks (when wanted) and the copies to the host, queued: the caller's Scratch waits for them
+  int finish(gpx_ctx* ctx, double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
+    if (best || best_cost) {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
+      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)part_c, (const int64_t*)part_i,
+                         nparts, best_c, best_i);
+      GPX_HIP(hipGetLastError());
+      if (best) GPX_HIP(hipMemcpyAsync(best, best_i, 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, best_c, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, cost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_host) GPX_HIP(hipMemcpyAsync(grad_host, grad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+  }
+};
+
 // Shared body of gpx_acq / gpx_acq_grad.  cost_host (M), grad_host (M x d) nullable; best / best_cost nullable.
 int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Z,
              int acq, double param, double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
@@ -184,16 +235,14 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
   const bool grad = grad_host != nullptr;
   const int64_t mcmax = gpx_eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  // the same solve as posterior_impl: from 2048 training points out of place through the block inverses
-  const bool oop = np >= 2048;
+  const bool oop = chol_cross_oop(np);   // the same solve as posterior_impl
   const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
   const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
   const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
-  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
   const int64_t bytesT = (grad && np >= 4096) ? mc_alloc * chol_binv_order(np) * 8 : 0;
   double *pB = nullptr, *pW = nullptr, *pT = nullptr, *pal = nullptr, *pmean = nullptr, *pout = nullptr, *ppart = nullptr;
-  double *pkd = nullptr, *pcost = nullptr, *pcoef = nullptr, *pgrad = nullptr, *ppc = nullptr, *pbc = nullptr;
-  int64_t *ppi = nullptr, *pbi = nullptr;
+  double* pkd = nullptr;
+  AcqOut out;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
   GPX_TRY(sc.get(bytesB, &pB));
   if (oop || grad) GPX_TRY(sc.get(bytesB, &pW));
@@ -203,15 +252,7 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
   GPX_TRY(sc.get(bytes_out, &pout));
   GPX_TRY(sc.get(bytes_out, &pkd));
   GPX_TRY(sc.get(bytes_part, &ppart));
-  GPX_TRY(sc.get(M * 8, &pcost));
-  GPX_TRY(sc.get(nparts * 8, &ppc));
-  GPX_TRY(sc.get(nparts * 8, &ppi));
-  GPX_TRY(sc.get(8, &pbc));
-  GPX_TRY(sc.get(8, &pbi));
-  if (grad) {
-    GPX_TRY(sc.get(2 * bytes_out, &pcoef));
-    GPX_TRY(sc.get(M * d * 8, &pgrad));
-  }
+  GPX_TRY(out.take(sc, M, mc_alloc, d, grad));
   GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
   GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
@@ -223,12 +264,7 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     // gpx_posterior's own per-chunk step: the values equal GP.evaluate's
     GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Zc, mc, B, oop ? pW : nullptr, pal, pmean, nullptr, pout, pkd, ppart));
     double* Wsol = oop ? pW : B;
-    {
-      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 5.0 * (double)mc);
-      hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
-                         param, (const double*)pmean, (const double*)pkd, (const double*)pout, mc, j0, pcost, pcoef, ppc, ppi);
-      GPX_HIP(hipGetLastError());
-    }
+    GPX_TRY(out.epilogue(ctx, acq, param, pmean, pkd, pout, mc, j0, 8.0 * 5.0 * (double)mc));
     if (!grad) continue;
     // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
     double* Bt = Wsol == B ? pW : B;
@@ -237,19 +273,9 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     else GPX_TRY(chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np));
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
                  8.0 * ((double)n * (double)mc + (double)n * d));
-    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, nullptr, np, pal, pcoef, pgrad + j0 * d));
+    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, nullptr, np, pal, out.coef, out.grad + j0 * d));
   }
-  if (best || best_cost) {
-    ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
-    hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                       pbc, pbi);
-    GPX_HIP(hipGetLastError());
-    if (best) GPX_HIP(hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (grad_host) GPX_HIP(hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream));
-  return 0;
+  return out.finish(ctx, cost_host, best, best_cost, grad_host);
 }
 
 // the acquisition entries' own checks in front of the shared prologue
@@ -272,12 +298,6 @@ int acq_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const g
 
 // scalars of the current pick, written by acq_pick_kernel, read by acq_batch_kernel
 enum { SC_DELTA = 0, SC_MU = 1, SC_LIE = 2, SC_PARAM = 3, SC_LIVE = 4, SC_N = 8 };
-
-__global__ __launch_bounds__(256) void acq_batch_v_kernel(const double* __restrict__ kd, const double* __restrict__ ss, int64_t M,
-                                                          double* __restrict__ v) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < M) v[j] = kd[j] - ss[j];
-}
 
 // pick `cur` = candidate s: its column of W_C (w, np), its coordinates along the earlier picks (uc, cur), the pick's scalars,
 // and the mask.  Reads mu / v / U only: the state is changed by the NEXT acq_batch_kernel.
@@ -351,100 +371,129 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
   }
 }
 
+// The state of the pick loop, dense (acq_batch_impl) and VFE (vfe_acq_batch_impl), beside the resident W the caller fills: the
+// rows U of the earlier picks, mu, v (dense: the signed variance; VFE: t), rfix (VFE only: r), hd (a column sum of squares of the
+// set-up, then h of every pick), kd = k(c, c), the costs with their arg-min partials and winner slots, the scalars of the pick, its
+// coordinates uc along the earlier picks, its column w of W, the mask, and the partial sums of the column reductions.
+struct AcqBatchState {
+  int64_t M = 0, Mp = 0, nparts = 0;
+  double *U = nullptr, *mu = nullptr, *v = nullptr, *rfix = nullptr, *hd = nullptr, *kd = nullptr, *part = nullptr;
+  double *cost = nullptr, *part_c = nullptr, *best_c = nullptr, *sc = nullptr, *uc = nullptr, *w = nullptr;
+  int64_t *part_i = nullptr, *best_i = nullptr;
+  int* mask = nullptr;
+  double sc0[SC_N];   // (lives as long as the call: the copy of the scalars is queued from it)
+
+  // prows: the padded row count of W (np, or nup on a VFE model)
+  int take(Scratch& s, int64_t M_, int64_t prows, int64_t q, bool vfe) {
+    M = M_;
+    Mp = gpx_round_up(M, GPX_TILE);
+    nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
+    const int64_t bytesM = Mp * 8;
+    GPX_TRY(s.get(q * Mp * 8, &U));
+    GPX_TRY(s.get(bytesM, &mu));
+    GPX_TRY(s.get(bytesM, &v));
+    if (vfe) GPX_TRY(s.get(bytesM, &rfix));
+    GPX_TRY(s.get(bytesM, &kd));
+    GPX_TRY(s.get(bytesM, &hd));
+    GPX_TRY(s.get(colreduce_partial_elems(prows, Mp) * 8 + 8, &part));
+    GPX_TRY(s.get(M * 8, &cost));
+    GPX_TRY(s.get(nparts * 8, &part_c));
+    GPX_TRY(s.get(nparts * 8, &part_i));
+    GPX_TRY(s.get(8, &best_c));
+    GPX_TRY(s.get(8, &best_i));
+    GPX_TRY(s.get(SC_N * 8, &sc));
+    GPX_TRY(s.get(q * 8, &uc));
+    GPX_TRY(s.get((prows > q ? prows : q) * 8, &w));
+    GPX_TRY(s.get(Mp * 4, &mask));
+    return 0;
+  }
+  // nothing picked yet, param as the caller gave it: queued before the set-up
+  int init(gpx_ctx* ctx, double param) {
+    for (int i = 0; i < SC_N; ++i) sc0[i] = 0.0;
+    sc0[SC_PARAM] = param;
+    GPX_HIP(hipMemsetAsync(mask, 0, (size_t)Mp * 4, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(sc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+  }
+};
+
+// The q picks on a state whose set-up is done (mu, v, rfix, kd filled; W = the resident rows x M matrix, row stride ld, prows
+// padded rows).  `who` opens the error text.
+template <bool VFE>
+int acq_batch_picks(gpx_ctx* ctx, const KParams& kp, int acq, const gpx_mat* Cm, AcqBatchState& st, const double* W, int64_t ld,
+                    int64_t rows, int64_t prows, double noise, int track_best, int lie, double lie_value, int64_t q,
+                    int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs, const char* who) {
+  const int64_t M = st.M, Mp = st.Mp;
+  const dim3 gEpi((unsigned)st.nparts), gPick((unsigned)(((prows > q ? prows : q) + 255) / 256));
+  int64_t s = -1;
+  for (int64_t t = 0; t < q; ++t) {
+    {
+      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
+      hipLaunchKernelGGL(acq_batch_kernel<VFE>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M,
+                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)st.sc, (const double*)st.uc, (const double*)st.hd, st.U, Mp,
+                         st.mu, st.v, (const double*)st.rfix, (const int*)st.mask, st.cost, st.part_c, st.part_i);
+      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)st.part_c,
+                         (const int64_t*)st.part_i, st.nparts, st.best_c, st.best_i);
+    }
+    double c = 0.0;
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpyAsync(&s, st.best_i, 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipMemcpyAsync(&c, st.best_c, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (all_costs) GPX_HIP(hipMemcpyAsync(all_costs + t * M, st.cost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GPX_HIP(hipStreamSynchronize(ctx->stream));
+    if (s < 0 || s >= M) {
+      gpx_set_error("%s: pick %lld of %lld: no candidate has a non-NaN cost", who, (long long)(t + 1), (long long)q);
+      return -1;
+    }
+    out_idx[t] = s;
+    if (out_cost) out_cost[t] = c;
+    if (t + 1 == q && !out_lie) break;
+    hipLaunchKernelGGL(acq_pick_kernel<VFE>, gPick, dim3(256), 0, ctx->stream, W, ld, prows, s, (const double*)st.U, Mp, (int)t,
+                       (const double*)st.mu, (const double*)st.v, VFE ? (const double*)nullptr : (const double*)st.kd, noise, lie,
+                       lie_value, track_best, st.sc, st.uc, st.w, st.mask);
+    GPX_HIP(hipGetLastError());
+    if (out_lie) GPX_HIP(hipMemcpyAsync(out_lie + t, st.sc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (t + 1 == q) break;
+    GPX_TRY(launch_colreduce(ctx, W, ld, rows, Mp, st.w, st.hd, st.part));
+  }
+  return 0;
+}
+
 int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Cm,
                    double noise, int acq, double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx,
                    double* out_cost, double* out_lie, double* all_costs) {
   const int64_t n = L->rows, np = L->prows, M = Cm->rows, d = kp.d;
   const int64_t Mp = gpx_round_up(M, GPX_TILE), ld = gpx_skew_ld(Mp);
-  // the solve of gpx_acq: in place below 2048 training points, above out of place through the block inverses, the cross matrix
-  // chunk by chunk into the resident W_C
-  const bool oop = np >= 2048;
+  // the solve of gpx_acq (chol_cross_solve), the cross matrix chunk by chunk into the resident W_C
+  const bool oop = chol_cross_oop(np);
   const int64_t mcmax = gpx_round_up(gpx_eval_chunk(np), GPX_TILE);
   const int64_t mcw = Mp < mcmax ? Mp : mcmax, ldb = gpx_skew_ld(mcw);
-  const int64_t bytesW = np * ld * 8, bytesB = oop ? np * ldb * 8 : 0, bytesU = q * Mp * 8, bytesM = Mp * 8;
-  const int64_t bytes_part = colreduce_partial_elems(np, Mp) * 8 + 8;
-  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
-  const int64_t bytes_w = (np > q ? np : q) * 8;
-  double *pW = nullptr, *pB = nullptr, *pU = nullptr, *pal = nullptr, *pmu = nullptr, *pv = nullptr, *pkd = nullptr, *pss = nullptr;
-  double *ppart = nullptr, *pcost = nullptr, *ppc = nullptr, *pbc = nullptr, *psc = nullptr, *puc = nullptr, *pw = nullptr;
-  int64_t *ppi = nullptr, *pbi = nullptr;
-  int* pmask = nullptr;
+  double *Wc = nullptr, *pB = nullptr, *pal = nullptr;
+  AcqBatchState st;
   Scratch sc(ctx);
-  const dim3 gEpi((unsigned)nparts), gM((unsigned)((M + 255) / 256));
-  const dim3 gPick((unsigned)(((np > q ? np : q) + 255) / 256));
-  GPX_TRY(sc.get(bytesW, &pW));
-  if (oop) GPX_TRY(sc.get(bytesB, &pB));
-  GPX_TRY(sc.get(bytesU, &pU));
+  GPX_TRY(sc.get(np * ld * 8, &Wc));
+  if (oop) GPX_TRY(sc.get(np * ldb * 8, &pB));
   GPX_TRY(sc.get(np * 8, &pal));
-  GPX_TRY(sc.get(bytesM, &pmu));
-  GPX_TRY(sc.get(bytesM, &pv));
-  GPX_TRY(sc.get(bytesM, &pkd));
-  GPX_TRY(sc.get(bytesM, &pss));    // |W_C[:, j]|^2 at the set-up, then h of every pick
-  GPX_TRY(sc.get(bytes_part, &ppart));
-  GPX_TRY(sc.get(M * 8, &pcost));
-  GPX_TRY(sc.get(nparts * 8, &ppc));
-  GPX_TRY(sc.get(nparts * 8, &ppi));
-  GPX_TRY(sc.get(8, &pbc));
-  GPX_TRY(sc.get(8, &pbi));
-  GPX_TRY(sc.get(SC_N * 8, &psc));
-  GPX_TRY(sc.get(q * 8, &puc));
-  GPX_TRY(sc.get(bytes_w, &pw));
-  GPX_TRY(sc.get(Mp * 4, &pmask));
-  double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
+  GPX_TRY(st.take(sc, M, np, q, false));
   GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
   GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  GPX_HIP(hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream));
-  double *Wc = pW, *U = pU, *mu = pmu, *v = pv, *hd = pss;
+  GPX_TRY(st.init(ctx, param));
   // ---- set-up: the posterior pass with W kept.  Not gpx_posterior_chunk: the solve lands in the resident W_C with ITS row
-  // stride, and the squares are reduced once over all of W_C ----
+  // stride, and the squares are reduced once over all of W_C (into hd) ----
   for (int64_t j0 = 0; j0 < Mp; j0 += mcw) {
     const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
     const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
     double* B = oop ? pB : Wc + j0;
     const int64_t ldc = oop ? gpx_skew_ld(mcp) : ld;
     GPX_TRY(launch_kfill(ctx, kp, X->p, n, Cm->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, np, mcp, ldc));
-    GPX_TRY(launch_colreduce(ctx, B, ldc, n, mcp, pal, mu + j0, ppart));
-    if (oop) GPX_TRY(chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldc, Wc + j0, ld, mcp));
-    else GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldc, np, mcp));
+    GPX_TRY(launch_colreduce(ctx, B, ldc, n, mcp, pal, st.mu + j0, st.part));
+    GPX_TRY(chol_cross_solve(ctx, L, B, ldc, oop ? Wc + j0 : nullptr, ld, mcp));
   }
-  GPX_TRY(launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, hd, ppart));
-  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, pkd));
-  hipLaunchKernelGGL(acq_batch_v_kernel, gM, dim3(256), 0, ctx->stream, (const double*)pkd, (const double*)hd, M, v);
-  GPX_HIP(hipGetLastError());
-  // ---- the picks ----
-  int64_t s = -1;
-  for (int64_t t = 0; t < q; ++t) {
-    {
-      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
-      hipLaunchKernelGGL(acq_batch_kernel<false>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M,
-                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)hd, U, Mp, mu, v,
-                         (const double*)nullptr, (const int*)pmask, pcost, ppc, ppi);
-      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                         pbc, pbi);
-    }
-    double c = 0.0;
-    GPX_HIP(hipGetLastError());
-    GPX_HIP(hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (all_costs) GPX_HIP(hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipStreamSynchronize(ctx->stream));
-    if (s < 0 || s >= M) {
-      gpx_set_error("acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
-      return -1;
-    }
-    out_idx[t] = s;
-    if (out_cost) out_cost[t] = c;
-    if (t + 1 == q && !out_lie) break;
-    hipLaunchKernelGGL(acq_pick_kernel<false>, gPick, dim3(256), 0, ctx->stream, (const double*)Wc, ld, np, s, (const double*)U, Mp,
-                       (int)t, (const double*)mu, (const double*)v, (const double*)pkd, noise, lie, lie_value, track_best,
-                       psc, puc, pw, pmask);
-    GPX_HIP(hipGetLastError());
-    if (out_lie) GPX_HIP(hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (t + 1 == q) break;
-    GPX_TRY(launch_colreduce(ctx, Wc, ld, n, Mp, pw, hd, ppart));
-  }
-  return 0;
+  GPX_TRY(launch_colreduce(ctx, Wc, ld, n, Mp, nullptr, st.hd, st.part));
+  GPX_TRY(launch_kdiag(ctx, kp, Cm->p, M, st.kd));
+  GPX_TRY(launch_vec_sub(ctx, st.kd, st.hd, M, st.v));
+  return acq_batch_picks<false>(ctx, kp, acq, Cm, st, Wc, ld, n, np, noise, track_best, lie, lie_value, q, out_idx, out_cost,
+                                out_lie, all_costs, "acq batch");
 }
 
 }  // namespace
@@ -453,8 +502,8 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
 // Notation of fitc.hip: S the nu inducing points, Quu = K(S,S) + noise I = Lu Lu^T, A = Quu + Kuf Kfu / noise = La La^T,
 // beta_u = Quu^-1 Kuf alpha, k_u(z) = K(S, z);  mean = k_u^T beta_u,  var = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2.
 //
-// Values: vfe_posterior_chunk (gpx_vfe_posterior's own per-chunk step), then acq_epilogue_kernel on the signed variance it leaves and
-// acq_argmin_kernel.  Gradient, with (a, b) from that epilogue:
+// Values: vfe_posterior_chunk (gpx_vfe_posterior's own per-chunk step), then AcqOut's epilogue on the signed variance it leaves
+// (ssq == NULL) and its arg-min.  Gradient, with (a, b) from that epilogue:
 //     gamma(z) = Quu^-1 k_u - A^-1 k_u,     grad_z A = sum_u dk(z, s_u)/dz (a beta_u[u] - 2 b gamma(z)[u])
 // The two forward solves of the values stay (Wu = Lu^-1 k_u, Wa = La^-1 k_u: FOUR nu x chunk buffers instead of two or three), each
 // is transposed and swept backward from the right (Wu^T Lu^-1, Wa^T La^-1: acq_impl's pattern, the nu-axis contiguous per
@@ -470,12 +519,10 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
   const int64_t mcmax = gpx_eval_chunk(nup);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  const bool oop = nup >= 2048;   // the predictor's rule
+  const bool oop = chol_cross_oop(nup);
   const int64_t bytesB = nup * gpx_skew_ld(mc_alloc) * 8, bytes_out = mc_alloc * 8;
-  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
-  double *B1, *B2, *Wu = nullptr, *Wa = nullptr, *part, *pm, *su, *sa, *kd, *pv, *bu, *pcost, *ppc, *pbc;
-  double *pcoef = nullptr, *pgrad = nullptr;
-  int64_t *ppi, *pbi;
+  double *B1, *B2, *Wu = nullptr, *Wa = nullptr, *part, *pm, *su, *sa, *kd, *pv, *bu;
+  AcqOut out;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
   GPX_TRY(sc.get(bytesB, &B1));
   GPX_TRY(sc.get(bytesB, &B2));
@@ -487,15 +534,7 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
   GPX_TRY(sc.get(bytes_out, &sa));
   GPX_TRY(sc.get(bytes_out, &kd));
   GPX_TRY(sc.get(bytes_out, &pv));
-  GPX_TRY(sc.get(M * 8, &pcost));
-  GPX_TRY(sc.get(nparts * 8, &ppc));
-  GPX_TRY(sc.get(nparts * 8, &ppi));
-  GPX_TRY(sc.get(8, &pbc));
-  GPX_TRY(sc.get(8, &pbi));
-  if (grad) {
-    GPX_TRY(sc.get(2 * bytes_out, &pcoef));
-    GPX_TRY(sc.get(M * d * 8, &pgrad));
-  }
+  GPX_TRY(out.take(sc, M, mc_alloc, d, grad));
   if (coeff) {
     GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
   } else {   // (GPX_ACQ_VARIANCE: no mean; its weight a is 0)
@@ -509,12 +548,7 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
     // values only: both out-of-place solutions land in the one buffer, as in gpx_vfe_posterior
     GPX_TRY(vfe_posterior_chunk(ctx, f, kpz, S, Zc, mc, B1, B2, oop ? Wu : nullptr, oop ? (grad ? Wa : Wu) : nullptr, bu, pm, su,
                                 sa, kd, pv, part));
-    {
-      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * 4.0 * (double)mc);
-      hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
-                         param, (const double*)pm, (const double*)pv, (const double*)nullptr, mc, j0, pcost, pcoef, ppc, ppi);
-      GPX_HIP(hipGetLastError());
-    }
+    GPX_TRY(out.epilogue(ctx, acq, param, pm, pv, nullptr, mc, j0, 8.0 * 4.0 * (double)mc));
     if (!grad) continue;
     // (Quu^-1 k_u)^T = Wu^T Lu^-1 and (A^-1 k_u)^T = Wa^T La^-1 (mcp x nup, row stride nup), in the two buffers the forward
     // solutions do not occupy
@@ -526,19 +560,9 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
     GPX_TRY(chol_trsm_right_n(ctx, fv.La->p, fv.La->ld, fv.La->aux, Ta, nup, mcp, nup));
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nu * (double)mc * (6.0 * (double)d + 26.0),
                  8.0 * (2.0 * (double)nu * (double)mc + (double)nu * d));
-    GPX_TRY(launch_acq_grad(ctx, kpz, S->p, nu, Zc, mc, Tu, Ta, nup, bu, pcoef, pgrad + j0 * d));
+    GPX_TRY(launch_acq_grad(ctx, kpz, S->p, nu, Zc, mc, Tu, Ta, nup, bu, out.coef, out.grad + j0 * d));
   }
-  if (best || best_cost) {
-    ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
-    hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                       pbc, pbi);
-    GPX_HIP(hipGetLastError());
-    if (best) GPX_HIP(hipMemcpyAsync(best, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (grad_host) GPX_HIP(hipMemcpyAsync(grad_host, pgrad, (size_t)(M * d * 8), hipMemcpyDeviceToHost, ctx->stream));
-  return 0;
+  return out.finish(ctx, cost_host, best, best_cost, grad_host);
 }
 
 // q-point batch on a VFE model whose inducing points and hyper-parameters stay fixed.  One more observation at c_s changes A to
@@ -550,7 +574,7 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
 //     mu_j += u_j (y_s - mu_s) / sqrt(delta),   t_j -= u_j^2,   param = max(param, y_s) when track_best
 // delta >= noise > 0 (gpx_vfe_fit refuses noise <= 0): the tiny-pivot rule of the dense path (delta <= 1e-13 k(c_s, c_s): u = 0) has
 // no counterpart here, every pick conditions.  The only nu x M pass per pick is h = Wa[:, s]^T Wa (launch_colreduce, fixed order);
-// acq_pick_kernel<true> / acq_batch_kernel<true> do the rest.  The set-up walks the candidates in gpx_vfe_acq's chunks with
+// acq_batch_picks<true> (the dense loop, with acq_pick_kernel<true> / acq_batch_kernel<true>) does the rest.  The set-up walks the candidates in gpx_vfe_acq's chunks with
 // gpx_vfe_acq's launches, so row 0 of the costs holds its bits; the Lu solve of a chunk is transient (one nup x chunk buffer; out of
 // place it lands in the chunk's columns of Wa, which the La solve then overwrites).
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
@@ -562,97 +586,38 @@ int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const 
   const int64_t Mp = gpx_round_up(M, GPX_TILE), ld = gpx_skew_ld(Mp);
   KParams kpz = *fv.kp;
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Cm));
-  const bool oop = nup >= 2048;
+  const bool oop = chol_cross_oop(nup);
   const int64_t mcmax = gpx_eval_chunk(nup);
   const int64_t mcw = Mp < mcmax ? Mp : mcmax, ldb = gpx_skew_ld(mcw);
-  const int64_t bytesM = Mp * 8;
-  const int64_t nparts = (M + ACQ_EPI - 1) / ACQ_EPI;
-  const int64_t nw = nup > q ? nup : q;
-  double *pW, *pB, *pU, *bu, *pmu, *pt, *pr, *pkd, *phd, *ppart, *pcost, *ppc, *pbc, *psc, *puc, *pw;
-  int64_t *ppi, *pbi;
-  int* pmask;
+  double *pW, *pB, *bu;
+  AcqBatchState st;   // v = t, rfix = r, hd = |Lu^-1 k_u|^2 at the set-up
   Scratch sc(ctx);
-  const dim3 gEpi((unsigned)nparts), gPick((unsigned)((nw + 255) / 256));
   GPX_TRY(sc.get(nup * ld * 8, &pW));
   GPX_TRY(sc.get(nup * ldb * 8, &pB));
-  GPX_TRY(sc.get(q * Mp * 8, &pU));
-  GPX_TRY(sc.get(bytesM, &pmu));
-  GPX_TRY(sc.get(bytesM, &pt));
-  GPX_TRY(sc.get(bytesM, &pr));
-  GPX_TRY(sc.get(bytesM, &pkd));
-  GPX_TRY(sc.get(bytesM, &phd));    // |Lu^-1 k_u|^2 at the set-up, then h of every pick
-  GPX_TRY(sc.get(colreduce_partial_elems(nup, Mp) * 8 + 8, &ppart));
-  GPX_TRY(sc.get(M * 8, &pcost));
-  GPX_TRY(sc.get(nparts * 8, &ppc));
-  GPX_TRY(sc.get(nparts * 8, &ppi));
-  GPX_TRY(sc.get(8, &pbc));
-  GPX_TRY(sc.get(8, &pbi));
-  GPX_TRY(sc.get(SC_N * 8, &psc));
-  GPX_TRY(sc.get(q * 8, &puc));
-  GPX_TRY(sc.get(nw * 8, &pw));
-  GPX_TRY(sc.get(Mp * 4, &pmask));
+  GPX_TRY(st.take(sc, M, nup, q, true));
   GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
-  double sc0[SC_N] = {0.0, 0.0, 0.0, param, 0.0, 0.0, 0.0, 0.0};
-  GPX_HIP(hipMemsetAsync(pmask, 0, (size_t)Mp * 4, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(psc, sc0, sizeof(sc0), hipMemcpyHostToDevice, ctx->stream));
-  // ---- set-up: gpx_vfe_acq's chunks.  Not vfe_posterior_chunk: the La solve lands in the resident Wa with ITS row stride ----
+  GPX_TRY(st.init(ctx, param));
+  // ---- set-up: gpx_vfe_acq's chunks.  Not vfe_posterior_chunk: the La solve lands in the resident Wa with ITS row stride; the Lu
+  // solve is transient (in place in pB; out of place in the chunk's columns of Wa, which the La solve then overwrites) ----
   for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
     const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
     const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldc = gpx_skew_ld(mcp);
     const double* Cc = Cm->p + j0 * d;
     double* Wc = pW + j0;
     GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, pB, nup, mcp, ldc));
-    GPX_TRY(launch_colreduce(ctx, pB, ldc, nu, mcp, bu, pmu + j0, ppart));
-    if (oop) {
-      GPX_TRY(chol_trsm_left_oop(ctx, fv.Lu, pB, ldc, Wc, ld, mcp));
-      GPX_TRY(launch_colreduce(ctx, Wc, ld, nu, mcp, nullptr, phd + j0, ppart));
-      GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, pB, nup, mcp, ldc));
-      GPX_TRY(chol_trsm_left_oop(ctx, fv.La, pB, ldc, Wc, ld, mcp));
-    } else {
-      GPX_TRY(chol_trsm_left(ctx, fv.Lu->p, fv.Lu->ld, fv.Lu->aux, pB, ldc, nup, mcp));
-      GPX_TRY(launch_colreduce(ctx, pB, ldc, nu, mcp, nullptr, phd + j0, ppart));
-      GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, Wc, nup, mcp, ld));
-      GPX_TRY(chol_trsm_left(ctx, fv.La->p, fv.La->ld, fv.La->aux, Wc, ld, nup, mcp));
-    }
-    GPX_TRY(launch_colreduce(ctx, Wc, ld, nu, mcp, nullptr, pt + j0, ppart));
-    GPX_TRY(launch_kdiag(ctx, *fv.kp, Cc, mc, pkd + j0));
+    GPX_TRY(launch_colreduce(ctx, pB, ldc, nu, mcp, bu, st.mu + j0, st.part));
+    GPX_TRY(chol_cross_solve(ctx, fv.Lu, pB, ldc, oop ? Wc : nullptr, ld, mcp));
+    GPX_TRY(launch_colreduce(ctx, oop ? Wc : pB, oop ? ld : ldc, nu, mcp, nullptr, st.hd + j0, st.part));
+    // the second fill: the right-hand side of the La solve -- out of place again in pB, in place in Wa's own columns
+    double* B2 = oop ? pB : Wc;
+    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, B2, nup, mcp, oop ? ldc : ld));
+    GPX_TRY(chol_cross_solve(ctx, fv.La, B2, oop ? ldc : ld, oop ? Wc : nullptr, ld, mcp));
+    GPX_TRY(launch_colreduce(ctx, Wc, ld, nu, mcp, nullptr, st.v + j0, st.part));
+    GPX_TRY(launch_kdiag(ctx, *fv.kp, Cc, mc, st.kd + j0));
   }
-  hipLaunchKernelGGL(acq_batch_v_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                     (const double*)phd, M, pr);
-  GPX_HIP(hipGetLastError());
-  // ---- the picks ----
-  int64_t s = -1;
-  for (int64_t t = 0; t < q; ++t) {
-    {
-      ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
-      hipLaunchKernelGGL(acq_batch_kernel<true>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kpz, acq, (const double*)Cm->p, M,
-                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)psc, (const double*)puc, (const double*)phd, pU, Mp, pmu,
-                         pt, (const double*)pr, (const int*)pmask, pcost, ppc, ppi);
-      hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)ppc, (const int64_t*)ppi, nparts,
-                         pbc, pbi);
-    }
-    double c = 0.0;
-    GPX_HIP(hipGetLastError());
-    GPX_HIP(hipMemcpyAsync(&s, pbi, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(&c, pbc, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (all_costs) GPX_HIP(hipMemcpyAsync(all_costs + t * M, pcost, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipStreamSynchronize(ctx->stream));
-    if (s < 0 || s >= M) {
-      gpx_set_error("vfe acq batch: pick %lld of %lld: no candidate has a non-NaN cost", (long long)(t + 1), (long long)q);
-      return -1;
-    }
-    out_idx[t] = s;
-    if (out_cost) out_cost[t] = c;
-    if (t + 1 == q && !out_lie) break;
-    hipLaunchKernelGGL(acq_pick_kernel<true>, gPick, dim3(256), 0, ctx->stream, (const double*)pW, ld, nup, s, (const double*)pU,
-                       Mp, (int)t, (const double*)pmu, (const double*)pt, (const double*)nullptr, fv.noise, lie, lie_value,
-                       track_best, psc, puc, pw, pmask);
-    GPX_HIP(hipGetLastError());
-    if (out_lie) GPX_HIP(hipMemcpyAsync(out_lie + t, psc + SC_LIE, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (t + 1 == q) break;
-    GPX_TRY(launch_colreduce(ctx, pW, ld, nu, Mp, pw, phd, ppart));
-  }
-  return 0;
+  GPX_TRY(launch_vec_sub(ctx, st.kd, st.hd, M, st.rfix));
+  return acq_batch_picks<true>(ctx, kpz, acq, Cm, st, pW, ld, nu, nup, fv.noise, track_best, lie, lie_value, q, out_idx, out_cost,
+                               out_lie, all_costs, "vfe acq batch");
 }
 
 extern "C" {

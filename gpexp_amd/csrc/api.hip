@@ -960,7 +960,7 @@ static int potrf_end(gpx_ctx* ctx, gpx_mat* K, PotrfJob* J) {
   if (info != 0) gpx_set_error("potrf: matrix is not positive definite (pivot %d <= 0)", info);
   // explicit inverses of the diagonal blocks for the solves that follow (potrs, posterior / IVAR): completed here, on the
   // factorisation's stream, so that consumers on different streams (the bench runs potrs beside IVAR) find them ready
-  if (info == 0 && K->prows >= 2048) {
+  if (info == 0 && chol_cross_oop(K->prows)) {
     if (J->built)
       GPX_TRY(chol_binv_finish(ctx, K, J->ib));
     else
@@ -1004,8 +1004,7 @@ int gpx_posterior_chunk(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const
     if (mean_host) GPX_HIP(hipMemcpyAsync(mean_host, mean_dev, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (!ssq) return 0;
-  if (Wout) GPX_TRY(chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, Wout, ldb, mcp));
-  else GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, np, mcp));
+  GPX_TRY(chol_cross_solve(ctx, L, B, ldb, Wout, ldb, mcp));
   GPX_TRY(launch_colreduce(ctx, Wout ? Wout : B, ldb, n, mcp, nullptr, ssq, part));
   return launch_kdiag(ctx, kp, Zc, mc, kd);
 }
@@ -1187,14 +1186,6 @@ int gpx_logdet(gpx_ctx* ctx, const gpx_mat* L, double* out) {
 }
 
 // ---- posterior / IVAR ---------------------------------------------------------------------------------
-// out[j] = a[j] - b[j]: posterior variance k(z,z) - |L^-1 k_z|^2 of a chunk, on the device (round 1 copied both vectors to
-// the host per chunk and subtracted there: a stream sync and two M-length PCIe copies inside every optimiser evaluation)
-__global__ __launch_bounds__(256) static void vec_diff_kernel(const double* __restrict__ a, const double* __restrict__ b,
-                                                              int64_t n, double* __restrict__ out) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j < n) out[j] = a[j] - b[j];
-}
-
 // mean of v[0 .. count) by halving: v[i] += v[i + h], h = ceil(m / 2), m <- h -- the summation ORDER of the host routine this
 // replaces (pairwise_mean), so results do not depend on where the reduction runs or on the chunking.  One workgroup (the
 // levels are separated by workgroup barriers; 32768 values: 15 levels, ~20 us); v is consumed.
@@ -1237,8 +1228,8 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
   const int64_t mcmax = eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
   double *pB = nullptr, *pW = nullptr, *pal = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
-  // from 2048 training points the solve goes through the explicit block inverses, out of place (chol_trsm_left_oop)
-  const bool oop = var && np >= 2048;
+  // the cross-solve rule (chol_cross_oop), for the callers that want variances: the mean alone solves nothing
+  const bool oop = var && chol_cross_oop(np);
   const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
   const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
   const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
@@ -1270,9 +1261,7 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
     const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
     GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Z->p + j0 * d, mc, pB, pW, pal, pout, mean ? mean + j0 : nullptr,
                                 var ? pout : nullptr, pkd, ppart));
-    if (var)
-      hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                         (const double*)pout, mc, var_dev + j0);
+    if (var) GPX_TRY(launch_vec_sub(ctx, pkd, pout, mc, var_dev + j0));
   }
   if (var_host) GPX_HIP(hipMemcpyAsync(var_host, var_dev, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (keepW) *keepW = Wm.release();
@@ -1361,8 +1350,7 @@ int gpx_ivar_update(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   GPX_TRY(chol_trsm_left(ctx, L->p + keep * (L->ld + 1), L->ld, L->aux + (keep / GPX_TILE) * GPX_TILE * GPX_TILE, W2, ldw, n2p, mcp));
   GPX_TRY(launch_colreduce(ctx, W->p, ldw, n, mcp, nullptr, pout, ppart));
   GPX_TRY(launch_kdiag(ctx, kp, Z->p, M, pkd));
-  hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)pkd,
-                     (const double*)pout, M, pv);
+  GPX_TRY(launch_vec_sub(ctx, pkd, pout, M, pv));
   hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(1024), 0, ctx->stream, pv, M, ctx->d_scal);
   GPX_HIP(hipMemcpyAsync(out, ctx->d_scal, 8, hipMemcpyDeviceToHost, ctx->stream));
   return 0;

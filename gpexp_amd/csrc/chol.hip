@@ -1589,6 +1589,14 @@ int chol_trsm_left_oop(gpx_ctx* ctx, gpx_mat* Lm, double* B, int64_t ldb, double
   return r;
 }
 
+// (gpx_internal.h: the cross-solve rule)
+bool chol_cross_oop(int64_t np) { return np >= 2048; }
+
+int chol_cross_solve(gpx_ctx* ctx, const gpx_mat* L, double* B, int64_t ldb, double* W, int64_t ldw, int64_t m) {
+  if (!W) return chol_trsm_left(ctx, L->p, L->ld, L->aux, B, ldb, L->prows, m);
+  return chol_trsm_left_oop(ctx, const_cast<gpx_mat*>(L), B, ldb, W, ldw, m);   // the block inverses are a cache inside the factor
+}
+
 int chol_trsm_left_group(gpx_ctx* ctx, const double* Lg, int64_t ld, const double* invd, int64_t w, int64_t below, int64_t ib,
                          double* B, int64_t ldb, int64_t m, double* inv, double* tmp, double* W, int64_t ldw) {
   GPX_ARG(Lg && invd && B && inv && tmp && W && W != B && w > 0 && w % NB == 0 && ib >= NB && ib % NB == 0, "trsm group: bad arguments");

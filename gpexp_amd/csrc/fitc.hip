@@ -72,8 +72,9 @@
 // scalar from a slot of its own: the three products and two solves of gpx_fitc_lml_grad, without its diag(c) pass.  Predictor (the
 // optimal variational posterior; k_u = K(S, z), nothing N x M):
 //     mean(z) = k_u^T beta_u,  beta_u = Quu^-1 (Kuf alpha);      var(z) = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2
-// per chunk of candidates one nu x M fill (two with the variance: each solve consumes its right-hand side), two left solves of
-// order nu, two column sums of squares, one weighted column sum and vfe_var_kernel; one device-to-host copy per output per chunk.
+// per chunk of candidates (gpx_eval_chunk, the dense predictor's budget) one nu x M fill (two with the variance: each solve consumes
+// its right-hand side), two left solves of order nu (chol_cross_solve, the dense predictor's rule), two column sums of squares,
+// one weighted column sum and vfe_var_kernel; one device-to-host copy per output per chunk.
 // That per-chunk step is vfe_posterior_chunk, shared with the acquisition costs on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad: their
 // bodies and gpx_vfe_acq_batch's are in acq.hip beside the kernels they share with the dense calls; the entries and their argument
 // checks are here, where the struct is).
@@ -195,16 +196,6 @@ void fitc_release(gpx_ctx* ctx, gpx_fitc* f) {
   if (f->g) gpx_dev_release(ctx, f->g, f->np * 8);
   if (f->ginv) gpx_dev_release(ctx, f->ginv, f->np * 8);
   delete f;
-}
-
-// chunk of evaluation points handled at once (same budget as the dense posterior: GPX_CROSS_BYTES, default 16 GiB)
-int64_t eval_chunk(int64_t np) {
-  int64_t budget = (int64_t)16 << 30;
-  const char* e = getenv("GPX_CROSS_BYTES");
-  if (e && atoll(e) > 0) budget = atoll(e);
-  int64_t mc = budget / (np * 8) / GPX_TILE * GPX_TILE;
-  if (mc < GPX_TILE) mc = GPX_TILE;
-  return mc;
 }
 
 // Bt[m][i] *= s[i] (row-major m x cols, row stride ld)
@@ -426,12 +417,6 @@ __global__ __launch_bounds__(256) void scale_cols_to_kernel(const double* in, in
 __global__ void fill_kernel(double* __restrict__ x, int64_t n, double v) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) x[i] = v;
-}
-
-// out[i] = A[i][i], i < n
-__global__ __launch_bounds__(256) void diag_kernel(const double* __restrict__ A, int64_t ld, int64_t n, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = A[i * (ld + 1)];
 }
 
 // the sums of fitc_wsum_kernel for the na x nb weights Mw into out[nd + 1] (device); ppart: (tiles of Mw) x (nd + 1) doubles
@@ -658,17 +643,10 @@ int vfe_posterior_chunk(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kpz, con
   if (!B2) return 0;
   // each solve consumes its right-hand side: a second fill (cheaper than a copy, as in the fit)
   GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Zc, mc, 0, nullptr, 0, 0.0, B2, nup, mcp, ldb));
-  if (Wu) {
-    GPX_TRY(chol_trsm_left_oop(ctx, f->Lu, B1, ldb, Wu, ldb, mcp));
-    GPX_TRY(launch_colreduce(ctx, Wu, ldb, nu, mcp, nullptr, su, part));
-    GPX_TRY(chol_trsm_left_oop(ctx, f->La, B2, ldb, Wa, ldb, mcp));
-    GPX_TRY(launch_colreduce(ctx, Wa, ldb, nu, mcp, nullptr, sa, part));
-  } else {
-    GPX_TRY(chol_trsm_left(ctx, f->Lu->p, f->Lu->ld, f->Lu->aux, B1, ldb, nup, mcp));
-    GPX_TRY(launch_colreduce(ctx, B1, ldb, nu, mcp, nullptr, su, part));
-    GPX_TRY(chol_trsm_left(ctx, f->La->p, f->La->ld, f->La->aux, B2, ldb, nup, mcp));
-    GPX_TRY(launch_colreduce(ctx, B2, ldb, nu, mcp, nullptr, sa, part));
-  }
+  GPX_TRY(chol_cross_solve(ctx, f->Lu, B1, ldb, Wu, ldb, mcp));
+  GPX_TRY(launch_colreduce(ctx, Wu ? Wu : B1, ldb, nu, mcp, nullptr, su, part));
+  GPX_TRY(chol_cross_solve(ctx, f->La, B2, ldb, Wa, ldb, mcp));   // (Wu and Wa: both or neither)
+  GPX_TRY(launch_colreduce(ctx, Wa ? Wa : B2, ldb, nu, mcp, nullptr, sa, part));
   GPX_TRY(launch_kdiag(ctx, f->kp, Zc, mc, kd));
   hipLaunchKernelGGL(vfe_var_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)kd,
                      (const double*)su, (const double*)sa, mc, pv);
@@ -804,8 +782,7 @@ int fitc_grad_tail(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kp, const Fit
   if (grad) {
     GPX_TRY(fitc_wsums(ctx, kp, S, X, b1, ldk, w.ppart, out));
     GPX_TRY(fitc_wsums(ctx, kp, S, S, T, ldt, w.ppart, out + nq));
-    hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)T, ldt, nu, w.dg);
-    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_diag(ctx, T, ldt, nu, w.dg));
     GPX_TRY(launch_sum(ctx, w.dg, nu, out + 2 * nq + 1));
   }
   // dL/ds_u = sum_i R[u][i] dk(s_u, x_i)/ds_u - sum_v T[u][v] dk(s_u, s_v)/ds_u: moving s_u changes row u of Kuf and row and column
@@ -1230,7 +1207,7 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
   if (M == 0) return 0;
   KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, X, Z));
-  const int64_t mcmax = eval_chunk(np);
+  const int64_t mcmax = gpx_eval_chunk(np);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
   Scratch tmp(ctx);
   const int64_t ldb = gpx_skew_ld(np), ldu = gpx_skew_ld(nup);
@@ -1302,11 +1279,11 @@ int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
   if (M == 0 || (!mean && !var)) return 0;
   KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
-  const int64_t mcmax = eval_chunk(nup);
+  const int64_t mcmax = gpx_eval_chunk(nup);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
   const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
-  // from order 2048 the solves go through the explicit block inverses, out of place (as the dense posterior)
-  const bool oop = var && nup >= 2048;
+  // the cross-solve rule (chol_cross_oop), for the callers that want variances: the mean alone solves nothing
+  const bool oop = var && chol_cross_oop(nup);
   Scratch tmp(ctx);   // its scope exit is the synchronisation the host results wait for
   double *B1, *B2 = nullptr, *Wo = nullptr, *part, *pm = nullptr, *su = nullptr, *sa = nullptr, *kd = nullptr, *pv = nullptr;
   double* bu = nullptr;

@@ -414,6 +414,12 @@ int64_t chol_binv_elems(int64_t n);
 int chol_binv_finish(gpx_ctx* ctx, gpx_mat* L, int64_t ib);  // explicit inverses of L's diagonal blocks (order <= 1024), cached in L
 // W (n x m, separate buffer) = L^-1 B through the block inverses: B is consumed (its lower block rows are updated in place)
 int chol_trsm_left_oop(gpx_ctx* ctx, gpx_mat* L, double* B, int64_t ldb, double* W, int64_t ldw, int64_t m);
+// The cross-solve rule, in one place: a freshly filled cross matrix B (L->prows x m) is solved in place below padded order 2048
+// and out of place through the block inverses from 2048 on.  chol_cross_oop is the rule (gpx_potrf builds the inverses by it, the
+// callers size their second buffer by it); chol_cross_solve runs chol_trsm_left on the factor's own p / ld / aux / prows when
+// W == NULL and chol_trsm_left_oop into W otherwise (B is then consumed).  The caller knows which buffer holds the solution.
+bool chol_cross_oop(int64_t np);
+int chol_cross_solve(gpx_ctx* ctx, const gpx_mat* L, double* B, int64_t ldb, double* W, int64_t ldw, int64_t m);
 // one GROUP step of a right-looking left solve: Lg = the group's w x w diagonal triangle (row stride ld, `below` more rows
 // underneath it), invd = the leaf inverses of its first row block, B = the group's w rows of the right-hand sides (m columns):
 //   B[0:w] <- Lg^-1 B[0:w];  B[w : w+below] -= Lg[w:, 0:w] B[0:w]
@@ -485,6 +491,8 @@ int64_t colreduce_partial_elems(int64_t rows, int64_t pcols);
 int launch_rowreduce(gpx_ctx* ctx, const double* B, int64_t ld, int64_t rows, int64_t cols, const double* v,
                      double* out, int weighted_squares = 0);
 int launch_sum(gpx_ctx* ctx, const double* x, int64_t n, double* d_out);
+int launch_diag(gpx_ctx* ctx, const double* A, int64_t ld, int64_t n, double* out);                 // out[i] = A[i][i], i < n
+int launch_vec_sub(gpx_ctx* ctx, const double* a, const double* b, int64_t n, double* out);        // out[j] = a[j] - b[j], j < n
 
 // hyper.hip: out[q] = sum over the tiles of partial[tile][q], q < nq, in a fixed order (the final pass of the tiled traces)
 int launch_tile_sums(gpx_ctx* ctx, const double* partial, int64_t nblocks, int nq, double* out);

@@ -312,7 +312,8 @@ int check_args(int kind, int d, const gpx_mat* L, const gpx_mat* X, const gpx_ma
 // the two buffers it ends up in.  Large factors (T != NULL: mcp * chol_binv_order(np) doubles): both solves through the
 // factor's explicit block inverses -- forward out of place (chol_trsm_left_oop, the IVAR solve of bench.py), backward as the
 // right solve beta^T = W^T L^-1 (chol_trsm_right_n_leading) -- every product K >= 1024 on 128-tiles: 2 x 31 ms at N = 8192,
-// M = 32768 where the in-place leaf recursions took 2 x 36.
+// M = 32768 where the in-place leaf recursions took 2 x 36.  (Not chol_cross_solve's rule: the switch here is the workspace T, which
+// its callers take from order 4096 on, and the row stride is mcp, not the skewed one -- folding it in would change bits.)
 // Wfwd != NULL: W = L^-1 K(X, Zc) is at hand (np x mcp; kept by gpx_ivar_keep at the same design) -- fill and forward solve are
 // skipped, a third of the gradient's work.
 int solve_beta(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,

@@ -81,6 +81,20 @@ __global__ __launch_bounds__(256) void sum_kernel(const double* __restrict__ x, 
   if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// out[i] = A[i][i], i < n
+__global__ __launch_bounds__(256) void diag_kernel(const double* __restrict__ A, int64_t ld, int64_t n, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = A[i * (ld + 1)];
+}
+
+// out[j] = a[j] - b[j]: the posterior variance k(z,z) - |L^-1 k_z|^2 of a chunk, on the device (round 1 copied both vectors to
+// the host per chunk and subtracted there: a stream sync and two M-length PCIe copies inside every optimiser evaluation)
+__global__ __launch_bounds__(256) void vec_diff_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t n,
+                                                       double* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) out[j] = a[j] - b[j];
+}
+
 inline void plan(int64_t rows, int64_t pcols, int64_t* chunk, int64_t* nchunk) {
   int64_t colblocks = (pcols + 255) / 256;
   int64_t want = 2048 / colblocks;
@@ -178,6 +192,18 @@ int launch_rowreduce(gpx_ctx* ctx, const double* B, int64_t ld, int64_t rows, in
 
 int launch_sum(gpx_ctx* ctx, const double* x, int64_t n, double* d_out) {
   hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, ctx->stream, x, n, d_out);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_diag(gpx_ctx* ctx, const double* A, int64_t ld, int64_t n, double* out) {
+  hipLaunchKernelGGL(diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, A, ld, n, out);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_vec_sub(gpx_ctx* ctx, const double* a, const double* b, int64_t n, double* out) {
+  hipLaunchKernelGGL(vec_diff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, b, n, out);
   GPX_HIP(hipGetLastError());
   return 0;
 }

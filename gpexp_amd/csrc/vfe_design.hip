@@ -15,7 +15,7 @@
 // index order, then scaled and mirrored (vfd_sym_kernel).  gpx_vfe_design_eval, with P = K(S,Xf) (nu x b) and P^T (its own fill):
 //     A  = A0 + P P^T / noise        SYRK into La's storage, then vfd_sym_kernel in place (lower triangle + mirror)
 //     La = chol(A)                   fitc_factor: chol_potrf with the context's pivot policy
-//     Y1 = La^-1 Gz La^-T            a copy of Gz, chol_trsm_left (from order 2048: chol_trsm_left_oop through the block inverses),
+//     Y1 = La^-1 Gz La^-T            a copy of Gz, chol_cross_solve (from order 2048 out of place through the block inverses),
 //                                    chol_trsm_right;   tr Y1: diagonal gather + launch_sum (fixed order)
 //     V^T = P^T La^-T,   H^T = (V^T Y1) La^-1        chol_trsm_right, one b x nu x nu product, chol_trsm_right_n: A^-1 Gz A^-1 is never
 //                                    formed, and H comes out as the b x nu weights the row pass wants
@@ -81,30 +81,18 @@ int launch_sym(gpx_ctx* ctx, const double* base, int64_t ldb, const double* T, i
   return 0;
 }
 
-// out[i] = A[i][i], i < n
-__global__ __launch_bounds__(256) void vfd_diag_kernel(const double* __restrict__ A, int64_t ld, int64_t n, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = A[i * (ld + 1)];
-}
-
 // *d_tr (device) = tr(L^-1 G L^-T) over the first nu diagonal entries, summed in a fixed order; returns the buffer that holds
 // L^-1 G L^-T (nup x nup, row stride ld): Y, or W when the left solve ran out of place (W != NULL).  dg: nup doubles of scratch.
 int two_sided(gpx_ctx* ctx, gpx_mat* L, const gpx_mat* G, double* Y, double* W, int64_t ld, int64_t nu, double* dg, double* d_tr,
               double** sol_out) {
   const int64_t nup = L->prows;
   GPX_TRY(gpx_copy2d(ctx, G->p, G->ld, Y, ld, nup, nup));
-  double* sol = Y;
-  if (W) {
-    GPX_TRY(chol_trsm_left_oop(ctx, L, Y, ld, W, ld, nup));
-    sol = W;
-  } else {
-    GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, Y, ld, nup, nup));
-  }
+  double* sol = W ? W : Y;
+  GPX_TRY(chol_cross_solve(ctx, L, Y, ld, W, ld, nup));
   GPX_TRY(chol_trsm_right(ctx, L->p, L->ld, L->aux, sol, ld, nup, nup));
   {
     ProfScope ps(ctx, GPX_PROF_REDUCE, (double)nu, 16.0 * (double)nu);
-    hipLaunchKernelGGL(vfd_diag_kernel, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)sol, ld, nu, dg);
-    GPX_HIP(hipGetLastError());
+    GPX_TRY(launch_diag(ctx, sol, ld, nu, dg));
     GPX_TRY(launch_sum(ctx, dg, nu, d_tr));
   }
   if (sol_out) *sol_out = sol;
@@ -263,7 +251,7 @@ int gpx_vfe_design_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int 
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, ds->S, Z));
   const int64_t mcmax = gpx_eval_chunk(nup);
   const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  const bool oop = nup >= 2048;   // the predictor's rule
+  const bool oop = chol_cross_oop(nup);
   MatHold Y(ctx), W(ctx);
   GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, Y.put()));
   if (oop) GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, W.put()));
@@ -323,7 +311,7 @@ int gpx_vfe_design_eval(gpx_ctx* ctx, const gpx_vfe_design* ds, const gpx_mat* X
   const int64_t nu = ds->nu, nup = ds->nup, ldn = ds->A0->ld, b = Xf->rows, bp = gpx_round_up(b, GPX_TILE), ldp = gpx_skew_ld(bp);
   KParams kp = ds->kp;
   GPX_TRY(gpx_kparams_sets(ctx, &kp, ds->S, Xf));
-  const bool oop = nup >= 2048;   // the predictor's rule
+  const bool oop = chol_cross_oop(nup);
   MatHold La(ctx), Y(ctx), W(ctx);
   GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, La.put()));
   GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, Y.put()));

@@ -7,7 +7,7 @@ measurement: the comparison is exact.  Every entry runs twice; the second time e
 
 Shapes (d = 3): the smallest that reach each allocation branch --
     N = 300,  M = 260   in-place solve, ragged against the 128-tile, three arg-min partials of 128 candidates
-    N = 2100            the out-of-place solve of gpx_posterior / gpx_acq (padded order >= 2048)
+    N = 2100            the out-of-place solve of gpx_posterior / gpx_acq / gpx_acq_batch's set-up (padded order >= 2048)
     N = 4100, M = 260   the block-inverse scratch of gpx_acq_grad's backward solve (padded order >= 4096)
 The factor's explicit block inverses are a cache inside the factor, built by the first solve against it: the model fixture's
 gpx_potrs builds them, so that the entries under test start from the steady state.
@@ -198,7 +198,7 @@ ENTRIES = [
     ("potrs", _potrs, 300), ("kdiag", _kdiag, 300),
     ("acq", _acq, 300), ("acq", _acq, 2100),
     ("acq_grad", _acq_grad, 300), ("acq_grad", _acq_grad, 4100),
-    ("acq_batch", _acq_batch, 300),
+    ("acq_batch", _acq_batch, 300), ("acq_batch", _acq_batch, 2100),
     ("ivar_grad", _ivar_grad, 300), ("var_grad_newpt", _var_grad_newpt, 300),
     ("lml_grad", _lml_grad, 300), ("mi_greedy", _mi_greedy, 300), ("greedy_var", _greedy_var, 300),
     ("dbg_greedy_var_scores", _dbg_greedy_var_scores, 300),
