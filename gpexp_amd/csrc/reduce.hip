@@ -5,6 +5,8 @@
 //
 // Fixed summation order (row chunks in order, then chunks in order) so that results -- and the
 // arg-max / arg-min selections built on them -- do not depend on scheduling.
+#include <algorithm>
+
 #include "gpx_internal.h"
 
 namespace {
@@ -215,4 +217,74 @@ extern "C" int gpx_dbg_colreduce_plan(int64_t rows, int64_t pcols, int64_t* nchu
   plan(rows, pcols, &chunk, nchunk);
   *bound_elems = colreduce_partial_elems(rows, pcols);
   return 0;
+}
+
+// test hooks: one launch of the reductions above on host vectors, with the scratch the product gives them.  Every device
+// result buffer carries DBG_BAND doubles of a sentinel behind its last entry; a launch that writes past its range fails the call.
+namespace {
+
+constexpr int64_t DBG_BAND = 32;
+constexpr double DBG_SENTINEL = -7.25;
+
+int dbg_out_alloc(gpx_ctx* ctx, Scratch& sc, int64_t count, const double* preset, double** d_out) {
+  std::vector<double> h((size_t)(count + DBG_BAND), DBG_SENTINEL);
+  if (preset) std::copy(preset, preset + count, h.begin());
+  GPX_TRY(sc.get((count + DBG_BAND) * 8, d_out));
+  GPX_HIP(hipMemcpyAsync(*d_out, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));   // (h goes out of scope)
+  return 0;
+}
+
+int dbg_out_fetch(gpx_ctx* ctx, const double* d_out, int64_t count, double* out) {
+  std::vector<double> h((size_t)(count + DBG_BAND));
+  GPX_HIP(hipMemcpyAsync(h.data(), d_out, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  for (int64_t i = 0; i < DBG_BAND; ++i)
+    GPX_ARG(h[(size_t)(count + i)] == DBG_SENTINEL, "reduction wrote behind the last entry of its result");
+  std::copy(h.begin(), h.begin() + count, out);
+  return 0;
+}
+
+int dbg_upload(gpx_ctx* ctx, Scratch& sc, const double* v, int64_t n, double** d_v) {
+  GPX_TRY(sc.get((n > 0 ? n : 1) * 8, d_v));
+  GPX_HIP(hipMemcpyAsync(*d_v, v, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int gpx_dbg_colreduce(gpx_ctx* ctx, const gpx_mat* B, int64_t rows, const double* v, double* out, int subtract) {
+  GPX_ARG(ctx && B && out, "NULL argument");
+  GPX_ARG(rows >= 1 && rows <= B->prows, "colreduce: rows outside the padded matrix");
+  Scratch sc(ctx);
+  double *dv = nullptr, *dout = nullptr, *dpart = nullptr;
+  if (v) GPX_TRY(dbg_upload(ctx, sc, v, rows, &dv));
+  GPX_TRY(dbg_out_alloc(ctx, sc, B->pcols, subtract ? out : nullptr, &dout));
+  GPX_TRY(sc.get(colreduce_partial_elems(rows, B->pcols) * 8 + 8, &dpart));
+  GPX_TRY(launch_colreduce(ctx, B->p, B->ld, rows, B->pcols, dv, dout, dpart, subtract));
+  return dbg_out_fetch(ctx, dout, B->pcols, out);
+}
+
+extern "C" int gpx_dbg_rowreduce(gpx_ctx* ctx, const gpx_mat* A, int64_t cols, const double* v, int weighted_squares,
+                                 double* out) {
+  GPX_ARG(ctx && A && out, "NULL argument");
+  GPX_ARG(A->rows >= 1 && cols >= 2 && cols <= A->pcols, "rowreduce: columns outside the padded matrix");
+  GPX_ARG(v || !weighted_squares, "rowreduce: the weighted squares need weights");
+  Scratch sc(ctx);
+  double *dv = nullptr, *dout = nullptr;
+  if (v) GPX_TRY(dbg_upload(ctx, sc, v, cols, &dv));
+  GPX_TRY(dbg_out_alloc(ctx, sc, A->rows, nullptr, &dout));
+  GPX_TRY(launch_rowreduce(ctx, A->p, A->ld, A->rows, cols, dv, dout, weighted_squares));
+  return dbg_out_fetch(ctx, dout, A->rows, out);
+}
+
+extern "C" int gpx_dbg_sum(gpx_ctx* ctx, const double* x, int64_t n, double* out) {
+  GPX_ARG(ctx && x && out && n >= 1, "bad arguments");
+  Scratch sc(ctx);
+  double *dx = nullptr, *dout = nullptr;
+  GPX_TRY(dbg_upload(ctx, sc, x, n, &dx));
+  GPX_TRY(dbg_out_alloc(ctx, sc, 1, nullptr, &dout));
+  GPX_TRY(launch_sum(ctx, dx, n, dout));
+  return dbg_out_fetch(ctx, dout, 1, out);
 }

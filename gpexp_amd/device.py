@@ -284,6 +284,47 @@ def matvec(ctx, A, v):
     return out
 
 
+def col_sumsq(ctx, B, rows):
+    """sum_{i < rows} B[i][j]^2 for the logical columns of a resident DeviceMatrix (gpx_col_sumsq; deterministic)."""
+    out = np.empty(B.shape[1])
+    check(ctx.lib.gpx_col_sumsq(ctx.h, B.h, int(rows), dptr(out)))
+    return out
+
+
+def dbg_colreduce(ctx, B, rows, pcols, v=None, out=None, subtract=False):
+    """(pcols,) column sums over the leading `rows` rows of B, all padded columns (test hook, gpx_dbg_colreduce): sum_i B[i][j] v[i],
+    or the squares when v is None; subtract=True: `out` minus that sum.  `pcols` = the padded width of B."""
+    v = as_f64(v) if v is not None else None
+    assert v is None or v.shape == (int(rows),)
+    pcols = int(pcols)
+    r, c, ld = c_i64(), c_i64(), c_i64()
+    check(ctx.lib.gpx_mat_shape(B.h, C.byref(r), C.byref(c), C.byref(ld)))
+    assert c.value <= pcols <= ld.value
+    res = np.zeros(ld.value)        # (the library writes its own padded width, which the leading dimension bounds)
+    if out is not None:
+        res[:pcols] = out
+    check(ctx.lib.gpx_dbg_colreduce(ctx.h, B.h, int(rows), dptr(v), dptr(res), 1 if subtract else 0))
+    return res[:pcols].copy()
+
+
+def dbg_rowreduce(ctx, A, cols, v=None, weighted_squares=False):
+    """(rows,) row sums over the leading `cols` (even) columns of A (test hook, gpx_dbg_rowreduce): sum_c A[r][c] v[c], the squares
+    when v is None, sum_c v[c] A[r][c]^2 when weighted_squares."""
+    v = as_f64(v) if v is not None else None
+    assert v is None or v.shape == (int(cols),)
+    out = np.empty(A.shape[0])
+    check(ctx.lib.gpx_dbg_rowreduce(ctx.h, A.h, int(cols), dptr(v), 1 if weighted_squares else 0, dptr(out)))
+    return out
+
+
+def dbg_sum(ctx, x):
+    """Sum of a host vector by the library's one-workgroup reduction (test hook, gpx_dbg_sum)."""
+    x = as_f64(np.ravel(x))
+    out = C.c_double()
+    check(ctx.lib.gpx_dbg_sum(ctx.h, dptr(x), int(x.size), C.byref(out)))
+    return out.value
+
+
 class FitcModel:
     """Device-resident FITC model (gpx_fitc_*): chol(Quu), Kuf, G and chol(Quu + Kuf G^-1 Kfu)."""
 

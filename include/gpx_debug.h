@@ -52,6 +52,17 @@ int gpx_dbg_panel_bcast_plan(int W, int me, int64_t small_elems, int npieces, co
  * uses, and the scratch bound callers allocate; the bound is monotone in both arguments (one buffer serves every sub-block
  * a sweep reduces).  No device work. */
 int gpx_dbg_colreduce_plan(int64_t rows, int64_t pcols, int64_t* nchunk, int64_t* bound_elems);
+/* One launch each of the deterministic reductions behind the posterior, the triangular sweeps, the sparse models, the
+ * leave-one-out sums and the selectors, on host vectors and with the scratch the product gives them (tests/test_gpu_reduce.py).
+ * The device result carries a sentinel band behind its last entry: a launch that writes there fails the call.
+ *   colreduce  out[j] = sum_{i < rows} B[i][j] * v[i]  (v: host[rows])  or  sum_{i < rows} B[i][j]^2  (v NULL), for all
+ *              B->pcols padded columns; rows <= B->prows; subtract != 0: out[j] = out[j] - that sum, out read first
+ *   rowreduce  out[r] = sum_{c < cols} A[r][c] * v[c]  |  A[r][c]^2 (v NULL)  |  v[c] * A[r][c]^2 (weighted_squares), for
+ *              the A->rows logical rows; cols even, <= A->pcols
+ *   sum        out[0] = sum_{i < n} x[i] */
+int gpx_dbg_colreduce(gpx_ctx* ctx, const gpx_mat* B, int64_t rows, const double* v, double* out, int subtract);
+int gpx_dbg_rowreduce(gpx_ctx* ctx, const gpx_mat* A, int64_t cols, const double* v, int weighted_squares, double* out);
+int gpx_dbg_sum(gpx_ctx* ctx, const double* x, int64_t n, double* out);
 /* what an assembly between X and Z (NULL: X with itself) would do: *exact = 1 when distances are formed from raw
  * coordinate differences on the VALU (wide domain relative to the length scale) instead of the centred expanded MFMA
  * product; center[d] = the origin subtracted before scaling (bounding-box midpoint; 0 for Mehler) */
