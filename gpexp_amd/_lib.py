@@ -92,6 +92,15 @@ _SIGS = {
     "gpx_acq_grad": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, c_dp, c_dp]),
     "gpx_acq_batch": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_double, C.c_int, C.c_double,
                                 C.c_int, C.c_int, C.c_double, c_i64, c_ip, c_dp, c_dp, c_dp]),
+    "gpx_psampler_create": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_double, C.POINTER(c_vp)]),
+    "gpx_psampler_draw": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_dp]),
+    "gpx_psampler_argbest": (C.c_int, [c_vp, c_vp, c_dp, c_i64, C.c_int, c_ip, c_dp, c_dp]),
+    "gpx_psampler_shape": (C.c_int, [c_vp, c_ip]),
+    "gpx_psampler_free": (C.c_int, [c_vp, c_vp]),
+    "gpx_acq_qei": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_i64, c_dp, c_i64, C.c_double,
+                              C.c_double, c_dp, c_ip, c_dp, c_ip]),
+    "gpx_dbg_qei_blocks": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_i64, C.c_double, c_dp, c_dp,
+                                     c_dp]),
     "gpx_lml_grad": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp]),
     "gpx_lml_grad_slab": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_i64, c_i64, c_dp]),
     "gpx_lml_grad_rows": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_i64, c_i64, C.c_int, c_dp]),

@@ -498,6 +498,14 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
 
 }  // namespace
 
+// (gpx_internal.h) acq_argmin_kernel for the arg-min partials of another file (sample.hip: one partial per q-EI workgroup)
+int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i, int64_t nparts, double* out_c, int64_t* out_i) {
+  ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 16.0 * (double)nparts);
+  hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, part_c, part_i, nparts, out_c, out_i);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- the same three calls on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad, gpx_vfe_acq_batch; argument checks: fitc.hip) -------------
 // Notation of fitc.hip: S the nu inducing points, Quu = K(S,S) + noise I = Lu Lu^T, A = Quu + Kuf Kfu / noise = La La^T,
 // beta_u = Quu^-1 Kuf alpha, k_u(z) = K(S, z);  mean = k_u^T beta_u,  var = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2.

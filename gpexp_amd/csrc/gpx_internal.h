@@ -482,6 +482,9 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
                        double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
                        double* out_lie, double* all_costs);
+// acq.hip: out_c[0], out_i[0] (device) = the first minimum among the nparts arg-min partials {cost, index} with index >= 0
+// (argmin_merge; index -1 and a NaN cost when there is none) -- gpx_acq's final reduction, for sample.hip's q-EI partials
+int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i, int64_t nparts, double* out_c, int64_t* out_i);
 
 // reduce.hip
 // out[j] = sum_i B[i][j] * v[i]   (v == nullptr: sum_i B[i][j]^2), i < rows, j < pcols; deterministic

@@ -706,6 +706,91 @@ def acq_batch(ctx, spec, L, X, alpha, C, noise, kind, param, track_best, lie, li
     return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
 
 
+def _sampler_not_pd(pivot, nugget):
+    e = _lib.NotPositiveDefinite(pivot)
+    e.args = ("posterior covariance + jitter I is not positive definite: pivot %d <= 0 at evaluation point %d (0-based) with "
+              "jitter %g -- the point repeats an earlier one or lies on a training point; pass a larger jitter"
+              % (pivot, pivot - 1, nugget),)
+    return e
+
+
+class PosteriorSampler:
+    """Device-resident joint sampler at the M points Z (gpx_psampler_*): the posterior mean and F = chol(C + nugget I), C the
+    posterior covariance; L = X = alpha = None: the prior.  The device makes no random numbers: `draw` and `argbest` take the
+    (S, M) standard-normal base samples."""
+
+    def __init__(self, ctx, spec, L, X, alpha, Z, nugget):
+        self.ctx, self.h, self.m, self.nugget = ctx, None, Z.shape[0], float(nugget)
+        al = as_f64(alpha) if alpha is not None else None
+        h = c_vp()
+        rc = ctx.lib.gpx_psampler_create(ctx.h, *spec.args(), L.h if L is not None else None, X.h if X is not None else None,
+                                         dptr(al), Z.h, self.nugget, C.byref(h))
+        if rc > 0:
+            raise _sampler_not_pd(rc, self.nugget)
+        check(rc)
+        self.h = h
+
+    def draw(self, xi):
+        """(S, M) joint samples: row s = mean + F xi[s]."""
+        xi = as_f64(xi)
+        assert xi.ndim == 2 and xi.shape[1] == self.m, "base samples are (S, M)"
+        out = np.empty_like(xi)
+        check(self.ctx.lib.gpx_psampler_draw(self.ctx.h, self.h, dptr(xi), xi.shape[0], dptr(out)))
+        return out
+
+    def argbest(self, xi, minimize=True, want_samples=False):
+        """Per sample the first index of its minimum (maximum: minimize=False) and the value there, reduced on the device:
+        (indices (S,) int64, values (S,)[, samples (S, M)])."""
+        xi = as_f64(xi)
+        assert xi.ndim == 2 and xi.shape[1] == self.m, "base samples are (S, M)"
+        s = xi.shape[0]
+        idx, val = np.empty(s, dtype=np.int64), np.empty(s)
+        smp = np.empty_like(xi) if want_samples else None
+        check(self.ctx.lib.gpx_psampler_argbest(self.ctx.h, self.h, dptr(xi), s, 1 if minimize else -1,
+                                                idx.ctypes.data_as(_lib.c_ip), dptr(val), dptr(smp)))
+        return (idx, val, smp) if want_samples else (idx, val)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.gpx_psampler_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+QEI_MAX_Q = 32
+
+
+def acq_qei(ctx, spec, L, X, alpha, Zb, q, xi, fBest, nugget, want_costs=True):
+    """Monte-Carlo joint expected improvement of the B batches of q consecutive rows of Zb on the (S, q) base samples xi
+    (gpx_acq_qei): (first arg-min among the non-NaN costs or -1, its cost, costs (B,) or None, batches whose covariance did not
+    factor)."""
+    xi = as_f64(xi)
+    assert xi.ndim == 2 and xi.shape[1] == int(q), "base samples are (S, q)"
+    nb = Zb.shape[0] // max(int(q), 1)
+    costs = np.empty(nb) if want_costs else None
+    best, best_cost, nbad = c_i64(), C.c_double(), c_i64()
+    al = as_f64(alpha)
+    check(ctx.lib.gpx_acq_qei(ctx.h, *spec.args(), L.h, X.h, dptr(al), Zb.h, int(q), dptr(xi), xi.shape[0], float(fBest),
+                              float(nugget), dptr(costs), C.byref(best), C.byref(best_cost), C.byref(nbad)))
+    return best.value, best_cost.value, costs, nbad.value
+
+
+def dbg_qei_blocks(ctx, spec, L, X, alpha, Zb, q, nugget):
+    """(means (B, q), C_b (B, q, q), F_b (B, q, q)) of gpx_acq_qei's kernel (test hook, gpx_dbg_qei_blocks)."""
+    q = int(q)
+    nb = Zb.shape[0] // q
+    mean, Cb, Fb = np.empty((nb, q)), np.empty((nb, q, q)), np.empty((nb, q, q))
+    al = as_f64(alpha)
+    check(ctx.lib.gpx_dbg_qei_blocks(ctx.h, *spec.args(), L.h, X.h, dptr(al), Zb.h, q, float(nugget), dptr(mean), dptr(Cb),
+                                     dptr(Fb)))
+    return mean, Cb, Fb
+
+
 def greedy_ivar(ctx, spec, L, X, Cpts, Z, noise, nsel, want_all=False):
     """nsel picks of discrete greedy IVAR with resident state (gpx_greedy_ivar): (indices, winner costs[, all costs nsel x M])."""
     nsel = int(nsel)

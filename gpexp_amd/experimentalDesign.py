@@ -32,7 +32,7 @@ from scipy.optimize import fmin_l_bfgs_b as _bfgs
 from . import device as _dev
 from . import dist as _dist
 from . import gp_kernel_utilities  # noqa: F401  (the reference module exposes it)
-from .gp import GP as _GP
+from .gp import GP as _GP, drawBaseSamples as _drawBaseSamples
 
 NLOPT = False
 
@@ -721,6 +721,24 @@ class _costFuncBO(costFunctionBase):
         idx, costs, allc = out[0], out[1], (out[3] if returnAllCosts else None)
         return (idx, costs, allc) if returnAllCosts else (idx, costs)
 
+    def thompsonBatch(self, candidates, nPoints, baseSamples=None, jitter=None, minimize=True):
+        """Thompson sampling over a candidate set: `nPoints` independent JOINT draws of the posterior at the candidates
+        (GP.posteriorSampler -> gpx_psampler_argbest), one pick each -- the first index of the draw's minimum (minimize=False:
+        maximum).  Returns (indices (nPoints,) int64, values (nPoints,)); independent draws may pick the same candidate.  Only the
+        picks reach the host.  `baseSamples` (nPoints, M): the standard-normal base samples (np.random.standard_normal when None);
+        `jitter`: the sampler's nugget (default 1e-10 * max k(c, c)).  Dense models only (NotImplementedError on FITC / VFE)."""
+        gp = self.gaussianProcess
+        gp._sampling_ready("thompsonBatch")
+        candidates = np.asarray(candidates, dtype=float)
+        assert candidates.ndim == 2 and candidates.shape[1] == self.space.dimension, \
+            ("candidates are the wrong size: ", candidates.shape)
+        smp = gp.posteriorSampler(candidates, jitter=jitter)
+        try:
+            idx, val = smp.argbest(int(nPoints), baseSamples, minimize=minimize)
+        finally:
+            smp.close()
+        return idx, val
+
     def _selectBatchRefit(self, candidates, q, kindLie, lieValue, param, track, returnAllCosts):
         """selectBatch when the resident state does not fit beside the factor: the refit loop it replaces, with the existing calls
         (gpx_acq / gpx_vfe_acq chunk the candidates).  On a VFE model every refit keeps the inducing points (`fitcnodes` is set)."""
@@ -820,6 +838,61 @@ class costFuncEI(_costFuncBO):
         probGamma = spstats.norm.pdf(gamma)
         cost = -predstd * (gamma * phiGamma + probGamma)
         return cost[0]
+
+    # ---- joint (q-point) expected improvement by Monte Carlo ------------------------------------------------------------------
+    def _jointCall(self, batches, nSamples, baseSamples, jitter, name, want_costs):
+        gp = self.gaussianProcess
+        gp._sampling_ready(name)
+        assert type(gp).gpPriorMean is _GP.gpPriorMean and "gpPriorMean" not in vars(gp), \
+            "joint expected improvement assumes the base class's zero gpPriorMean"
+        b = np.asarray(batches, dtype=float)
+        if b.ndim == 2:
+            b = b[None]
+        if b.ndim != 3 or b.shape[0] < 1 or b.shape[2] != self.space.dimension:
+            raise ValueError("%s: batches must be (B, q, %d) or (q, %d), not %r" % (name, self.space.dimension, self.space.dimension,
+                                                                                 np.shape(batches)))
+        nb, q = b.shape[0], b.shape[1]
+        if not 1 <= q <= _dev.QEI_MAX_Q:
+            raise ValueError("%s: the batch size must be in 1 .. %d, not %d" % (name, _dev.QEI_MAX_Q, q))
+        xi = _drawBaseSamples(baseSamples, nSamples, q, name)
+        ctx = _dev.context()
+        spec = gp.kernel._spec()
+        Zb = _dev.points(ctx, b.reshape(nb * q, b.shape[2]))
+        nugget = gp._jitter(ctx, spec, Zb, jitter, name)
+        return _dev.acq_qei(ctx, spec, gp._L, gp._X, gp.coeff, Zb, q, xi, self._fBest(), nugget, want_costs=want_costs)
+
+    def jointEI(self, batches, nSamples=256, baseSamples=None, jitter=None):
+        """(B,) joint expected improvement of B batches of q points, minimisation form like `evaluate` (gpx_acq_qei):
+
+            cost_b = -(1/S) sum_s max(0, fBest - min_j f_s(batches[b, j])),      f_s = mean_b + chol(C_b + jitter I) baseSamples[s]
+
+        a sample average over S joint posterior draws of the batch with COMMON random numbers: the same `baseSamples` (S, q;
+        np.random.standard_normal((nSamples, q)) when None) for every batch, so that two batches are compared on the same draws.
+        `batches`: (B, q, d) or one batch (q, d), q <= 32.  `jitter`: nugget on every batch's q x q posterior covariance (default
+        1e-10 * max k(z, z)).  A batch whose covariance does not factor with it (two identical points and jitter=0) costs NaN.
+        With q = 1 the cost tends to evaluateBatch's closed form as S grows.  Dense models only."""
+        return self._jointCall(batches, nSamples, baseSamples, jitter, "jointEI", True)[2]
+
+    def bestJointBatch(self, batches, nSamples=256, baseSamples=None, jitter=None):
+        """(index, cost) of the batch with the lowest jointEI cost: the first minimum among the non-NaN costs, (-1, NaN) when every
+        cost is NaN.  Arguments as jointEI; only the winner reaches the host."""
+        best, cost, _, _ = self._jointCall(batches, nSamples, baseSamples, jitter, "bestJointBatch", False)
+        return best, cost
+
+    def selectBatchJoint(self, candidates, nPoints, lies=("believer", "min", "max", "mean"), nSamples=256, baseSamples=None,
+                         jitter=None):
+        """The best of several greedy batches by their JOINT expected improvement: `selectBatch(candidates, nPoints, lie)` proposes
+        one batch per entry of `lies`, one gpx_acq_qei call scores them all on common base samples, and the winner comes back as
+        (indices (nPoints,) int64, its jointEI cost, its lie).  Arguments as selectBatch and jointEI."""
+        lies = list(lies)
+        if not lies:
+            raise ValueError("selectBatchJoint: needs at least one lie")
+        candidates = np.asarray(candidates, dtype=float)
+        picks = [self.selectBatch(candidates, nPoints, lie=lie)[0] for lie in lies]
+        best, cost = self.bestJointBatch(np.stack([candidates[idx] for idx in picks]), nSamples, baseSamples, jitter)
+        if best < 0:
+            raise _dev._lib.GpxError("selectBatchJoint: no proposed batch has a non-NaN joint cost (a larger jitter factors them)")
+        return picks[best], cost, lies[best]
 
 
 def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rbounds=None, maxiter=50):

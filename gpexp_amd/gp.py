@@ -49,6 +49,57 @@ except ImportError:  # pragma: no cover
 NLOPT = False
 
 
+def drawBaseSamples(baseSamples, nSamples, width, what):
+    """The standard-normal base samples of a sampling call as a C-contiguous float64 array (S, width).  None draws
+    np.random.standard_normal((nSamples, width)) -- the device makes no random numbers -- except under an attached multi-process
+    session, where the calls run replicated and every rank would draw its own: ValueError.  A given array brings its own sample
+    count S (nSamples is not consulted) and is checked for its shape (S >= 1, width) and finiteness (ValueError)."""
+    width = int(width)
+    if baseSamples is None:
+        if int(nSamples) < 1:
+            raise ValueError("%s: needs at least one sample, not %r" % (what, nSamples))
+        if _dist.session() is not None:
+            raise ValueError("%s: under a multi-process session baseSamples must be given (the call runs replicated and every "
+                             "rank would draw its own)" % what)
+        return np.ascontiguousarray(np.random.standard_normal((int(nSamples), width)), dtype=np.float64)
+    xi = np.ascontiguousarray(baseSamples, dtype=np.float64)
+    if xi.ndim != 2 or xi.shape[0] < 1 or xi.shape[1] != width:
+        raise ValueError("%s: baseSamples must have shape (nSamples >= 1, %d), not %r" % (what, width, xi.shape))
+    if not np.all(np.isfinite(xi)):
+        raise ValueError("%s: baseSamples must be finite" % what)
+    return xi
+
+
+class JointSampler(object):
+    """What GP.posteriorSampler returns: a device-resident joint sampler at M points (device.PosteriorSampler) behind the
+    base-sample rules of drawBaseSamples."""
+
+    def __init__(self, state, m):
+        self._state, self.nPoints = state, int(m)
+
+    def _live(self):
+        if self._state is None:
+            raise ValueError("the sampler is closed")
+        return self._state
+
+    def draw(self, nSamples=1, baseSamples=None):
+        """(nSamples, M): row s = mean + F baseSamples[s]."""
+        st = self._live()
+        return st.draw(drawBaseSamples(baseSamples, nSamples, self.nPoints, "draw"))
+
+    def argbest(self, nSamples=1, baseSamples=None, minimize=True, returnSamples=False):
+        """(indices (nSamples,) int64, values (nSamples,)[, samples (nSamples, M)]): per draw the FIRST index of its minimum
+        (minimize=False: maximum) and the value there, reduced on the device."""
+        st = self._live()
+        return st.argbest(drawBaseSamples(baseSamples, nSamples, self.nPoints, "argbest"), minimize=bool(minimize),
+                          want_samples=bool(returnSamples))
+
+    def close(self):
+        if self._state is not None:
+            self._state.close()
+        self._state = None
+
+
 class GP:
     """Zero-prior-mean GP regression model."""
 
@@ -477,6 +528,75 @@ class GP:
 
     def generateSamples(self, x, noise=1e-10):
         raise NotImplementedError("generateSamples (SVD sampling, gp.py:343-371) is outside the GPU hot path")
+
+    # ---- joint samples (none of these touches generateSamples) ---------------------------------------------------------------
+    def _sampling_ready(self, name, fitted=True):
+        if self.FITC is not None:
+            raise NotImplementedError("%s needs the dense Cholesky factor: there is no sampler for FITC / VFE models" % name)
+        if fitted and (not self._has_factor() or self.coeff is None):
+            raise NotImplementedError("%s needs a trained model: call train first" % name)
+
+    def _jitter(self, ctx, spec, Z, jitter, name):
+        """The nugget of a sampler: `jitter`, or 1e-10 * max k(z, z) over the evaluation points (gpx_kdiag)."""
+        if jitter is None:
+            return 1e-10 * float(np.max(_dev.kdiag(ctx, spec, Z)))
+        jitter = float(jitter)
+        if not (jitter >= 0.0 and np.isfinite(jitter)):
+            raise ValueError("%s: jitter must be a finite number >= 0, not %r" % (name, jitter))
+        return jitter
+
+    def posteriorSampler(self, newpt, jitter=None, addNoise=False):
+        """A sampler of the JOINT posterior of the latent function at the M rows of `newpt` (gpx_psampler_*): the posterior mean
+        and F = chol(C + nugget I) stay on the device, C the full posterior covariance (evaluate(compvar=2)).  nugget = `jitter`,
+        by default 1e-10 * max k(z, z); `addNoise` adds the model's scalar noise to it: samples of OBSERVATIONS.  No pivot is
+        dropped: NotPositiveDefinite names the point when the nugget is too small (exact duplicates with jitter=0).  Returns an
+        object with
+            draw(nSamples=1, baseSamples=None)                        (S, M): row s = mean + F baseSamples[s]
+            argbest(nSamples=1, baseSamples=None, minimize=True, returnSamples=False)
+                                                                      (indices (S,) int64, values (S,)[, samples (S, M)]): per
+                                                                      draw the first index of its minimum / maximum
+            close()
+        The device makes no random numbers: `baseSamples` (S, M) are the standard-normal base samples, drawn with
+        np.random.standard_normal when None -- the same base samples give the same bits.  Dense models only; under a multi-process
+        session the calls run replicated, and baseSamples=None raises ValueError there (every rank would draw its own)."""
+        self._sampling_ready("posteriorSampler")
+        newpt = np.asarray(newpt, dtype=float)
+        assert newpt.ndim == 2 and newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
+        ctx = _dev.context()
+        spec = self.kernel._spec()
+        Z = _dev.points(ctx, newpt)
+        nugget = self._jitter(ctx, spec, Z, jitter, "posteriorSampler")
+        if addNoise:
+            if np.ndim(self.noise) != 0:
+                raise NotImplementedError("posteriorSampler(addNoise=True) needs a scalar noise")
+            nugget += float(self.noise)
+        return JointSampler(_dev.PosteriorSampler(ctx, spec, self._L, self._X, self.coeff, Z, nugget), newpt.shape[0])
+
+    def samplePosterior(self, newpt, nSamples=1, baseSamples=None, jitter=None):
+        """(nSamples, M) joint posterior samples at `newpt`: posteriorSampler(newpt, jitter).draw(nSamples, baseSamples)."""
+        smp = self.posteriorSampler(newpt, jitter=jitter)
+        try:
+            return smp.draw(nSamples, baseSamples)
+        finally:
+            smp.close()
+
+    def samplePrior(self, x, nSamples=1, noise=1e-10, baseSamples=None):
+        """(nSamples, M) joint samples of the PRIOR at the rows of `x` -- what the reference's generateSamples(x, noise) draws
+        (gp.py:343-371), with no training set: a zero-mean normal vector of covariance K(x, x) + noise I.  The reference adds two
+        independent terms, sqrt(K) z1 by an SVD and sqrt(noise) z2; here the noise is the nugget of one factorisation,
+        chol(K + noise I): the same distribution from ONE base vector per sample (`baseSamples`, (nSamples, M))."""
+        self._sampling_ready("samplePrior", fitted=False)
+        x = np.asarray(x, dtype=float)
+        assert x.ndim == 2 and x.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
+        ctx = _dev.context()
+        spec = self.kernel._spec()
+        Z = _dev.points(ctx, x)
+        nugget = self._jitter(ctx, spec, Z, 0.0 if noise is None else noise, "samplePrior")
+        smp = JointSampler(_dev.PosteriorSampler(ctx, spec, None, None, None, Z, nugget), x.shape[0])
+        try:
+            return smp.draw(nSamples, baseSamples)
+        finally:
+            smp.close()
 
     # ---- marginal likelihood -------------------------------------------------------------------------------------
     def computeLogLike(self, pts, evals):

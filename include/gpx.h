@@ -241,6 +241,47 @@ int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, co
                   int lie, double lie_value, int64_t q,
                   int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs);
 
+/* ---- joint posterior samples, Thompson picks and Monte-Carlo q-EI -------------------------------------------------------------
+ * The reference draws functions from the PRIOR (GP.generateSamples, gp.py:343-371: an SVD and numpy.random inside); these draw
+ * from the posterior at the M points of Z JOINTLY, pick per draw, and score whole q-batches.  Two rules:
+ *   - no random numbers are made on the device: every call takes the standard-normal BASE SAMPLES xi from the caller (host), so a
+ *     result is a deterministic function of its arguments -- two calls return the same bits -- and batches are compared on
+ *     common random numbers;
+ *   - the covariance is made positive definite by a NUGGET on its diagonal, F = chol(C + nugget I), factored with the pivot policy
+ *     (0, report) whatever gpx_potrf_policy holds (it is put back on every exit): no pivot is dropped, a pivot <= 0 comes back as
+ *     its 1-based index (status > 0, as gpx_potrf).  nugget < 0 is an argument error.  Dense factor only.
+ * gpx_psampler_create: resident state mean (M) and F (M x M; only these two stay).  mean_j = k_j^T alpha, the bits gpx_posterior
+ *   returns; C = K(Z,Z) - W^T W with W = L^-1 K(X,Z), formed by gpx_posterior_cov's own sequence (before the nugget, the bits that
+ *   call returns); after the factorisation one step of refinement, F <- F + F Phi(F^-1 (Chat - F F^T) F^-T), brings
+ *   |F F^T - Chat| down to a few (M + 1) u sqrt(Chat_ii Chat_jj) / 10.  L == X == alpha == NULL: the PRIOR, C = K(Z,Z), mean 0.  Every kernel kind.  M < 1 is an argument error.  No
+ *   chunking over Z (a joint draw cannot be chunked): what does not fit fails with the allocator's error.
+ * gpx_psampler_draw: out[s][j] = mean_j + sum_{k <= j} F_jk xi[s][k]; xi, out: host S x M.  The product runs on the MFMA path;
+ *   S is chunked under GPX_CROSS_BYTES.  A sample's bits depend neither on S nor on the chunking nor on the other samples.
+ * gpx_psampler_argbest: per sample the FIRST index of the minimum (sign = +1) or maximum (sign = -1) over the M points -- exactly
+ *   the first arg-best of the row gpx_psampler_draw returns for the same xi -- and its value (out_val: S, nullable); samples
+ *   (S x M, nullable) the draws themselves.  Without `samples` only S indices and values reach the host (Thompson sampling). */
+typedef struct gpx_psampler gpx_psampler;
+int gpx_psampler_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                        const double* alpha, const gpx_mat* Z, double nugget, gpx_psampler** out);
+int gpx_psampler_draw(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi, int64_t S, double* out);
+int gpx_psampler_argbest(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi, int64_t S, int sign, int64_t* out_idx,
+                         double* out_val, double* samples);
+int gpx_psampler_shape(const gpx_psampler* ps, int64_t* m);
+int gpx_psampler_free(gpx_ctx* ctx, gpx_psampler* ps);
+/* Joint expected improvement of B batches of q points by Monte Carlo, in gpx_acq's minimisation form.  Zb: (B q) x d, consecutive q
+ * rows form one batch; xi: host S x q, the SAME base samples for every batch (a sample-average approximation):
+ *     cost_b = -(1/S) sum_s max(0, fBest - min_j (mu_bj + (F_b xi_s)_j)),   F_b = chol(C_b + nugget I)
+ * with mu_b the posterior means (gpx_posterior's) and C_b the q x q posterior covariance of the batch.  q = 1 tends to GPX_ACQ_EI's
+ * closed form as S grows.  A batch whose factorisation meets a pivot <= 0 gets cost NaN and is counted in *n_bad (nullable); the
+ * call still succeeds.  cost (host B, nullable); *best / *best_cost as gpx_acq: the FIRST arg-min among the non-NaN costs, -1 (and
+ * NaN) when all are NaN, whatever the chunking (whole batches under GPX_CROSS_BYTES).  1 <= q <= GPX_QEI_MAX_Q, rows of Zb a
+ * multiple of q, S >= 1: anything else is an argument error.  Fixed-order reductions, no atomics: permuting the batches permutes
+ * the costs bit for bit.  Dense factor only. */
+#define GPX_QEI_MAX_Q 32
+int gpx_acq_qei(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
+                const gpx_mat* Zb, int64_t q, const double* xi, int64_t S, double fBest, double nugget, double* cost, int64_t* best,
+                double* best_cost, int64_t* n_bad);
+
 /* ---- hyper-parameter gradient -------------------------------------------------------------------- */
 /* grad[k] = 1/2 tr((alpha alpha^T - K^-1) dK/d theta_k), theta = {hyp[0..nhyp-1], noise}; the noise entry is
  * the raw 1/2 tr(alpha alpha^T - K^-1) (the caller applies the reference's x 2*noise, gp.py:463-464).

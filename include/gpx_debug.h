@@ -91,6 +91,12 @@ int gpx_dbg_leaf_stamps(gpx_ctx* ctx, gpx_mat* K, int fast, int64_t* out30);
 int gpx_dbg_greedy_var_scores(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* C, const int64_t* keep,
                               int64_t nkeep, double* out_d /* host M */);
 
+/* The blocks gpx_acq_qei's kernel works on, by its own launches: mean (host, B x q) the batches' posterior means, Cb (B x q x q)
+   the posterior covariance of every batch BEFORE the nugget (both triangles), Fb (B x q x q) chol(C_b + nugget I), strict upper
+   triangle 0 (NaN entries where a pivot was <= 0).  tests/test_gpu_qei.py replays the costs from them in extended precision. */
+int gpx_dbg_qei_blocks(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                       const double* alpha, const gpx_mat* Zb, int64_t q, double nugget, double* mean, double* Cb, double* Fb);
+
 #ifdef __cplusplus
 }
 #endif

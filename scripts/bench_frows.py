@@ -3,12 +3,13 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo,vfedesign] [--kernel se,matern52] [--out FILE]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo,vfedesign,sample,qei] [--kernel se,matern52] [--out FILE]
 
 --kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
 matern52; default se) -- the other entries keep their own kernels.
 --out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl), the `fitc` section its two
 leave-one-out lines (profiles/fitc_loo_frows.jsonl).
+--sample-out: where the `sample` and `qei` sections append their lines (default profiles/sample_qei_frows.jsonl).
 --vfe-out: where the `fitc` section appends its gpx_vfe_* lines (default profiles/vfe_frows.jsonl).
 """
 import json
@@ -571,3 +572,97 @@ if want("vfedesign"):
     with open(path, "w") as f:
         json.dump(vd, f, indent=1)
         f.write("\n")
+
+
+# ---- sample / qei: joint posterior draws and Monte-Carlo q-EI against what a user can do without them: gpx_posterior_cov to the
+# host, NumPy Cholesky, a NumPy product.  The two sides ALTERNATE (device, host, device, ...) and every line carries min / median /
+# max of its repetitions.
+def alternate(dev_f, host_f, reps):
+    td, th = [], []
+    for _ in range(reps):
+        for f, ts in ((dev_f, td), (host_f, th)):
+            ctx.sync()
+            t0 = time.perf_counter()
+            f()
+            ctx.sync()
+            ts.append(time.perf_counter() - t0)
+    return td, th
+
+
+def spread(ts):
+    return dict(ms_min=1e3 * min(ts), ms_median=1e3 * float(np.median(ts)), ms_max=1e3 * max(ts), reps=len(ts))
+
+
+def sample_report(line):
+    out = sys.argv[sys.argv.index("--sample-out") + 1] if "--sample-out" in sys.argv else \
+        os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sample_qei_frows.jsonl")
+    print(json.dumps(line), flush=True)
+    with open(out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+
+
+if want("sample") or want("qei"):
+    from gpExp.kernels import KernelIsoMatern
+    from gpExp.gp import GP
+    from gpExp.experimentalDesign import costFuncEI
+
+    class _Space8(object):
+        dimension = 8
+
+    Ns = 2048 if quick else 8192
+    rs = np.random.default_rng(Ns + 1)
+    Xs = rs.uniform(-1, 1, (Ns, 8))
+    ys = np.sin(3.0 * Xs[:, 0]) + 0.5 * np.cos(2.0 * Xs.sum(1)) + 0.05 * rs.standard_normal(Ns)
+    cfs = costFuncEI(GP(KernelIsoMatern(1.5, 1.0, 8, nu=2.5), 1e-2), Xs, ys, 2, _Space8())
+    gps = cfs.gaussianProcess
+    reps = 3 if quick else 5
+
+if want("sample"):
+    Ms, Ss = (1024, 64) if quick else (4096, 256)
+    Zs = rs.uniform(-1, 1, (Ms, 8))
+    xis = rs.standard_normal((Ss, Ms))
+    jit = 1e-10
+
+    def dev_draw():
+        return gps.samplePosterior(Zs, baseSamples=xis, jitter=jit)
+
+    def host_draw():
+        mean, cov = gps.evaluate(Zs, compvar=2)
+        F = np.linalg.cholesky(cov + jit * np.eye(Ms))
+        return mean[None, :] + xis @ F.T
+
+    dev_draw(), host_draw()
+    td, th = alternate(dev_draw, host_draw, reps)
+    size = dict(N=Ns, d=8, M=Ms, S=Ss, kernel="Matern-5/2")
+    sample_report(dict(entry="gpx_psampler (samplePosterior: create + draw + free)", size=size, **spread(td),
+                       note="mean, C = K(Z,Z) - W^T W, chol(C + jitter I), F Xi^T on the MFMA path; S x M doubles come back"))
+    sample_report(dict(entry="host path: evaluate(compvar=2) + numpy.linalg.cholesky + product", size=size, **spread(th),
+                       note="what a user can do without the sampler: M x M doubles cross to the host; median ratio host / device "
+                            "%.2f" % (float(np.median(th)) / float(np.median(td)))))
+
+if want("qei"):
+    Bq, qq, Sq = (512, 8, 256) if quick else (4096, 8, 256)
+    Zq = rs.uniform(-1, 1, (Bq, qq, 8))
+    xiq = rs.standard_normal((Sq, qq))
+    fbq = float(np.max(ys))
+
+    def dev_qei():
+        return cfs.jointEI(Zq, baseSamples=xiq, jitter=1e-10)
+
+    def host_qei(nb=None):
+        out = []
+        for b in range(Bq if nb is None else nb):
+            mean, cov = gps.evaluate(Zq[b], compvar=2)
+            F = np.linalg.cholesky(cov + 1e-10 * np.eye(qq))
+            out.append(-np.mean(np.maximum(fbq - np.min(mean[None, :] + xiq @ F.T, axis=1), 0.0)))
+        return np.array(out)
+
+    nbh = 16                                    # the host loop is timed on 16 batches and scaled: one device call per batch
+    dev_qei(), host_qei(2)
+    td, th = alternate(dev_qei, lambda: host_qei(nbh), reps)
+    size = dict(N=Ns, d=8, B=Bq, q=qq, S=Sq, kernel="Matern-5/2")
+    sample_report(dict(entry="gpx_acq_qei (jointEI)", size=size, **spread(td),
+                       note="posterior chunk over all B q points + one kernel: C_b, chol in LDS, S samples per batch"))
+    sample_report(dict(entry="host path per batch: evaluate(compvar=2) + NumPy", size=dict(size, B=nbh), **spread(th),
+                       note="%d batches timed, one gpx_posterior_cov call each; scaled to B = %d: %.1f ms (median)"
+                            % (nbh, Bq, 1e3 * float(np.median(th)) * Bq / nbh)))
