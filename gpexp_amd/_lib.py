@@ -97,6 +97,13 @@ _SIGS = {
     "gpx_psampler_argbest": (C.c_int, [c_vp, c_vp, c_dp, c_i64, C.c_int, c_ip, c_dp, c_dp]),
     "gpx_psampler_shape": (C.c_int, [c_vp, c_ip]),
     "gpx_psampler_free": (C.c_int, [c_vp, c_vp]),
+    "gpx_paths_create": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp, c_i64,
+                                   C.POINTER(c_vp)]),
+    "gpx_paths_eval": (C.c_int, [c_vp, c_vp, c_vp, c_dp, C.c_int, c_ip, c_dp]),
+    "gpx_paths_grad": (C.c_int, [c_vp, c_vp, c_vp, c_ip, c_dp, c_dp]),
+    "gpx_paths_coeff": (C.c_int, [c_vp, c_vp, c_dp]),
+    "gpx_paths_shape": (C.c_int, [c_vp, c_ip, c_ip, c_ip]),
+    "gpx_paths_free": (C.c_int, [c_vp, c_vp]),
     "gpx_acq_qei": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_i64, c_dp, c_i64, C.c_double,
                               C.c_double, c_dp, c_ip, c_dp, c_ip]),
     "gpx_dbg_qei_blocks": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_i64, C.c_double, c_dp, c_dp,

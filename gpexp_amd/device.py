@@ -762,6 +762,68 @@ class PosteriorSampler:
             pass
 
 
+class PathSampler:
+    """Device-resident PATHWISE sampler (gpx_paths_*): S posterior paths f_s(z) = sum_j c_sj cos(omega_j . z + phase_j) +
+    sum_i v_si k(z, x_i) with c = sqrt(2 signalSize / L) w and V = alpha - (K + noise I)^-1 (f~(X) + eps); L = X = alpha = None:
+    prior paths (V = 0).  The device makes no random numbers: omega (L, d), phase (L,), w (S, L) and eps (S, N) or None come from the
+    caller (gpexp_amd.paths.PathBase turns unit draws into them).  Stationary kernels only."""
+
+    def __init__(self, ctx, spec, L, X, alpha, omega, phase, w, eps):
+        self.ctx, self.h, self.d = ctx, None, spec.d
+        omega, phase, w = as_f64(omega), as_f64(phase), as_f64(w)
+        assert omega.ndim == 2 and omega.shape[1] == spec.d and phase.shape == (omega.shape[0],), "omega is (L, d), phase (L,)"
+        assert w.ndim == 2 and w.shape[1] == omega.shape[0], "w is (S, L)"
+        self.S, self.nfeat, self.n = w.shape[0], omega.shape[0], (X.shape[0] if X is not None else 0)
+        al = as_f64(alpha) if alpha is not None else None
+        ep = as_f64(eps) if eps is not None else None
+        assert ep is None or ep.shape == (self.S, self.n), "eps is (S, N)"
+        h = c_vp()
+        check(ctx.lib.gpx_paths_create(ctx.h, *spec.args(), L.h if L is not None else None, X.h if X is not None else None,
+                                       dptr(al), dptr(omega), dptr(phase), self.nfeat, dptr(w), dptr(ep), self.S, C.byref(h)))
+        self.h = h
+
+    def evaluate(self, Z):
+        """(S, M): row s = path s at the rows of the device point set Z."""
+        out = np.empty((self.S, Z.shape[0]))
+        check(self.ctx.lib.gpx_paths_eval(self.ctx.h, self.h, Z.h, dptr(out), 0, None, None))
+        return out
+
+    def argbest(self, Z, minimize=True, want_values=False):
+        """Per path the first index of its minimum (maximum: minimize=False) over the rows of Z and the value there, reduced on
+        the device across the chunks of Z: (indices (S,) int64, values (S,)[, values (S, M)])."""
+        idx, val = np.empty(self.S, dtype=np.int64), np.empty(self.S)
+        out = np.empty((self.S, Z.shape[0])) if want_values else None
+        check(self.ctx.lib.gpx_paths_eval(self.ctx.h, self.h, Z.h, dptr(out), 1 if minimize else -1,
+                                          idx.ctypes.data_as(_lib.c_ip), dptr(val)))
+        return (idx, val, out) if want_values else (idx, val)
+
+    def gradient(self, Zp, path, want_values=False):
+        """(P, d): row p = the gradient of path path[p] at row p of the device point set Zp [, values (P,)]."""
+        path = np.ascontiguousarray(path, dtype=np.int64)
+        assert path.shape == (Zp.shape[0],), "one path index per point"
+        grad = np.empty((Zp.shape[0], self.d))
+        val = np.empty(Zp.shape[0]) if want_values else None
+        check(self.ctx.lib.gpx_paths_grad(self.ctx.h, self.h, Zp.h, path.ctypes.data_as(_lib.c_ip), dptr(val), dptr(grad)))
+        return (grad, val) if want_values else grad
+
+    def coefficients(self):
+        """(S, N): the resident update weights V."""
+        v = np.empty((self.S, self.n))
+        check(self.ctx.lib.gpx_paths_coeff(self.ctx.h, self.h, dptr(v)))
+        return v
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.gpx_paths_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 QEI_MAX_Q = 32
 
 

@@ -739,6 +739,60 @@ class _costFuncBO(costFunctionBase):
             smp.close()
         return idx, val
 
+    def thompsonPaths(self, candidates, nPoints, nFeatures=1024, base=None, minimize=True, polish=False, lbounds=None,
+                      rbounds=None, maxiter=50):
+        """Thompson sampling with PATHS (GP.pathSampler -> gpx_paths_eval): `nPoints` posterior paths with `nFeatures` random
+        features, ONE arg-best pass over the candidates -- any number of them, chunked under GPX_CROSS_BYTES, no M x M factor --
+        one pick each: the first index of the path's minimum (minimize=False: maximum).  Returns (points (q, d), values (q,),
+        indices (q,) int64); independent paths may pick the same candidate.  `base`: the PathBase of the draws (PathBase.draw with
+        NumPy when None; the same base gives the same result).
+        polish=True: a path is a differentiable function, so SciPy L-BFGS-B then runs from every path's discrete winner at once,
+        the way optimizeAcquisition drives its starts -- the objective is the SUM of the paths' values over the stacked q x d
+        vector (separable), one gpx_paths_grad call per iteration -- inside the box [lbounds, rbounds] (default: the candidates'
+        bounding box).  A polished point replaces the discrete winner only where its value is better, so no value is worse than
+        the discrete one; `indices` stays the discrete index.  Pathwise samples are approximate draws (GP.pathSampler);
+        thompsonBatch draws exactly.  Stationary kernels and dense models only (NotImplementedError otherwise)."""
+        gp = self.gaussianProcess
+        candidates = np.asarray(candidates, dtype=float)
+        assert candidates.ndim == 2 and candidates.shape[1] == self.space.dimension, \
+            ("candidates are the wrong size: ", candidates.shape)
+        q, d = int(nPoints), candidates.shape[1]
+        inside = None
+        if polish:
+            lb = np.min(candidates, axis=0) if lbounds is None else np.broadcast_to(np.asarray(lbounds, dtype=float), (d,))
+            ub = np.max(candidates, axis=0) if rbounds is None else np.broadcast_to(np.asarray(rbounds, dtype=float), (d,))
+            # candidates outside the box take no part (`indices` still counts rows of `candidates`)
+            inside = np.flatnonzero(np.all((candidates >= lb) & (candidates <= ub), axis=1))
+            if len(inside) == 0:
+                raise ValueError("thompsonPaths: no candidate lies inside the bounds")
+        smp = gp.pathSampler(q, nFeatures, base)
+        try:
+            q = smp.nPaths
+            if inside is None or len(inside) == len(candidates):
+                idx, val = smp.argbest(candidates, minimize=minimize)
+            else:
+                idx, val = smp.argbest(candidates[inside], minimize=minimize)
+                idx = inside[idx]
+            pts = candidates[idx].copy()
+            if polish:
+                sgn, paths = (1.0 if minimize else -1.0), np.arange(q, dtype=np.int64)
+
+                def objective(x):
+                    g, v = smp.gradient(np.ascontiguousarray(np.reshape(x, (q, d))), paths, returnValues=True)
+                    if not np.all(np.isfinite(v)) or not np.all(np.isfinite(g)):
+                        return 1e300, np.zeros(q * d)
+                    return sgn * float(np.sum(v)), sgn * g.ravel()
+
+                x = _bfgs(objective, np.clip(pts, lb, ub).ravel(), bounds=list(zip(np.tile(lb, q), np.tile(ub, q))),
+                          maxiter=int(maxiter))[0]
+                P = np.clip(np.reshape(x, (q, d)), lb, ub)
+                pv = smp.gradient(P, paths, returnValues=True)[1]
+                better = (pv < val) if minimize else (pv > val)
+                pts[better], val = P[better], np.where(better, pv, val)
+        finally:
+            smp.close()
+        return pts, val, idx
+
     def _selectBatchRefit(self, candidates, q, kindLie, lieValue, param, track, returnAllCosts):
         """selectBatch when the resident state does not fit beside the factor: the refit loop it replaces, with the existing calls
         (gpx_acq / gpx_vfe_acq chunk the candidates).  On a VFE model every refit keeps the inducing points (`fitcnodes` is set)."""

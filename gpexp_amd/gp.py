@@ -41,6 +41,7 @@ from . import device as _dev
 from . import dist as _dist
 from ._lib import NotPositiveDefinite, hdot as _hdot
 from .gp_kernel_utilities import calculateCovarianceMatrix, _check_nugget  # noqa: F401  (re-export like the reference)
+from .paths import PathBase, spectralFrequencies as _spectralFrequencies
 
 try:  # the reference prefers nlopt and falls back to SciPy (gp.py:28-41); only the SciPy branch is provided
     from scipy.optimize import fmin_l_bfgs_b as bfgs
@@ -93,6 +94,42 @@ class JointSampler(object):
         st = self._live()
         return st.argbest(drawBaseSamples(baseSamples, nSamples, self.nPoints, "argbest"), minimize=bool(minimize),
                           want_samples=bool(returnSamples))
+
+    def close(self):
+        if self._state is not None:
+            self._state.close()
+        self._state = None
+
+
+class PathSampler(object):
+    """What GP.pathSampler / GP.priorPathSampler return: S device-resident posterior (prior) PATHS (device.PathSampler), functions
+    that can be evaluated at any number of points, in chunks, and differentiated.  `base` is the PathBase they were made from."""
+
+    def __init__(self, state, base, d):
+        self._state, self.base, self.nPaths, self._d = state, base, base.nPaths, int(d)
+
+    def _points(self, pts):
+        if self._state is None:
+            raise ValueError("the sampler is closed")
+        pts = np.asarray(pts, dtype=float)
+        assert pts.ndim == 2 and pts.shape[1] == self._d, "evaluation points for GP is incorrect shape"
+        return _dev.points(_dev.context(), pts)
+
+    def evaluate(self, newpt):
+        """(S, M): row s = path s at the rows of `newpt`."""
+        Z = self._points(newpt)
+        return self._state.evaluate(Z)
+
+    def argbest(self, newpt, minimize=True, returnValues=False):
+        """(indices (S,) int64, values (S,)[, values (S, M)]): per path the FIRST index of its minimum (minimize=False: maximum)
+        over the rows of `newpt` and the value there, reduced on the device; without returnValues only these reach the host."""
+        Z = self._points(newpt)
+        return self._state.argbest(Z, minimize=bool(minimize), want_values=bool(returnValues))
+
+    def gradient(self, points, pathIndex, returnValues=False):
+        """(P, d): row p = the gradient of path pathIndex[p] at points[p] [, the values (P,) there]."""
+        Z = self._points(points)
+        return self._state.gradient(Z, np.asarray(pathIndex, dtype=np.int64).ravel(), want_values=bool(returnValues))
 
     def close(self):
         if self._state is not None:
@@ -597,6 +634,70 @@ class GP:
             return smp.draw(nSamples, baseSamples)
         finally:
             smp.close()
+
+    # ---- pathwise samples (Matheron's rule) ---------------------------------------------------------------------------------------
+    def _pathBase(self, name, nPaths, nFeatures, base, nTrain):
+        spec = self.kernel._spec()
+        if spec.kind == _dev.K_MEHLER:
+            raise NotImplementedError("%s: %s has no spectral density here (squared exponential and isotropic Matern only)"
+                                      % (name, type(self.kernel).__name__))
+        d = self.kernel.dimension
+        if base is None:
+            if _dist.session() is not None:
+                raise ValueError("%s: under a multi-process session base must be given (the call runs replicated and every rank "
+                                 "would draw its own)" % name)
+            return PathBase.draw(nPaths, nFeatures, nTrain, d, spec)
+        if not isinstance(base, PathBase):
+            raise ValueError("%s: base must be a PathBase (PathBase.draw), not %r" % (name, type(base).__name__))
+        if base.dimension != d or base.nTrain != nTrain or (base.u is None) != (spec.kind == _dev.K_SE):
+            raise ValueError("%s: base was drawn for d = %d, %d training points and a %s kernel; the model has d = %d, %d points"
+                             % (name, base.dimension, base.nTrain, "squared-exponential" if base.u is None else "Matern", d, nTrain))
+        return base
+
+    def pathSampler(self, nPaths=1, nFeatures=1024, base=None):
+        """`nPaths` PATHS of the posterior of the latent function (gpx_paths_*; Matheron's rule, Wilson et al. 2020): each draw is
+        a function, a random-Fourier-feature draw of the prior (`nFeatures` features) plus a kernel-basis update solved once
+        against the resident factor, so it can be evaluated at ANY number of points afterwards (chunked under GPX_CROSS_BYTES; no
+        M x M factor) and differentiated.  Returns an object with
+            evaluate(newpt)                                          (S, M)
+            argbest(newpt, minimize=True, returnValues=False)        (indices (S,) int64, values (S,)[, values (S, M)])
+            gradient(points, pathIndex)                              (P, d): row p = gradient of path pathIndex[p] at points[p]
+            base                                                     the PathBase used
+            close()
+        The device makes no random numbers: `base` (PathBase.draw(nPaths, nFeatures, N, d, kernel, rng)) holds every draw, made
+        with NumPy when None -- the same base gives the same bits.  These are NOT exact posterior samples: with finitely many
+        features the prior part has covariance Phi Phi^T instead of K (the mean is exact, the covariance tends to the posterior's as
+        nFeatures grows); posteriorSampler stays the exact one.  Stationary kernels, dense models and scalar noise only
+        (NotImplementedError); under a multi-process session the calls run replicated, and base=None raises ValueError there."""
+        self._sampling_ready("pathSampler")
+        if np.ndim(self.noise) != 0:
+            raise NotImplementedError("pathSampler needs a scalar noise: there is no pathwise sampler for per-point noise")
+        n = self.pts.shape[0]
+        base = self._pathBase("pathSampler", nPaths, nFeatures, base, n)
+        ctx = _dev.context()
+        spec = self.kernel._spec()
+        eps = np.sqrt(float(self.noise)) * base.xi
+        state = _dev.PathSampler(ctx, spec, self._L, self._X, self.coeff, _spectralFrequencies(spec, base.g, base.u), base.phase,
+                                 base.w, eps)
+        return PathSampler(state, base, self.kernel.dimension)
+
+    def samplePaths(self, newpt, nPaths=1, nFeatures=1024, base=None):
+        """(nPaths, M) pathwise posterior samples at `newpt`: pathSampler(nPaths, nFeatures, base).evaluate(newpt)."""
+        smp = self.pathSampler(nPaths, nFeatures, base)
+        try:
+            return smp.evaluate(newpt)
+        finally:
+            smp.close()
+
+    def priorPathSampler(self, nPaths=1, nFeatures=1024, base=None):
+        """Paths of the PRIOR (no training set, no update: V = 0) -- the pathwise counterpart of samplePrior, same object as
+        pathSampler returns.  `base`: PathBase.draw(nPaths, nFeatures, 0, d, kernel, rng)."""
+        self._sampling_ready("priorPathSampler", fitted=False)
+        base = self._pathBase("priorPathSampler", nPaths, nFeatures, base, 0)
+        ctx = _dev.context()
+        spec = self.kernel._spec()
+        state = _dev.PathSampler(ctx, spec, None, None, None, _spectralFrequencies(spec, base.g, base.u), base.phase, base.w, None)
+        return PathSampler(state, base, self.kernel.dimension)
 
     # ---- marginal likelihood -------------------------------------------------------------------------------------
     def computeLogLike(self, pts, evals):

@@ -282,6 +282,42 @@ int gpx_acq_qei(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, cons
                 const gpx_mat* Zb, int64_t q, const double* xi, int64_t S, double fBest, double nugget, double* cost, int64_t* best,
                 double* best_cost, int64_t* n_bad);
 
+/* ---- pathwise posterior samples (Matheron's rule): draws that are FUNCTIONS ------------------------------------------------------
+ * gpx_psampler_* draws jointly at M fixed points through an M x M factor; these draw PATHS, which can be evaluated at any number of
+ * points afterwards (Z is chunked under GPX_CROSS_BYTES), and differentiated:
+ *     f~_s(z) = sum_j c_sj cos(omega_j . z + b_j),   c = sqrt(2 signalSize / nfeat) w            (prior path, nfeat random features)
+ *     V       = alpha - (K + noise I)^-1 (f~(X) + eps)                                           (update weights, S x N)
+ *     f_s(z)  = f~_s(z) + sum_i v_si k(z, x_i)                                                   (posterior path)
+ * The sampler's rules hold: no random numbers are made on the device -- omega (the frequencies, draws of the kernel's spectral
+ * density), phase (uniform in [0, 2 pi)), w (standard normal) and eps (the noise draw, variance = the model's noise) come from
+ * the caller, so a result is a deterministic function of its arguments and two calls return the same bits.  Stationary kernels only
+ * (GPX_K_SE, GPX_K_MATERN32, GPX_K_MATERN52: GPX_K_MEHLER is an argument error); dense factor only.
+ * What pathwise samples are NOT: with finitely many features the prior part has covariance Phi Phi^T, not K, so the paths'
+ * covariance at Z is A (Phi_J Phi_J^T) A^T + noise G G^T with G = K(Z,X) (K + noise I)^-1, A = [I, -G] and Phi_J the features at
+ * (Z; X) -- it tends to the exact posterior covariance as nfeat grows.  The mean is exact.  gpx_psampler_* stays the exact sampler.
+ * gpx_paths_create: evaluates the prior paths at X with gpx_paths_eval's own kernel, solves (K + noise I)^-1 (f~(X) + eps) against L
+ *   (gpx_potrs_dev's solve, one right-hand side per path) and keeps omega, phase, c, V and a copy of X's points: nothing N x N stays.
+ *   L == X == alpha == NULL: PRIOR paths (V = 0, N = 0).  nfeat < 1 and S < 1 are argument errors.
+ * gpx_paths_eval: out[s][m] = f_s(z_m) (host S x M, nullable) by ONE product on the fp64 MFMA path whose large operand -- the
+ *   features and K(X, Z) -- is generated in registers and never stored (no N x chunk buffer; the budget covers the S x chunk
+ *   output).  The value of (s, m) depends on path s and on z_m alone: not on S, on the other paths or points of the call, or on the
+ *   chunking, bit for bit.  sign = +1 / -1: per path the FIRST index of its minimum / maximum over the M points (best_idx: S) and
+ *   the value there (best_val: S, nullable), reduced on the device and merged across chunks (the smaller index wins a tie); with
+ *   out == NULL only these reach the host.  sign = 0: no pick.
+ * gpx_paths_grad: point p (row p of Zp) belongs to path path[p]: grad[p][l] = d f_path[p](z_p) / d z_l, the true derivative (0 from
+ *   the kernel term at z = x_i: nothing divides by the distance); val[p] (nullable) = the value there.  Fixed-order sums.
+ * gpx_paths_coeff: v = V (host S x N).  gpx_paths_shape: S, nfeat, N (each nullable). */
+typedef struct gpx_paths gpx_paths;
+int gpx_paths_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                     const double* alpha, const double* omega, const double* phase, int64_t nfeat, const double* w,
+                     const double* eps, int64_t S, gpx_paths** out);
+int gpx_paths_eval(gpx_ctx* ctx, const gpx_paths* ps, const gpx_mat* Z, double* out, int sign, int64_t* best_idx,
+                   double* best_val);
+int gpx_paths_grad(gpx_ctx* ctx, const gpx_paths* ps, const gpx_mat* Zp, const int64_t* path, double* val, double* grad);
+int gpx_paths_coeff(gpx_ctx* ctx, const gpx_paths* ps, double* v);
+int gpx_paths_shape(const gpx_paths* ps, int64_t* S, int64_t* nfeat, int64_t* n);
+int gpx_paths_free(gpx_ctx* ctx, gpx_paths* ps);
+
 /* ---- hyper-parameter gradient -------------------------------------------------------------------- */
 /* grad[k] = 1/2 tr((alpha alpha^T - K^-1) dK/d theta_k), theta = {hyp[0..nhyp-1], noise}; the noise entry is
  * the raw 1/2 tr(alpha alpha^T - K^-1) (the caller applies the reference's x 2*noise, gp.py:463-464).
