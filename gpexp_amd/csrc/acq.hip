@@ -233,47 +233,32 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
              int acq, double param, double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
   const int64_t n = L->rows, np = L->prows, M = Z->rows, d = kp.d;
   const bool grad = grad_host != nullptr;
-  const int64_t mcmax = gpx_eval_chunk(np);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  const bool oop = chol_cross_oop(np);   // the same solve as posterior_impl
-  const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
-  const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
-  const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
-  const int64_t bytesT = (grad && np >= 4096) ? mc_alloc * chol_binv_order(np) * 8 : 0;
-  double *pB = nullptr, *pW = nullptr, *pT = nullptr, *pal = nullptr, *pmean = nullptr, *pout = nullptr, *ppart = nullptr;
-  double* pkd = nullptr;
+  const ChunkRange cr(M, gpx_eval_chunk(np));
+  const int64_t bytesT = (grad && np >= 4096) ? cr.mc_alloc * chol_binv_order(np) * 8 : 0;
+  double *pBt = nullptr, *pT = nullptr;
+  PosteriorWork w(np, cr.mc_alloc, true);   // the same solve as posterior_impl
   AcqOut out;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  GPX_TRY(sc.get(bytesB, &pB));
-  if (oop || grad) GPX_TRY(sc.get(bytesB, &pW));
+  GPX_TRY(w.take(sc, true, true));
+  if (grad && !w.oop()) GPX_TRY(sc.get(w.bytesB, &pBt));
   if (bytesT) GPX_TRY(sc.get(bytesT, &pT));
-  GPX_TRY(sc.get(np * 8, &pal));
-  GPX_TRY(sc.get(bytes_out, &pmean));
-  GPX_TRY(sc.get(bytes_out, &pout));
-  GPX_TRY(sc.get(bytes_out, &pkd));
-  GPX_TRY(sc.get(bytes_part, &ppart));
-  GPX_TRY(out.take(sc, M, mc_alloc, d, grad));
-  GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE);
-    double* B = pB;
+  GPX_TRY(out.take(sc, M, cr.mc_alloc, d, grad));
+  GPX_TRY(w.upload_alpha(ctx, alpha, n));
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
     const double* Zc = Z->p + j0 * d;
-    const int64_t ldb = gpx_skew_ld(mcp);
     // gpx_posterior's own per-chunk step: the values equal GP.evaluate's
-    GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Zc, mc, B, oop ? pW : nullptr, pal, pmean, nullptr, pout, pkd, ppart));
-    double* Wsol = oop ? pW : B;
-    GPX_TRY(out.epilogue(ctx, acq, param, pmean, pkd, pout, mc, j0, 8.0 * 5.0 * (double)mc));
+    GPX_TRY(w.run(ctx, kp, L, X, Zc, mc));
+    GPX_TRY(out.epilogue(ctx, acq, param, w.mean, w.kd, w.ssq, mc, j0, 8.0 * 5.0 * (double)mc));
     if (!grad) continue;
     // beta^T = W^T L^-1 (mcp x np, row stride np) in the buffer W does not occupy (B is consumed by the out-of-place solve)
-    double* Bt = Wsol == B ? pW : B;
-    GPX_TRY(launch_transpose(ctx, Wsol, np, mcp, ldb, Bt, np));
+    double* Bt = w.oop() ? w.B : pBt;
+    GPX_TRY(launch_transpose(ctx, w.solution(), np, mcp, gpx_skew_ld(mcp), Bt, np));
     if (pT) GPX_TRY(chol_trsm_right_n_leading(ctx, const_cast<gpx_mat*>(L), np, Bt, np, mcp, pT));
     else GPX_TRY(chol_trsm_right_n(ctx, L->p, L->ld, L->aux, Bt, np, mcp, np));
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)n * (double)mc * (6.0 * (double)d + 25.0),
                  8.0 * ((double)n * (double)mc + (double)n * d));
-    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, nullptr, np, pal, out.coef, out.grad + j0 * d));
+    GPX_TRY(launch_acq_grad(ctx, kp, X->p, n, Zc, mc, Bt, nullptr, np, w.alpha, out.coef, out.grad + j0 * d));
   }
   return out.finish(ctx, cost_host, best, best_cost, grad_host);
 }
@@ -473,13 +458,12 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
   Scratch sc(ctx);
   GPX_TRY(sc.get(np * ld * 8, &Wc));
   if (oop) GPX_TRY(sc.get(np * ldb * 8, &pB));
-  GPX_TRY(sc.get(np * 8, &pal));
+  GPX_TRY(gpx_upload_padded(ctx, sc, alpha, n, np, &pal));
   GPX_TRY(st.take(sc, M, np, q, false));
-  GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   GPX_TRY(st.init(ctx, param));
   // ---- set-up: the posterior pass with W kept.  Not gpx_posterior_chunk: the solve lands in the resident W_C with ITS row
-  // stride, and the squares are reduced once over all of W_C (into hd) ----
+  // stride, and the squares are reduced once over all of W_C (into hd).  Its own step rule, not ChunkRange's: the walk is over
+  // the PADDED columns (mcw at a time, every chunk a multiple of 128 wide) ----
   for (int64_t j0 = 0; j0 < Mp; j0 += mcw) {
     const int64_t mcp = (Mp - j0) < mcw ? (Mp - j0) : mcw;
     const int64_t mc = (M - j0) < mcp ? (M - j0) : mcp;
@@ -525,50 +509,37 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
   const bool grad = grad_host != nullptr;
   KParams kpz = *fv.kp;   // the candidates may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
-  const int64_t mcmax = gpx_eval_chunk(nup);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  const bool oop = chol_cross_oop(nup);
-  const int64_t bytesB = nup * gpx_skew_ld(mc_alloc) * 8, bytes_out = mc_alloc * 8;
-  double *B1, *B2, *Wu = nullptr, *Wa = nullptr, *part, *pm, *su, *sa, *kd, *pv, *bu;
+  const ChunkRange cr(M, gpx_eval_chunk(nup));
+  double *T1 = nullptr, *T2 = nullptr;
+  VfePosteriorWork w(nup, cr.mc_alloc, true);
   AcqOut out;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  GPX_TRY(sc.get(bytesB, &B1));
-  GPX_TRY(sc.get(bytesB, &B2));
-  if (oop || grad) GPX_TRY(sc.get(bytesB, &Wu));
-  if (grad) GPX_TRY(sc.get(bytesB, &Wa));
-  GPX_TRY(sc.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
-  GPX_TRY(sc.get(bytes_out, &pm));
-  GPX_TRY(sc.get(bytes_out, &su));
-  GPX_TRY(sc.get(bytes_out, &sa));
-  GPX_TRY(sc.get(bytes_out, &kd));
-  GPX_TRY(sc.get(bytes_out, &pv));
-  GPX_TRY(out.take(sc, M, mc_alloc, d, grad));
-  if (coeff) {
-    GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
-  } else {   // (GPX_ACQ_VARIANCE: no mean; its weight a is 0)
-    GPX_TRY(sc.get(nup * 8, &bu));
-    GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
+  GPX_TRY(w.take(sc, true));
+  const bool oop = w.oop();
+  if (grad) {   // two more blocks: the targets of the transpositions, or (out of place) the second one Wa's own
+    if (!oop) GPX_TRY(sc.get(w.bytesB, &T1));
+    GPX_TRY(sc.get(w.bytesB, &T2));
+    if (oop) w.Wa = T2;
   }
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
+  GPX_TRY(out.take(sc, M, cr.mc_alloc, d, grad));
+  GPX_TRY(w.beta(ctx, f, coeff, sc));   // (GPX_ACQ_VARIANCE: no coeff, no mean; its weight a is 0)
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0, ldb = gpx_skew_ld(mcp);
     const double* Zc = Z->p + j0 * d;
     // values only: both out-of-place solutions land in the one buffer, as in gpx_vfe_posterior
-    GPX_TRY(vfe_posterior_chunk(ctx, f, kpz, S, Zc, mc, B1, B2, oop ? Wu : nullptr, oop ? (grad ? Wa : Wu) : nullptr, bu, pm, su,
-                                sa, kd, pv, part));
-    GPX_TRY(out.epilogue(ctx, acq, param, pm, pv, nullptr, mc, j0, 8.0 * 4.0 * (double)mc));
+    GPX_TRY(w.run(ctx, f, kpz, S, Zc, mc));
+    GPX_TRY(out.epilogue(ctx, acq, param, w.pm, w.pv, nullptr, mc, j0, 8.0 * 4.0 * (double)mc));
     if (!grad) continue;
     // (Quu^-1 k_u)^T = Wu^T Lu^-1 and (A^-1 k_u)^T = Wa^T La^-1 (mcp x nup, row stride nup), in the two buffers the forward
     // solutions do not occupy
-    const double *solU = oop ? Wu : B1, *solA = oop ? Wa : B2;
-    double *Tu = oop ? B1 : Wu, *Ta = oop ? B2 : Wa;
-    GPX_TRY(launch_transpose(ctx, solU, nup, mcp, ldb, Tu, nup));
+    double *Tu = oop ? w.B1 : T1, *Ta = oop ? w.B2 : T2;
+    GPX_TRY(launch_transpose(ctx, w.solU(), nup, mcp, ldb, Tu, nup));
     GPX_TRY(chol_trsm_right_n(ctx, fv.Lu->p, fv.Lu->ld, fv.Lu->aux, Tu, nup, mcp, nup));
-    GPX_TRY(launch_transpose(ctx, solA, nup, mcp, ldb, Ta, nup));
+    GPX_TRY(launch_transpose(ctx, w.solA(), nup, mcp, ldb, Ta, nup));
     GPX_TRY(chol_trsm_right_n(ctx, fv.La->p, fv.La->ld, fv.La->aux, Ta, nup, mcp, nup));
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nu * (double)mc * (6.0 * (double)d + 26.0),
                  8.0 * (2.0 * (double)nu * (double)mc + (double)nu * d));
-    GPX_TRY(launch_acq_grad(ctx, kpz, S->p, nu, Zc, mc, Tu, Ta, nup, bu, out.coef, out.grad + j0 * d));
+    GPX_TRY(launch_acq_grad(ctx, kpz, S->p, nu, Zc, mc, Tu, Ta, nup, w.bu, out.coef, out.grad + j0 * d));
   }
   return out.finish(ctx, cost_host, best, best_cost, grad_host);
 }
@@ -595,8 +566,8 @@ int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const 
   KParams kpz = *fv.kp;
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Cm));
   const bool oop = chol_cross_oop(nup);
-  const int64_t mcmax = gpx_eval_chunk(nup);
-  const int64_t mcw = Mp < mcmax ? Mp : mcmax, ldb = gpx_skew_ld(mcw);
+  const ChunkRange cr(M, gpx_eval_chunk(nup));
+  const int64_t ldb = gpx_skew_ld(cr.mc_alloc);
   double *pW, *pB, *bu;
   AcqBatchState st;   // v = t, rfix = r, hd = |Lu^-1 k_u|^2 at the set-up
   Scratch sc(ctx);
@@ -607,9 +578,8 @@ int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const 
   GPX_TRY(st.init(ctx, param));
   // ---- set-up: gpx_vfe_acq's chunks.  Not vfe_posterior_chunk: the La solve lands in the resident Wa with ITS row stride; the Lu
   // solve is transient (in place in pB; out of place in the chunk's columns of Wa, which the La solve then overwrites) ----
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE), ldc = gpx_skew_ld(mcp);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0, ldc = gpx_skew_ld(mcp);
     const double* Cc = Cm->p + j0 * d;
     double* Wc = pW + j0;
     GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Cc, mc, 0, nullptr, 0, 0.0, pB, nup, mcp, ldc));

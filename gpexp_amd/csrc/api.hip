@@ -994,6 +994,39 @@ int gpx_entry_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, c
   return Z ? gpx_kparams_sets(ctx, kp, X, Z, C) : 0;
 }
 
+// (gpx_internal.h) the one budget rule
+int64_t gpx_chunk_len(int64_t default_budget, int64_t bytes_per_col) {
+  int64_t budget = default_budget;
+  const char* e = getenv("GPX_CROSS_BYTES");
+  if (e && atoll(e) > 0) budget = atoll(e);
+  const int64_t mc = budget / bytes_per_col / GPX_TILE * GPX_TILE;
+  return mc < GPX_TILE ? GPX_TILE : mc;
+}
+
+// (gpx_internal.h) the uploads of host vectors
+int gpx_fill_padded(gpx_ctx* ctx, double* dev, const double* host, int64_t n, int64_t np) {
+  GPX_HIP(hipMemsetAsync(dev, 0, (size_t)np * 8, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(dev, host, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+int gpx_upload_padded(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t n, int64_t np, double** dev) {
+  GPX_TRY(sc.get(np * 8, dev));
+  return gpx_fill_padded(ctx, *dev, host, n, np);
+}
+int gpx_upload(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t count, double** dev) {
+  *dev = nullptr;
+  if (!host) return 0;
+  GPX_TRY(sc.get(count * 8, dev));
+  GPX_HIP(hipMemcpyAsync(*dev, host, (size_t)count * 8, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+int gpx_model_or_prior(const gpx_mat* L, const gpx_mat* X, const double* alpha, const char* msg, bool* prior) {
+  *prior = !L && !X && !alpha;
+  GPX_ARG(*prior || (L && X && alpha), msg);
+  return 0;
+}
+
 int gpx_posterior_chunk(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,
                         double* B, double* Wout, const double* alpha_dev, double* mean_dev, double* mean_host, double* ssq,
                         double* kd, double* part) {
@@ -1147,10 +1180,8 @@ int gpx_potrs(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* alpha) {
   const int64_t sb = chol_potrs_scratch_bytes(np);
   Scratch sc(ctx);   // (its scope exit completes the copy of alpha)
   double *dv, *ps;
-  GPX_TRY(sc.get(np * 8, &dv));
+  GPX_TRY(gpx_upload_padded(ctx, sc, y, n, np, &dv));
   GPX_TRY(sc.get(sb, &ps));
-  GPX_HIP(hipMemsetAsync(dv, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(dv, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   GPX_TRY(chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, ps));  // caches the block inverses in L
   GPX_HIP(hipMemcpyAsync(alpha, dv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   return 0;
@@ -1201,16 +1232,8 @@ __global__ __launch_bounds__(1024) static void pairwise_mean_kernel(double* __re
   if (threadIdx.x == 0) out[0] = v[0] / (double)count;
 }
 
-// chunk of evaluation points handled at once: keep the (N x Mc) cross matrix under ~16 GiB
-static int64_t eval_chunk(int64_t np) {
-  int64_t budget = (int64_t)16 << 30;
-  const char* e = getenv("GPX_CROSS_BYTES");
-  if (e && atoll(e) > 0) budget = atoll(e);
-  int64_t mc = budget / (np * 8) / GPX_TILE * GPX_TILE;
-  if (mc < GPX_TILE) mc = GPX_TILE;
-  return mc;
-}
-int64_t gpx_eval_chunk(int64_t np) { return eval_chunk(np); }
+// the posterior-shaped passes' use of the budget rule: the (N x Mc) cross matrix under ~16 GiB
+int64_t gpx_eval_chunk(int64_t np) { return gpx_chunk_len((int64_t)16 << 30, np * 8); }
 
 // Shared body; mean/var are host arrays of length M (nullable).  For every chunk of Z: B = K(X, Zc) (N x chunk),
 // mean = B^T alpha (column dots), W = L^-1 B (recursive LEFT triangular solve: NN updates B2 -= L21 W1), var = k(z,z) -
@@ -1225,43 +1248,24 @@ static int posterior_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, con
   const bool var = var_host != nullptr || var_dev != nullptr;
   if (keepW) *keepW = nullptr;
   if (M == 0) return 0;
-  const int64_t mcmax = eval_chunk(np);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  double *pB = nullptr, *pW = nullptr, *pal = nullptr, *pout = nullptr, *ppart = nullptr, *pkd = nullptr;
-  // the cross-solve rule (chol_cross_oop), for the callers that want variances: the mean alone solves nothing
-  const bool oop = var && chol_cross_oop(np);
-  const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
-  const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
-  const int64_t bytes_part = colreduce_partial_elems(np, mc_alloc) * 8 + 8;
+  const ChunkRange cr(M, gpx_eval_chunk(np));
+  PosteriorWork w(np, cr.mc_alloc, var);
   // keepW: the solved W = L^-1 K(X, Z) stays, as a matrix of its own, for the cost's gradient at the same design
   // (gpx_ivar_grad_w) -- when all of Z is one chunk; it then IS the buffer the solution lands in.  The caller's on success only.
   MatHold Wm(ctx);
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
   // all M variances, device (when the caller did not bring its own)
   if (var && !var_dev) GPX_TRY(sc.get(M * 8, &var_dev));
-  if (keepW && var && M <= mcmax && gpx_mat_new(ctx, n, M, 1, Wm.put()) == 0 &&
-      (Wm->prows != np || Wm->ld != ldb_alloc || Wm->bytes < bytesB))
+  if (keepW && var && cr.single() && gpx_mat_new(ctx, n, M, 1, Wm.put()) == 0 &&
+      (Wm->prows != np || Wm->ld != gpx_skew_ld(cr.mc_alloc) || Wm->bytes < w.bytesB))
     Wm.reset();
-  // (the kept matrix's buffer serves as pB or pW; it belongs to the gpx_mat and never goes through the scratch owner)
-  if (Wm.get() && !oop) pB = Wm->p;
-  else GPX_TRY(sc.get(bytesB, &pB));
-  if (oop) {
-    if (Wm.get()) pW = Wm->p;
-    else GPX_TRY(sc.get(bytesB, &pW));
-  }
-  GPX_TRY(sc.get(bytes_out, &pout));
-  GPX_TRY(sc.get(bytes_out, &pkd));
-  GPX_TRY(sc.get(bytes_part, &ppart));
-  if (mean) {
-    GPX_TRY(sc.get(np * 8, &pal));
-    GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  }
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Z->p + j0 * d, mc, pB, pW, pal, pout, mean ? mean + j0 : nullptr,
-                                var ? pout : nullptr, pkd, ppart));
-    if (var) GPX_TRY(launch_vec_sub(ctx, pkd, pout, mc, var_dev + j0));
+  // (the kept matrix's buffer serves as B or W; it belongs to the gpx_mat and never goes through the scratch owner)
+  if (Wm.get()) (w.oop() ? w.W : w.B) = Wm->p;
+  GPX_TRY(w.take(sc, mean != nullptr, false));
+  if (mean) GPX_TRY(w.upload_alpha(ctx, alpha, n));
+  for (const ChunkRange::Step c : cr) {
+    GPX_TRY(w.run(ctx, kp, L, X, Z->p + c.j0 * d, c.mc, mean ? mean + c.j0 : nullptr));
+    if (var) GPX_TRY(launch_vec_sub(ctx, w.kd, w.ssq, c.mc, var_dev + c.j0));
   }
   if (var_host) GPX_HIP(hipMemcpyAsync(var_host, var_dev, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (keepW) *keepW = Wm.release();
@@ -1400,10 +1404,8 @@ int gpx_matvec(gpx_ctx* ctx, const gpx_mat* A, const double* v, double* out) {
   GPX_ARG(A->pcols % 2 == 0 && A->ld % 2 == 0, "matvec needs an even padded width");
   Scratch sc(ctx);   // (its scope exit completes the copy)
   double *pv, *po;
-  GPX_TRY(sc.get(A->pcols * 8, &pv));
+  GPX_TRY(gpx_upload_padded(ctx, sc, v, A->cols, A->pcols, &pv));
   GPX_TRY(sc.get((A->rows > 0 ? A->rows : 1) * 8, &po));
-  GPX_HIP(hipMemsetAsync(pv, 0, (size_t)A->pcols * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(pv, v, (size_t)A->cols * 8, hipMemcpyHostToDevice, ctx->stream));
   GPX_TRY(launch_rowreduce(ctx, A->p, A->ld, A->rows, A->pcols, pv, po));
   GPX_HIP(hipMemcpyAsync(out, po, (size_t)A->rows * 8, hipMemcpyDeviceToHost, ctx->stream));
   return 0;

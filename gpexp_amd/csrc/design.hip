@@ -346,6 +346,20 @@ static int greedy_var_run(gpx_ctx* ctx, int kind, int d, const double* hyp, int 
   return 0;
 }
 
+// (gpx_internal.h)
+int posterior_cov_into(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const gpx_mat* Z, Scratch& sc, double* C,
+                       int64_t ldc) {
+  const int64_t n = L->rows, np = L->prows, m = Z->rows, mp = gpx_round_up(m, GPX_TILE);
+  double *pW, *pWt;
+  GPX_TRY(sc.get(np * mp * 8, &pW));
+  GPX_TRY(sc.get(np * mp * 8, &pWt));
+  GPX_TRY(launch_kfill(ctx, kp, X->p, n, Z->p, m, 0, nullptr, 0, 0.0, pW, np, mp, mp));
+  GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, pW, mp, np, mp));
+  GPX_TRY(launch_transpose(ctx, pW, np, mp, mp, pWt, np));
+  GPX_TRY(launch_kfill(ctx, kp, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, C, mp, mp, ldc));
+  return launch_gemm(ctx, pWt, np, pWt, np, C, ldc, mp, mp, np, true, true, false);
+}
+
 extern "C" {
 
 int gpx_kernel_eval(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const double* A, int64_t na,
@@ -375,18 +389,12 @@ int gpx_posterior_cov(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp
   GPX_ARG(ctx && L && X && Z && cov, "NULL argument");
   KParams kp;
   GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", &kp));
-  const int64_t n = L->rows, np = L->prows, m = Z->rows, mp = gpx_round_up(m > 0 ? m : 1, GPX_TILE);
+  const int64_t m = Z->rows, mp = gpx_round_up(m, GPX_TILE);
   if (m == 0) return 0;
   Scratch sc(ctx);
-  void *pW, *pWt, *pK;
-  GPX_TRY(sc.get(np * mp * 8, &pW));
-  GPX_TRY(sc.get(np * mp * 8, &pWt));
+  double* pK;
   GPX_TRY(sc.get(mp * mp * 8, &pK));
-  GPX_TRY(launch_kfill(ctx, kp, X->p, n, Z->p, m, 0, nullptr, 0, 0.0, (double*)pW, np, mp, mp));
-  GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, (double*)pW, mp, np, mp));
-  GPX_TRY(launch_transpose(ctx, (double*)pW, np, mp, mp, (double*)pWt, np));
-  GPX_TRY(launch_kfill(ctx, kp, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, (double*)pK, mp, mp, mp));
-  GPX_TRY(launch_gemm(ctx, (double*)pWt, np, (double*)pWt, np, (double*)pK, mp, mp, mp, np, true, true, false));
+  GPX_TRY(posterior_cov_into(ctx, kp, L, X, Z, sc, pK, mp));
   GPX_HIP(hipMemcpy2DAsync(cov, (size_t)m * 8, pK, (size_t)mp * 8, (size_t)m * 8, (size_t)m, hipMemcpyDeviceToHost,
                            ctx->stream));
   GPX_HIP(hipStreamSynchronize(ctx->stream));
@@ -450,12 +458,8 @@ int gpx_greedy_ivar_step(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
   GPX_ARG(M > 0 && nmc > 0, "need candidates and integration points");
   const int64_t zp = gpx_round_up(nmc, GPX_TILE);
   // candidate chunk: W_C (np x mc) + G (zp x mc) under ~24 GiB
-  int64_t budget = (int64_t)24 << 30;
-  const char* e = getenv("GPX_CROSS_BYTES");
-  if (e && atoll(e) > 0) budget = atoll(e);
-  int64_t mcmax = budget / ((np + zp) * 8) / GPX_TILE * GPX_TILE;
-  if (mcmax < GPX_TILE) mcmax = GPX_TILE;
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const ChunkRange cr(M, gpx_chunk_len((int64_t)24 << 30, (np + zp) * 8));
+  const int64_t mc_alloc = cr.mc_alloc;
 
   Scratch sc(ctx);
   void *pWz, *pWzt, *pWc, *pG, *pss, *pkd, *pq, *ppart, *pcost;
@@ -487,9 +491,8 @@ int gpx_greedy_ivar_step(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
 
   // ---- candidates, chunked ----
   std::vector<double> cost((size_t)M);
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
     const double* Cc = Cm->p + j0 * d;
     GPX_TRY(launch_kfill(ctx, kp, X->p, n, Cc, mc, 0, nullptr, 0, 0.0, (double*)pWc, np, mcp, mcp));
     GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, (double*)pWc, mcp, np, mcp));

@@ -566,8 +566,7 @@ int fitc_wgrad(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx_mat*
 // dt (np doubles, device) <- alpha = P y:  u = Kuf Gi y = -(Ks y);  w = A^-1 u;  t = Kfu w;  alpha = Gi (y - t), 0 on the padding.
 // dy (np): y, zero padded.  du (nup), part (colreduce partials for nup x np), ps (chol_potrs_scratch_bytes(nup)): scratch.
 int fitc_alpha(gpx_ctx* ctx, const gpx_fitc* f, const double* y, double* dy, double* du, double* dt, double* part, double* ps) {
-  GPX_HIP(hipMemsetAsync(dy, 0, (size_t)f->np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(dy, y, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(gpx_fill_padded(ctx, dy, y, f->n, f->np));
   GPX_HIP(hipMemsetAsync(du, 0, (size_t)f->nup * 8, ctx->stream));
   GPX_TRY(launch_rowreduce(ctx, f->Ks->p, f->Ks->ld, f->nu, f->np, dy, du));
   hipLaunchKernelGGL(negate_kernel, dim3((unsigned)((f->nup + 255) / 256)), dim3(256), 0, ctx->stream, du, f->nup);
@@ -620,11 +619,9 @@ int fitc_wgrad_rows(gpx_ctx* ctx, const KParams& kp, const gpx_mat* A, const gpx
 int vfe_beta_u(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& tmp, double** bu_out) {
   const int64_t np = f->np, nup = f->nup;
   double *dc, *bu, *ps;
-  GPX_TRY(tmp.get(np * 8, &dc));
+  GPX_TRY(gpx_upload_padded(ctx, tmp, coeff, f->n, np, &dc));
   GPX_TRY(tmp.get(nup * 8, &bu));
   GPX_TRY(tmp.get(chol_potrs_scratch_bytes(nup), &ps));
-  GPX_HIP(hipMemsetAsync(dc, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(dc, coeff, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
   GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
   GPX_TRY(launch_rowreduce(ctx, f->Kuf->p, f->Kuf->ld, f->nu, np, dc, bu));
   GPX_TRY(chol_potrs(ctx, f->Lu, bu, ps));
@@ -1207,8 +1204,8 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
   if (M == 0) return 0;
   KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, X, Z));
-  const int64_t mcmax = gpx_eval_chunk(np);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const ChunkRange cr(M, gpx_eval_chunk(np));
+  const int64_t mc_alloc = cr.mc_alloc;
   Scratch tmp(ctx);
   const int64_t ldb = gpx_skew_ld(np), ldu = gpx_skew_ld(nup);
   double *B, *U, *dc = nullptr, *o1, *o2, *kd;
@@ -1217,15 +1214,10 @@ int gpx_fitc_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const 
   GPX_TRY(tmp.get(mc_alloc * 8, &o1));
   GPX_TRY(tmp.get(mc_alloc * 8, &o2));
   GPX_TRY(tmp.get(mc_alloc * 8, &kd));
-  if (mean) {
-    GPX_TRY(tmp.get(np * 8, &dc));
-    GPX_HIP(hipMemsetAsync(dc, 0, (size_t)np * 8, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(dc, coeff, (size_t)f->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  }
+  if (mean) GPX_TRY(gpx_upload_padded(ctx, tmp, coeff, f->n, np, &dc));
   std::vector<double> h1((size_t)mc_alloc), h2((size_t)mc_alloc), hk((size_t)mc_alloc);
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
     const double* Zc = Z->p + j0 * d;
     GPX_TRY(launch_kfill(ctx, kpz, Zc, mc, X->p, f->n, 0, nullptr, 0, 0.0, B, mcp, np, ldb));
     if (mean) {
@@ -1267,45 +1259,33 @@ int gpx_vfe_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double*
   return vfe_grad_impl(ctx, f, kind, d, hyp, nhyp, X, S, y, bound, grad, grad_s);
 }
 
+// the point sets of the VFE predictor's callers: S the model's inducing points, Z unpadded points of its dimension
+static int vfe_point_sets(const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z) {
+  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
+          "point sets do not match");
+  return 0;
+}
+
 // mean[j] = k_u(z_j)^T beta_u (coeff = alpha required),  var[j] = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2 (signed); each nullable
 int gpx_vfe_posterior(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double* mean,
                       double* var) {
   GPX_ARG(ctx && f && S && Z, "NULL argument");
   FITC_KIND(f, true, "vfe_posterior", "call gpx_fitc_posterior");
-  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
-          "point sets do not match");
+  GPX_TRY(vfe_point_sets(f, S, Z));
   GPX_ARG(mean == nullptr || coeff != nullptr, "coeff is required for the mean");
   const int64_t M = Z->rows, d = f->kp.d, nup = f->nup;
   if (M == 0 || (!mean && !var)) return 0;
   KParams kpz = f->kp;  // the evaluation points may reach beyond the training domain
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
-  const int64_t mcmax = gpx_eval_chunk(nup);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
-  const int64_t ldb_alloc = gpx_skew_ld(mc_alloc);
-  // the cross-solve rule (chol_cross_oop), for the callers that want variances: the mean alone solves nothing
-  const bool oop = var && chol_cross_oop(nup);
+  const ChunkRange cr(M, gpx_eval_chunk(nup));
   Scratch tmp(ctx);   // its scope exit is the synchronisation the host results wait for
-  double *B1, *B2 = nullptr, *Wo = nullptr, *part, *pm = nullptr, *su = nullptr, *sa = nullptr, *kd = nullptr, *pv = nullptr;
-  double* bu = nullptr;
-  GPX_TRY(tmp.get(nup * ldb_alloc * 8, &B1));
-  GPX_TRY(tmp.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
-  if (var) {
-    GPX_TRY(tmp.get(nup * ldb_alloc * 8, &B2));
-    if (oop) GPX_TRY(tmp.get(nup * ldb_alloc * 8, &Wo));
-    GPX_TRY(tmp.get(mc_alloc * 8, &su));
-    GPX_TRY(tmp.get(mc_alloc * 8, &sa));
-    GPX_TRY(tmp.get(mc_alloc * 8, &kd));
-    GPX_TRY(tmp.get(mc_alloc * 8, &pv));
-  }
-  if (mean) {
-    GPX_TRY(tmp.get(mc_alloc * 8, &pm));
-    GPX_TRY(vfe_beta_u(ctx, f, coeff, tmp, &bu));
-  }
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    GPX_TRY(vfe_posterior_chunk(ctx, f, kpz, S, Z->p + j0 * d, mc, B1, B2, Wo, Wo, bu, pm, su, sa, kd, pv, part));
-    if (mean) GPX_HIP(hipMemcpyAsync(mean + j0, pm, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (var) GPX_HIP(hipMemcpyAsync(var + j0, pv, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+  VfePosteriorWork w(nup, cr.mc_alloc, var != nullptr);
+  GPX_TRY(w.take(tmp, mean != nullptr));
+  if (mean) GPX_TRY(w.beta(ctx, f, coeff, tmp));
+  for (const ChunkRange::Step c : cr) {
+    GPX_TRY(w.run(ctx, f, kpz, S, Z->p + c.j0 * d, c.mc));
+    if (mean) GPX_HIP(hipMemcpyAsync(mean + c.j0, w.pm, (size_t)c.mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (var) GPX_HIP(hipMemcpyAsync(var + c.j0, w.pv, (size_t)c.mc * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   GPX_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -1317,8 +1297,7 @@ static int vfe_acq_args(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const
   GPX_ARG(ctx && f && S && Z && coeff, "NULL argument");
   FITC_KIND(f, true, what, "the batched acquisition costs are offered on VFE models only");
   GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
-  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
-          "point sets do not match");
+  GPX_TRY(vfe_point_sets(f, S, Z));
   return 0;
 }
 
@@ -1375,8 +1354,7 @@ int gpx_vfe_var_grad_newpt(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, co
   FITC_KIND(f, true, "vfe_var_grad_newpt", "call gpx_fitc_var_grad_newpt");
   FITC_ARG(f->kp.kind == GPX_K_SE || f->kp.kind == GPX_K_MATERN32 || f->kp.kind == GPX_K_MATERN52, "vfe_var_grad_newpt",
            "point derivatives exist for the squared exponential and the isotropic Materns only, not for the Mehler kernel");
-  GPX_ARG(S->rows == f->nu && S->cols == f->kp.d && S->pcols == f->kp.d && Z->cols == f->kp.d && Z->pcols == f->kp.d,
-          "point sets do not match");
+  GPX_TRY(vfe_point_sets(f, S, Z));
   if (Z->rows == 0) return 0;
   // gpx_vfe_acq_grad's own sequence with (a, b) = (0, 1): grad_z var = -2 sum_u dk(z, s_u)/dz gamma(z)[u]
   return vfe_acq_impl(ctx, f, S, nullptr, Z, GPX_ACQ_VARIANCE, 0.0, nullptr, nullptr, nullptr, out);

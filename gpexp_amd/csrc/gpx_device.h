@@ -1,6 +1,6 @@
 // Per-pair and per-workgroup device helpers shared by the element-wise kernels of design.hip, hyper.hip, grad.hip, acq.hip and
 // fitc.hip (gfx950).  __device__ __forceinline__ functions and templates only -- no kernels, no host code.  The tiled fills (kfill.hip)
-// and the reductions of reduce.hip / chol.hip have their own forms and do not come through here.
+// and the sums of reduce.hip / chol.hip have their own forms and do not come through here (reduce.hip's row arg-best does).
 #pragma once
 #include "gpx_internal.h"
 

@@ -317,9 +317,34 @@ int gpx_prof_flush(gpx_ctx* ctx);
     else GPX_SE_DISPATCH(GPX_K_MATERN52, d_, CALL);                             \
   } while (0)
 
-// evaluation points per chunk of the posterior-shaped passes (gpx_posterior, gpx_acq): the N x chunk cross matrix under ~16 GiB,
-// or GPX_CROSS_BYTES
+// ---- chunking and scratch of the posterior-shaped passes ---------------------------------------------------------------------
+// The ONE reader of GPX_CROSS_BYTES (api.hip): columns per chunk that keep `bytes_per_col` bytes a column under the budget -- the
+// caller's default, or GPX_CROSS_BYTES -- rounded down to 128, 128 at least.  gpx_eval_chunk: the N x chunk cross matrix of the
+// posterior-shaped passes (gpx_posterior, gpx_acq) under ~16 GiB.
+int64_t gpx_chunk_len(int64_t default_budget, int64_t bytes_per_col);
 extern "C" __attribute__((visibility("hidden"))) int64_t gpx_eval_chunk(int64_t np);
+// M evaluation points in chunks of at most mcmax: for (const ChunkRange::Step c : cr) visits (j0, mc, mcp = mc padded to 128).
+// widest / mc_alloc: the longest chunk and its padded length, which the per-call buffers are sized by.
+struct ChunkRange {
+  struct Step { int64_t j0, mc, mcp; };
+  struct It {
+    int64_t j0, M, mcmax;
+    Step operator*() const { return {j0, M - j0 < mcmax ? M - j0 : mcmax, gpx_round_up(M - j0 < mcmax ? M - j0 : mcmax, GPX_TILE)}; }
+    void operator++() { j0 += mcmax; }
+    bool operator!=(const It&) const { return j0 < M; }
+  };
+  int64_t M, mcmax, widest, mc_alloc;
+  ChunkRange(int64_t M_, int64_t c) : M(M_), mcmax(c), widest(M_ < c ? M_ : c), mc_alloc(gpx_round_up(widest, GPX_TILE)) {}
+  It begin() const { return {0, M, mcmax}; }
+  It end() const { return {M, M, mcmax}; }
+  bool single() const { return M <= mcmax; }
+  bool last(const Step& c) const { return c.j0 + mcmax >= M; }
+};
+// dev[0, n) = host[0, n), 0 up to np: the one memset-and-copy pair.  gpx_upload_padded takes the np doubles from sc first;
+// gpx_upload (*dev = NULL for a NULL host) the unpadded form.
+int gpx_fill_padded(gpx_ctx* ctx, double* dev, const double* host, int64_t n, int64_t np);
+int gpx_upload_padded(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t n, int64_t np, double** dev);
+int gpx_upload(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t count, double** dev);
 // One chunk Zc (mc points) of those passes -- the ONE sequence behind gpx_posterior, gpx_ivar and gpx_acq, so that their values
 // agree by construction (api.hip):
 //   B = K(X, Zc) (np x mcp, row stride gpx_skew_ld(mcp));   mean_dev = B^T alpha_dev [-> mean_host, mc doubles];
@@ -329,6 +354,12 @@ extern "C" __attribute__((visibility("hidden"))) int64_t gpx_eval_chunk(int64_t 
 int gpx_posterior_chunk(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,
                         double* B, double* Wout, const double* alpha_dev, double* mean_dev, double* mean_host, double* ssq,
                         double* kd, double* part);
+// C (mp x mp, row stride ldc; mp = Z's rows padded to 128) = K(Z,Z) - W^T W with W = L^-1 K(X,Z): the posterior covariance of
+// gpx_posterior_cov, through two np x mp blocks from sc (design.hip)
+int posterior_cov_into(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const gpx_mat* Z, Scratch& sc, double* C,
+                       int64_t ldc);
+// "L, X and alpha are given together, or all three NULL": the rule of the sampler constructors; *prior = all three NULL
+int gpx_model_or_prior(const gpx_mat* L, const gpx_mat* X, const double* alpha, const char* msg, bool* prior);
 
 // ---- kernel launchers (all asynchronous on ctx->stream) ------------------------------------------
 // kfill.hip
@@ -497,9 +528,85 @@ int launch_sum(gpx_ctx* ctx, const double* x, int64_t n, double* d_out);
 int launch_diag(gpx_ctx* ctx, const double* A, int64_t ld, int64_t n, double* out);                 // out[i] = A[i][i], i < n
 int launch_vec_sub(gpx_ctx* ctx, const double* a, const double* b, int64_t n, double* out);        // out[j] = a[j] - b[j], j < n
 
+// One workgroup per row (`rows` of them, row stride ld, mc entries, global index m0 + j): the first minimum (sign > 0) or maximum of
+// the row by vi_min / vi_max on the raw values -- the smaller index wins a tie, a NaN never wins -- merged into the running winner
+// idx / val unless `first`.  gpx_row_argbest_nan (host, after the copies have landed): an all-NaN row, left at index INT64_MAX,
+// becomes index 0 and a NaN value, as np.argmin.
+int launch_row_argbest(gpx_ctx* ctx, const double* rowsp, int64_t rows, int64_t ld, int64_t mc, int64_t m0, int sign, int first,
+                       int64_t* idx, double* val);
+void gpx_row_argbest_nan(int64_t rows, int64_t* idx, double* val);
+
 // hyper.hip: out[q] = sum over the tiles of partial[tile][q], q < nq, in a fixed order (the final pass of the tiled traces)
 int launch_tile_sums(gpx_ctx* ctx, const double* partial, int64_t nblocks, int nq, double* out);
 
 // design.hip
 extern "C" __attribute__((visibility("hidden"))) int gpx_potri_impl(gpx_ctx* ctx, const gpx_mat* L, gpx_mat** outP, int full);
 int launch_transpose(gpx_ctx* ctx, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);
+
+// The input side of those passes (AcqOut, acq.hip, is the output side): the work set of gpx_posterior_chunk for chunks of up to
+// mc_alloc points against a factor of padded order np (var: with the solve and its sums of squares), from the caller's Scratch.  B
+// or W set before take() (posterior_impl's kept matrix) is used as it is.  The means land in `mean` when a block of their own was
+// asked for, else they pass through ssq's.
+struct PosteriorWork {
+  const int64_t np, mc_alloc, bytesB;
+  const bool var;
+  double *B = nullptr, *W = nullptr, *alpha = nullptr, *mean = nullptr, *ssq = nullptr, *kd = nullptr, *part = nullptr;
+
+  PosteriorWork(int64_t np_, int64_t mc_alloc_, bool var_)
+      : np(np_), mc_alloc(mc_alloc_), bytesB(np_ * gpx_skew_ld(mc_alloc_) * 8), var(var_) {}
+  bool oop() const { return var && chol_cross_oop(np); }   // the cross-solve rule: the mean alone solves nothing
+  // outs == false: the mean alone, into a block of the caller's (run's mean_to) -- B, alpha and part only
+  int take(Scratch& sc, bool want_mean, bool mean_block, bool outs = true) {
+    if (!B) GPX_TRY(sc.get(bytesB, &B));
+    if (oop() && !W) GPX_TRY(sc.get(bytesB, &W));
+    if (want_mean) GPX_TRY(sc.get(np * 8, &alpha));
+    if (mean_block) GPX_TRY(sc.get(mc_alloc * 8, &mean));
+    if (outs) GPX_TRY(sc.get(mc_alloc * 8, &ssq));
+    if (outs) GPX_TRY(sc.get(mc_alloc * 8, &kd));
+    return sc.get(colreduce_partial_elems(np, mc_alloc) * 8 + 8, &part);
+  }
+  int upload_alpha(gpx_ctx* ctx, const double* host, int64_t n) { return gpx_fill_padded(ctx, alpha, host, n, np); }
+  int run(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* Zc, int64_t mc,
+          double* mean_host = nullptr, double* mean_to = nullptr) {
+    return gpx_posterior_chunk(ctx, kp, L, X, Zc, mc, B, oop() ? W : nullptr, alpha, mean_to ? mean_to : mean ? mean : ssq,
+                               mean_host, var ? ssq : nullptr, kd, part);
+  }
+  double* solution() const { return oop() ? W : B; }   // holds L^-1 K(X, Zc) after run()
+};
+
+// The VFE counterpart: the work set of vfe_posterior_chunk for chunks of up to mc_alloc points against nup padded inducing points.
+// Out of place both solutions land in Wo; a caller that wants them both afterwards (the gradient) sets Wa to a block of its own.
+struct VfePosteriorWork {
+  const int64_t nup, mc_alloc, bytesB;
+  const bool var;
+  double *B1 = nullptr, *B2 = nullptr, *Wo = nullptr, *Wa = nullptr, *part = nullptr, *pm = nullptr, *su = nullptr, *sa = nullptr;
+  double *kd = nullptr, *pv = nullptr, *bu = nullptr;
+
+  VfePosteriorWork(int64_t nup_, int64_t mc_alloc_, bool var_)
+      : nup(nup_), mc_alloc(mc_alloc_), bytesB(nup_ * gpx_skew_ld(mc_alloc_) * 8), var(var_) {}
+  bool oop() const { return var && chol_cross_oop(nup); }
+  int take(Scratch& sc, bool want_mean) {
+    GPX_TRY(sc.get(bytesB, &B1));
+    GPX_TRY(sc.get(colreduce_partial_elems(nup, mc_alloc) * 8 + 8, &part));
+    if (var) {
+      GPX_TRY(sc.get(bytesB, &B2));
+      if (oop()) GPX_TRY(sc.get(bytesB, &Wo));
+      for (double** o : {&su, &sa, &kd, &pv}) GPX_TRY(sc.get(mc_alloc * 8, o));
+    }
+    if (want_mean) GPX_TRY(sc.get(mc_alloc * 8, &pm));
+    return 0;
+  }
+  // beta_u through vfe_beta_u; coeff == NULL: beta_u = 0 (a cost without a mean term)
+  int beta(gpx_ctx* ctx, const gpx_fitc* f, const double* coeff, Scratch& sc) {
+    if (coeff) return vfe_beta_u(ctx, f, coeff, sc, &bu);
+    GPX_TRY(sc.get(nup * 8, &bu));
+    GPX_HIP(hipMemsetAsync(bu, 0, (size_t)nup * 8, ctx->stream));
+    return 0;
+  }
+  int run(gpx_ctx* ctx, const gpx_fitc* f, const KParams& kpz, const gpx_mat* S, const double* Zc, int64_t mc) {
+    return vfe_posterior_chunk(ctx, f, kpz, S, Zc, mc, B1, B2, Wo, Wo && Wa ? Wa : Wo, bu, pm, su, sa, kd, pv, part);
+  }
+  // hold Lu^-1 K(S, Zc) and La^-1 K(S, Zc) after run() (out of place without a Wa of its own: only the latter survives)
+  double* solU() const { return Wo ? Wo : B1; }
+  double* solA() const { return Wo ? (Wa ? Wa : Wo) : B2; }
+};

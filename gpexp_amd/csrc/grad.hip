@@ -391,22 +391,8 @@ int solve_scratch(gpx_ctx* ctx, Scratch& sc, int64_t np, int64_t mcp, double** T
   return sc.get(mcp * chol_binv_order(np) * 8, T);
 }
 
-int upload(gpx_ctx* ctx, Scratch& sc, const double* host, int64_t count, double** dev) {
-  *dev = nullptr;
-  if (!host) return 0;
-  GPX_TRY(sc.get(count * 8, dev));
-  GPX_HIP(hipMemcpyAsync(*dev, host, (size_t)count * 8, hipMemcpyHostToDevice, ctx->stream));
-  return 0;
-}
-
 // evaluation points per chunk: beta and the transpose scratch / C_l (two np x mc matrices) + the output slab under ~12 GiB
-int64_t grad_chunk(int64_t np) {
-  int64_t budget = (int64_t)12 << 30;
-  const char* e = getenv("GPX_CROSS_BYTES");
-  if (e && atoll(e) > 0) budget = atoll(e);
-  int64_t mc = budget / (3 * np * 8) / GPX_TILE * GPX_TILE;
-  return mc < GPX_TILE ? GPX_TILE : mc;
-}
+int64_t grad_chunk(int64_t np) { return gpx_chunk_len((int64_t)12 << 30, 3 * np * 8); }
 
 }  // namespace
 
@@ -434,7 +420,7 @@ int gpx_ivar_grad_w(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, 
   GPX_TRY(sc.get(np * np * 8, &pS));
   GPX_TRY(sc.get(n * d * 8, &pg));
   double* d_nd;
-  GPX_TRY(upload(ctx, sc, noise_deriv, n * d, &d_nd));
+  GPX_TRY(gpx_upload(ctx, sc, noise_deriv, n * d, &d_nd));
   double *W, *T;
   GPX_TRY(solve_scratch(ctx, sc, np, mp, &T));
   GPX_ARG(Wkept == nullptr || (Wkept->prows == np && Wkept->pcols == mp && Wkept->rows == n && Wkept->cols == m),
@@ -553,8 +539,8 @@ static int var_grad_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   const int64_t n = fitc ? fitc_n(fitc) : L->rows, np = fitc ? fitc_np(fitc) : L->prows, M = Z->rows;
   GPX_ARG(np <= 65535, "var_grad: at most 65535 training points");
-  const int64_t mcmax = grad_chunk(np);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const ChunkRange cr(M, grad_chunk(np));
+  const int64_t mc_alloc = cr.mc_alloc;
   Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pW, *pWt, *pA, *pO;
   GPX_TRY(sc.get(np * mc_alloc * 8, &pW));
@@ -562,9 +548,9 @@ static int var_grad_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
   GPX_TRY(sc.get(np * np * 8, &pA));
   GPX_TRY(sc.get(n * mc_alloc * 8, &pO));
   double *d_nd, *d_eb, *d_db;
-  GPX_TRY(upload(ctx, sc, noise_deriv, n * d, &d_nd));
-  GPX_TRY(upload(ctx, sc, eval_bias, n, &d_eb));
-  GPX_TRY(upload(ctx, sc, dk_bias, n * d, &d_db));
+  GPX_TRY(gpx_upload(ctx, sc, noise_deriv, n * d, &d_nd));
+  GPX_TRY(gpx_upload(ctx, sc, eval_bias, n, &d_eb));
+  GPX_TRY(gpx_upload(ctx, sc, dk_bias, n * d, &d_db));
   double* T = nullptr;
   void* pU = nullptr;
   if (fitc) GPX_TRY(sc.get(mc_alloc * fitc_nup(fitc) * 8, &pU));
@@ -581,10 +567,8 @@ static int var_grad_impl(gpx_ctx* ctx, int kind, int d, const double* hyp, int n
                      hipEventCreateWithFlags(&evd[1], hipEventDisableTiming) == hipSuccess;
   struct Item { int64_t j0, mc, mcp; int l; };
   std::vector<Item> items;
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    for (int l = 0; l < d; ++l) items.push_back({j0, mc, gpx_round_up(mc, GPX_TILE), l});
-  }
+  for (const ChunkRange::Step c : cr)
+    for (int l = 0; l < d; ++l) items.push_back({c.j0, c.mc, c.mcp, l});
   double *W = nullptr, *Cl = nullptr;
   auto compute = [&](const Item& it, int b) -> int {
     const double* Zc = Z->p + it.j0 * d;
@@ -631,8 +615,8 @@ static int var_grad_newpt_impl(gpx_ctx* ctx, int kind, int d, const double* hyp,
   GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
   GPX_TRY(gpx_kparams_sets(ctx, &kp, X, Z));
   const int64_t n = fitc ? fitc_n(fitc) : L->rows, np = fitc ? fitc_np(fitc) : L->prows, M = Z->rows;
-  const int64_t mcmax = grad_chunk(np);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const ChunkRange cr(M, grad_chunk(np));
+  const int64_t mc_alloc = cr.mc_alloc;
   Scratch sc(ctx, Scratch::Device);   // the passes below span the context's streams
   void *pW, *pWt, *pO;
   GPX_TRY(sc.get(np * mc_alloc * 8, &pW));
@@ -642,9 +626,8 @@ static int var_grad_newpt_impl(gpx_ctx* ctx, int kind, int d, const double* hyp,
   void* pU = nullptr;
   if (fitc) GPX_TRY(sc.get(mc_alloc * fitc_nup(fitc) * 8, &pU));
   else GPX_TRY(solve_scratch(ctx, sc, np, mc_alloc, &T));
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax;
-    const int64_t mcp = gpx_round_up(mc, GPX_TILE);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
     double* beta;
     if (kind != GPX_K_MEHLER) {   // beta^T: row m contiguous over the training points, and no transpose back
       GPX_TRY(solve_beta(ctx, kp, L, X, Z->p + j0 * d, mc, mcp, nullptr, (double*)pW, (double*)pWt, T, 1, &beta, nullptr, fitc,

@@ -164,8 +164,7 @@ inline dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // dv (np doubles) <- alpha = K^-1 y: y zero padded, solved in place
 int loo_alpha(gpx_ctx* ctx, const gpx_mat* L, const double* y, double* dy, double* dv, double* potrs_scratch) {
   const int64_t n = L->rows, np = L->prows;
-  GPX_HIP(hipMemsetAsync(dy, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(gpx_fill_padded(ctx, dy, y, n, np));
   GPX_HIP(hipMemcpyAsync(dv, dy, (size_t)np * 8, hipMemcpyDeviceToDevice, ctx->stream));
   return chol_potrs(ctx, const_cast<gpx_mat*>(L), dv, potrs_scratch);  // caches the block inverses in L, as gpx_potrs does
 }

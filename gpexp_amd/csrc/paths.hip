@@ -119,32 +119,6 @@ __global__ __launch_bounds__(256) void paths_eval_kernel(KParams kp, const doubl
   }
 }
 
-// per path (one workgroup per row of the chunk): the first minimum (sign > 0) or maximum of the row, merged into the running
-// winner of the earlier chunks (vi_min / vi_max: the smaller index wins a tie).  An all-NaN row leaves index INT64_MAX.
-__global__ __launch_bounds__(256) void paths_argbest_kernel(const double* __restrict__ rows, int64_t ld, int64_t mc, int64_t m0,
-                                                            int sign, int first, int64_t* __restrict__ idx,
-                                                            double* __restrict__ val) {
-  __shared__ double sv[256];
-  __shared__ int64_t si[256];
-  const double* __restrict__ row = rows + (int64_t)blockIdx.x * ld;
-  VI v{sign > 0 ? __builtin_inf() : -__builtin_inf(), INT64_MAX};
-  if (sign > 0) {
-    for (int64_t j = threadIdx.x; j < mc; j += 256) v = vi_min(v, VI{row[j], m0 + j});
-    v = block_arg_reduce(v, sv, si, 256, vi_min);
-  } else {
-    for (int64_t j = threadIdx.x; j < mc; j += 256) v = vi_max(v, VI{row[j], m0 + j});
-    v = block_arg_reduce(v, sv, si, 256, vi_max);
-  }
-  if (threadIdx.x == 0) {
-    if (!first) {
-      const VI prev{val[blockIdx.x], idx[blockIdx.x]};
-      v = sign > 0 ? vi_min(prev, v) : vi_max(prev, v);
-    }
-    idx[blockIdx.x] = v.i;
-    val[blockIdx.x] = v.v;
-  }
-}
-
 // F[s][i] += eps[s][i]  (F: row stride ld; eps: S x n)
 __global__ __launch_bounds__(256) void paths_addeps_kernel(double* __restrict__ F, int64_t ld, const double* __restrict__ eps,
                                                            int64_t n, int64_t S) {
@@ -284,8 +258,8 @@ int gpx_paths_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp,
   GPX_ARG(ctx && omega && phase && w && out, "NULL argument");
   GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
           "paths: stationary kernels only (squared exponential, Matern 3/2, Matern 5/2)");
-  const bool prior = !L && !X && !alpha;
-  GPX_ARG(prior || (L && X && alpha), "paths: L, X and alpha are given together, or all three NULL (prior paths)");
+  bool prior;
+  GPX_TRY(gpx_model_or_prior(L, X, alpha, "paths: L, X and alpha are given together, or all three NULL (prior paths)", &prior));
   GPX_ARG(nfeat >= 1, "paths: needs at least one feature");
   GPX_ARG(S >= 1, "paths: needs at least one path");
   KParams kp;
@@ -353,27 +327,25 @@ int gpx_paths_eval(gpx_ctx* ctx, const gpx_paths* ps, const gpx_mat* Z, double* 
   KParams kz = ps->kp;
   GPX_TRY(gpx_kparams_sets(ctx, &kz, Z));   // (refuses a non-finite coordinate; the centre it computes is not used here)
   const int64_t M = Z->rows, S = ps->S, R = ps->Lp + ps->Np;
-  const int64_t mcmax = gpx_eval_chunk(ps->Sp), mc_alloc = M < mcmax ? M : mcmax;
+  const ChunkRange cr(M, gpx_eval_chunk(ps->Sp));
   {
     double *outd, *dval = nullptr;
     int64_t* didx = nullptr;
     Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-    GPX_TRY(sc.get(S * mc_alloc * 8, &outd));
+    GPX_TRY(sc.get(S * cr.widest * 8, &outd));
     if (sign != 0) {
       GPX_TRY(sc.get(S * 8, &didx));
       GPX_TRY(sc.get(S * 8, &dval));
     }
-    for (int64_t m0 = 0; m0 < M; m0 += mcmax) {
-      const int64_t mc = (M - m0) < mcmax ? (M - m0) : mcmax;
+    for (const ChunkRange::Step c : cr) {
+      const int64_t m0 = c.j0, mc = c.mc;
       GPX_TRY(launch_paths_eval(ctx, ps, R, Z->p + m0 * d, mc, outd, mc));
       if (out)
         GPX_HIP(hipMemcpy2DAsync(out + m0, (size_t)M * 8, outd, (size_t)mc * 8, (size_t)mc * 8, (size_t)S, hipMemcpyDeviceToHost,
                                  ctx->stream));
       if (sign != 0) {
         ProfScope pf(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)S * (double)mc);
-        hipLaunchKernelGGL(paths_argbest_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, (const double*)outd, mc, mc, m0,
-                           sign, m0 == 0 ? 1 : 0, didx, dval);
-        GPX_HIP(hipGetLastError());
+        GPX_TRY(launch_row_argbest(ctx, outd, S, mc, mc, m0, sign, m0 == 0 ? 1 : 0, didx, dval));
       }
     }
     if (sign != 0) {
@@ -381,12 +353,7 @@ int gpx_paths_eval(gpx_ctx* ctx, const gpx_paths* ps, const gpx_mat* Z, double* 
       if (best_val) GPX_HIP(hipMemcpyAsync(best_val, dval, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
   }
-  if (sign != 0)
-    for (int64_t s = 0; s < S; ++s)
-      if (best_idx[s] == INT64_MAX) {   // a row of NaNs: index 0, as np.argmin
-        best_idx[s] = 0;
-        if (best_val) best_val[s] = __builtin_nan("");
-      }
+  if (sign != 0) gpx_row_argbest_nan(S, best_idx, best_val);
   return 0;
 }
 

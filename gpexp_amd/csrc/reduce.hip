@@ -7,7 +7,7 @@
 // arg-max / arg-min selections built on them -- do not depend on scheduling.
 #include <algorithm>
 
-#include "gpx_internal.h"
+#include "gpx_device.h"
 
 namespace {
 
@@ -211,6 +211,46 @@ int launch_vec_sub(gpx_ctx* ctx, const double* a, const double* b, int64_t n, do
 }
 
 // test hook (host logic only, no device work): chunk count a rows x pcols reduction launches with, and the buffer bound
+// (gpx_internal.h) An all-NaN row leaves index INT64_MAX: gpx_row_argbest_nan's part.
+__global__ __launch_bounds__(256) static void row_argbest_kernel(const double* __restrict__ rows, int64_t ld, int64_t mc, int64_t m0,
+                                                                 int sign, int first, int64_t* __restrict__ idx,
+                                                                 double* __restrict__ val) {
+  __shared__ double sv[256];
+  __shared__ int64_t si[256];
+  const double* __restrict__ row = rows + (int64_t)blockIdx.x * ld;
+  VI v{sign > 0 ? __builtin_inf() : -__builtin_inf(), INT64_MAX};
+  if (sign > 0) {
+    for (int64_t j = threadIdx.x; j < mc; j += 256) v = vi_min(v, VI{row[j], m0 + j});
+    v = block_arg_reduce(v, sv, si, 256, vi_min);
+  } else {
+    for (int64_t j = threadIdx.x; j < mc; j += 256) v = vi_max(v, VI{row[j], m0 + j});
+    v = block_arg_reduce(v, sv, si, 256, vi_max);
+  }
+  if (threadIdx.x == 0) {
+    if (!first) {
+      const VI prev{val[blockIdx.x], idx[blockIdx.x]};
+      v = sign > 0 ? vi_min(prev, v) : vi_max(prev, v);
+    }
+    idx[blockIdx.x] = v.i;
+    val[blockIdx.x] = v.v;
+  }
+}
+
+int launch_row_argbest(gpx_ctx* ctx, const double* rowsp, int64_t rows, int64_t ld, int64_t mc, int64_t m0, int sign, int first,
+                       int64_t* idx, double* val) {
+  hipLaunchKernelGGL(row_argbest_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, rowsp, ld, mc, m0, sign, first, idx, val);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+void gpx_row_argbest_nan(int64_t rows, int64_t* idx, double* val) {
+  for (int64_t s = 0; s < rows; ++s)
+    if (idx[s] == INT64_MAX) {
+      idx[s] = 0;
+      if (val) val[s] = __builtin_nan("");
+    }
+}
+
 extern "C" int gpx_dbg_colreduce_plan(int64_t rows, int64_t pcols, int64_t* nchunk, int64_t* bound_elems) {
   if (rows < 1 || pcols < 1 || !nchunk || !bound_elems) return -1;
   int64_t chunk;

@@ -20,7 +20,7 @@
 // ascending k whatever tile size the launch picks; the tile size only moves the END of a row tile's k range, and what lies
 // between the two ends is the zero part of F, which adds +0 exactly -- so a sample's bits depend neither on S nor on the chunking
 // nor on the other samples of the call.  psampler_epilogue_kernel adds the mean and turns Y (M x S) into sample-major rows;
-// psampler_argbest_kernel reduces a row to its first minimum / maximum (vi_min: the smaller index wins a tie).
+// launch_row_argbest (reduce.hip) reduces a row to its first minimum / maximum (the smaller index wins a tie).
 //
 // q-EI (gpx_acq_qei).  cost_b = -(1/S) sum_s max(0, fBest - min_j (mu_bj + (F_b xi_s)_j)), F_b = chol(C_b + nugget I).  The means
 // and W = L^-1 K(X, Zb) come from gpx_posterior_chunk, chunked over WHOLE batches; qei_kernel does the rest.  A workgroup owns a
@@ -63,13 +63,6 @@ struct PolicyScope {
     ctx->piv_skip = piv_skip;
   }
 };
-
-int64_t cross_budget() {
-  int64_t budget = (int64_t)16 << 30;
-  const char* e = getenv("GPX_CROSS_BYTES");
-  if (e && atoll(e) > 0) budget = atoll(e);
-  return budget;
-}
 
 __global__ __launch_bounds__(256) void psampler_nugget_kernel(double* __restrict__ F, int64_t ld, int64_t m, double nugget) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -122,30 +115,13 @@ __global__ __launch_bounds__(256) void psampler_epilogue_kernel(const double* __
     if (s0 + r < sc && j0 + tx < m) out[(s0 + r) * m + j0 + tx] = mj + tile[tx][r];
 }
 
-// per sample (one workgroup per row): the FIRST index of the minimum of sign * row, and the row's value there
-__global__ __launch_bounds__(256) void psampler_argbest_kernel(const double* __restrict__ rows, int64_t m, double sign,
-                                                               int64_t* __restrict__ idx, double* __restrict__ val) {
-  __shared__ double sv[256];
-  __shared__ int64_t si[256];
-  const double* __restrict__ row = rows + (int64_t)blockIdx.x * m;
-  VI v{__builtin_inf(), INT64_MAX};
-  for (int64_t j = threadIdx.x; j < m; j += 256) v = vi_min(v, VI{sign * row[j], j});
-  const VI r = block_arg_reduce(v, sv, si, 256, vi_min);
-  if (threadIdx.x == 0) {
-    const int64_t i = r.i == INT64_MAX ? 0 : r.i;   // (a row of NaNs: index 0, as np.argmin)
-    idx[blockIdx.x] = i;
-    val[blockIdx.x] = row[i];
-  }
-}
-
 // draw / argbest: S samples in chunks whose work matrices stay under the cross-matrix budget
 int psampler_run(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi, int64_t S, int sign, double* samples, int64_t* out_idx,
                  double* out_val) {
   const int64_t m = ps->m, mp = ps->mp;
   // per sample: a column of Xt and of Y (mp each), a row of the staged Xi and of the result (m each)
-  int64_t scmax = cross_budget() / ((2 * mp + 2 * m) * 8) / GPX_TILE * GPX_TILE;
-  if (scmax < GPX_TILE) scmax = GPX_TILE;
-  const int64_t sc_alloc = S < scmax ? S : scmax, scp_alloc = gpx_round_up(sc_alloc, GPX_TILE);
+  const ChunkRange cr(S, gpx_chunk_len((int64_t)16 << 30, (2 * mp + 2 * m) * 8));
+  const int64_t sc_alloc = cr.widest, scp_alloc = cr.mc_alloc;
   double *stage, *Xt, *Y, *outd, *dval = nullptr;
   int64_t* didx = nullptr;
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
@@ -157,8 +133,8 @@ int psampler_run(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi, int64_t
     GPX_TRY(sc.get(sc_alloc * 8, &didx));
     GPX_TRY(sc.get(sc_alloc * 8, &dval));
   }
-  for (int64_t s0 = 0; s0 < S; s0 += scmax) {
-    const int64_t scn = (S - s0) < scmax ? (S - s0) : scmax, scp = gpx_round_up(scn, GPX_TILE);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t s0 = c.j0, scn = c.mc, scp = c.mcp;
     GPX_HIP(hipMemcpyAsync(stage, xi + s0 * m, (size_t)(scn * m * 8), hipMemcpyHostToDevice, ctx->stream));
     const dim3 grid((unsigned)(scp / 32), (unsigned)(mp / 32));
     hipLaunchKernelGGL(psampler_xi_kernel, grid, dim3(256), 0, ctx->stream, (const double*)stage, scn, m, Xt, scp);
@@ -170,9 +146,7 @@ int psampler_run(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi, int64_t
     if (samples) GPX_HIP(hipMemcpyAsync(samples + s0 * m, outd, (size_t)(scn * m * 8), hipMemcpyDeviceToHost, ctx->stream));
     if (out_idx) {
       ProfScope pf(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)scn * (double)m);
-      hipLaunchKernelGGL(psampler_argbest_kernel, dim3((unsigned)scn), dim3(256), 0, ctx->stream, (const double*)outd, m,
-                         sign > 0 ? 1.0 : -1.0, didx, dval);
-      GPX_HIP(hipGetLastError());
+      GPX_TRY(launch_row_argbest(ctx, outd, scn, m, m, 0, sign, 1, didx, dval));   // (one chunk covers the whole row)
       GPX_HIP(hipMemcpyAsync(out_idx + s0, didx, (size_t)scn * 8, hipMemcpyDeviceToHost, ctx->stream));
       if (out_val) GPX_HIP(hipMemcpyAsync(out_val + s0, dval, (size_t)scn * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -402,27 +376,19 @@ int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
              int64_t* n_bad, double* dbg_mean, double* dbg_C, double* dbg_F) {
   const int64_t n = L->rows, np = L->prows, B = Zb->rows / q, d = kp.d;
   const QeiPlan pl = qei_plan((int)q);
-  // whole batches per chunk (whole workgroup spans while the chunk holds one)
+  // whole batches per chunk (whole workgroup spans while the chunk holds one): its own step rule, not ChunkRange's
   const int64_t mcmax = gpx_eval_chunk(np);
   int64_t bc = mcmax / q;
   if (bc >= pl.G) bc = bc / pl.G * pl.G;
   if (bc > B) bc = B;
   const int64_t nchunks = (B + bc - 1) / bc, ngroups = (bc + pl.G - 1) / pl.G * nchunks;
-  const int64_t mc_alloc = gpx_round_up(bc * q, GPX_TILE), ldb_alloc = gpx_skew_ld(mc_alloc);
-  const bool oop = chol_cross_oop(np);
-  const int64_t bytesB = np * ldb_alloc * 8, bytes_out = mc_alloc * 8;
-  double *pB, *pW = nullptr, *pal, *pmean, *pssq, *pkd, *ppart, *dxi, *dcost, *part_c, *best_c, *dC = nullptr, *dF = nullptr;
+  double *dxi, *dcost, *part_c, *best_c, *dC = nullptr, *dF = nullptr;
   int64_t *part_i, *best_i;
   int* dbad;
+  PosteriorWork w(np, gpx_round_up(bc * q, GPX_TILE), true);
   std::vector<int> hbad((size_t)ngroups, 0);
   Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  GPX_TRY(sc.get(bytesB, &pB));
-  if (oop) GPX_TRY(sc.get(bytesB, &pW));
-  GPX_TRY(sc.get(np * 8, &pal));
-  GPX_TRY(sc.get(bytes_out, &pmean));
-  GPX_TRY(sc.get(bytes_out, &pssq));
-  GPX_TRY(sc.get(bytes_out, &pkd));
-  GPX_TRY(sc.get(colreduce_partial_elems(np, mc_alloc) * 8 + 8, &ppart));
+  GPX_TRY(w.take(sc, true, true));
   GPX_TRY(sc.get(S * q * 8, &dxi));
   GPX_TRY(sc.get(B * 8, &dcost));
   GPX_TRY(sc.get(ngroups * 8, &part_c));
@@ -434,8 +400,7 @@ int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     GPX_TRY(sc.get(B * q * q * 8, &dC));
     GPX_TRY(sc.get(B * q * q * 8, &dF));
   }
-  GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(w.upload_alpha(ctx, alpha, n));
   GPX_HIP(hipMemcpyAsync(dxi, xi, (size_t)(S * q * 8), hipMemcpyHostToDevice, ctx->stream));
   int64_t g0 = 0;
   for (int64_t b0 = 0; b0 < B; b0 += bc) {
@@ -443,9 +408,8 @@ int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
     const int64_t ldb = gpx_skew_ld(gpx_round_up(mc, GPX_TILE)), groups = (nb + pl.G - 1) / pl.G;
     const double* Zc = Zb->p + b0 * q * d;
     // gpx_posterior's own per-chunk step: the means are GP.evaluate's, W the solve every variance comes from
-    GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Zc, mc, pB, oop ? pW : nullptr, pal, pmean, dbg_mean ? dbg_mean + b0 * q : nullptr,
-                                pssq, pkd, ppart));
-    const double* Wsol = oop ? pW : pB;
+    GPX_TRY(w.run(ctx, kp, L, X, Zc, mc, dbg_mean ? dbg_mean + b0 * q : nullptr));
+    const double *Wsol = w.solution(), *pmean = w.mean;
     ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nb * ((double)n * (double)(q * (q + 1)) + (double)S * (double)(q * (q + 1))),
                  8.0 * (double)n * (double)mc);
 #define GPX_QEI(QM_)                                                                                                            \
@@ -515,8 +479,8 @@ int gpx_psampler_shape(const gpx_psampler* ps, int64_t* m) {
 int gpx_psampler_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                         const double* alpha, const gpx_mat* Z, double nugget, gpx_psampler** out) {
   GPX_ARG(ctx && Z && out, "NULL argument");
-  const bool prior = !L && !X && !alpha;
-  GPX_ARG(prior || (L && X && alpha), "psampler: L, X and alpha are given together, or all three NULL (the prior)");
+  bool prior;
+  GPX_TRY(gpx_model_or_prior(L, X, alpha, "psampler: L, X and alpha are given together, or all three NULL (the prior)", &prior));
   GPX_ARG(nugget >= 0.0, "psampler: the nugget must not be negative");
   GPX_ARG(Z->rows >= 1, "psampler: needs at least one point");
   KParams kp;
@@ -541,29 +505,13 @@ int gpx_psampler_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nh
     GPX_HIP(hipMemsetAsync(ps->mean, 0, (size_t)mp * 8, ctx->stream));
     GPX_TRY(launch_kfill(ctx, kp, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, F->p, mp, mp, F->ld));
   } else {
-    const int64_t n = L->rows, np = L->prows;
     // the mean: gpx_posterior's chunks and launches (the bits it returns)
-    const int64_t mcmax = gpx_eval_chunk(np);
-    const int64_t mc_alloc = gpx_round_up(m < mcmax ? m : mcmax, GPX_TILE);
-    double *pB, *pal, *ppart, *pW, *pWt;
-    GPX_TRY(sc.get(np * gpx_skew_ld(mc_alloc) * 8, &pB));
-    GPX_TRY(sc.get(np * 8, &pal));
-    GPX_TRY(sc.get(colreduce_partial_elems(np, mc_alloc) * 8 + 8, &ppart));
-    GPX_HIP(hipMemsetAsync(pal, 0, (size_t)np * 8, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(pal, alpha, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    for (int64_t j0 = 0; j0 < m; j0 += mcmax) {
-      const int64_t mc = (m - j0) < mcmax ? (m - j0) : mcmax;
-      GPX_TRY(gpx_posterior_chunk(ctx, kp, L, X, Z->p + j0 * d, mc, pB, nullptr, pal, ps->mean + j0, nullptr, nullptr, nullptr,
-                                  ppart));
-    }
-    // C = K(Z,Z) - W^T W: gpx_posterior_cov's sequence, into F's storage
-    GPX_TRY(sc.get(np * mp * 8, &pW));
-    GPX_TRY(sc.get(np * mp * 8, &pWt));
-    GPX_TRY(launch_kfill(ctx, kp, X->p, n, Z->p, m, 0, nullptr, 0, 0.0, pW, np, mp, mp));
-    GPX_TRY(chol_trsm_left(ctx, L->p, L->ld, L->aux, pW, mp, np, mp));
-    GPX_TRY(launch_transpose(ctx, pW, np, mp, mp, pWt, np));
-    GPX_TRY(launch_kfill(ctx, kp, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, F->p, mp, mp, F->ld));
-    GPX_TRY(launch_gemm(ctx, pWt, np, pWt, np, F->p, F->ld, mp, mp, np, true, true, false));
+    const ChunkRange cr(m, gpx_eval_chunk(L->prows));
+    PosteriorWork w(L->prows, cr.mc_alloc, false);
+    GPX_TRY(w.take(sc, true, false, false));
+    GPX_TRY(w.upload_alpha(ctx, alpha, L->rows));
+    for (const ChunkRange::Step c : cr) GPX_TRY(w.run(ctx, kp, L, X, Z->p + c.j0 * d, c.mc, nullptr, ps->mean + c.j0));
+    GPX_TRY(posterior_cov_into(ctx, kp, L, X, Z, sc, F->p, F->ld));
   }
   hipLaunchKernelGGL(psampler_nugget_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, F->p, F->ld, m, nugget);
   GPX_HIP(hipGetLastError());
@@ -611,7 +559,9 @@ int gpx_psampler_argbest(gpx_ctx* ctx, const gpx_psampler* ps, const double* xi,
   GPX_ARG(ctx && ps && xi && out_idx, "NULL argument");
   GPX_ARG(S >= 1, "psampler: needs at least one sample");
   GPX_ARG(sign == 1 || sign == -1, "psampler: sign must be +1 (minimum) or -1 (maximum)");
-  return psampler_run(ctx, ps, xi, S, sign, samples, out_idx, out_val);
+  GPX_TRY(psampler_run(ctx, ps, xi, S, sign, samples, out_idx, out_val));   // (synchronised: its Scratch is gone)
+  gpx_row_argbest_nan(S, out_idx, out_val);
+  return 0;
 }
 
 int gpx_acq_qei(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,

@@ -181,8 +181,8 @@ int vfe_var_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const g
   GPX_TRY(gpx_kparams_sets(ctx, &kpx, X, S));
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
   const int64_t ldn = gpx_skew_ld(nup);
-  const int64_t mcmax = gpx_eval_chunk(np * (d + 2) + nup);   // E, D and the d row blocks of the result, and C^T
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE), ldm = gpx_skew_ld(mc_alloc);
+  const ChunkRange cr(M, gpx_eval_chunk(np * (d + 2) + nup));   // E, D and the d row blocks of the result, and C^T
+  const int64_t mc_alloc = cr.mc_alloc, ldm = gpx_skew_ld(mc_alloc);
   Scratch tmp(ctx);   // its scope exit is the synchronisation the host result waits for
   double *Kxs, *Dk, *Ct, *E, *D, *O;
   GPX_TRY(tmp.get(np * ldn * 8, &Kxs));
@@ -192,8 +192,8 @@ int vfe_var_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const g
   GPX_TRY(tmp.get(np * ldm * 8, &D));
   GPX_TRY(tmp.get(n * d * ldm * 8, &O));
   GPX_TRY(launch_kfill(ctx, kpx, X->p, n, S->p, nu, 0, nullptr, 0, 0.0, Kxs, np, nup, ldn));
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax, mcp = gpx_round_up(mc, GPX_TILE);
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
     // C^T = K(Zc,S) La^-T La^-1 (mcp x nup)
     GPX_TRY(launch_kfill(ctx, kpz, Z->p + j0 * d, mc, S->p, nu, 0, nullptr, 0, 0.0, Ct, mcp, nup, ldn));
     GPX_TRY(chol_trsm_right(ctx, fv.La->p, fv.La->ld, fv.La->aux, Ct, ldn, mcp, nup));
@@ -209,7 +209,7 @@ int vfe_var_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const g
     }
     GPX_HIP(hipMemcpy2DAsync(out + j0, (size_t)M * 8, O, (size_t)ldm * 8, (size_t)mc * 8, (size_t)(n * d), hipMemcpyDeviceToHost,
                              ctx->stream));
-    if (j0 + mcmax < M) GPX_HIP(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites O
+    if (!cr.last(c)) GPX_HIP(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites O
   }
   return 0;
 }
@@ -249,21 +249,20 @@ int gpx_vfe_design_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int 
   // from zero and the scale is -1 / M
   KParams kpz = ds->kp;
   GPX_TRY(gpx_kparams_sets(ctx, &kpz, ds->S, Z));
-  const int64_t mcmax = gpx_eval_chunk(nup);
-  const int64_t mc_alloc = gpx_round_up(M < mcmax ? M : mcmax, GPX_TILE);
+  const ChunkRange cr(M, gpx_eval_chunk(nup));
   const bool oop = chol_cross_oop(nup);
   MatHold Y(ctx), W(ctx);
   GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, Y.put()));
   if (oop) GPX_TRY(gpx_mat_new(ctx, nu, nu, 1, W.put()));
   Scratch tmp(ctx);
   double *B, *kd, *dg;
-  GPX_TRY(tmp.get(nup * gpx_skew_ld(mc_alloc) * 8, &B));
+  GPX_TRY(tmp.get(nup * gpx_skew_ld(cr.mc_alloc) * 8, &B));
   GPX_TRY(tmp.get(M * 8, &kd));
   GPX_TRY(tmp.get((nup + 8) * 8, &dg));
   GPX_HIP(hipMemsetAsync(ds->Gz->p, 0, (size_t)ds->Gz->bytes, ctx->stream));
-  for (int64_t j0 = 0; j0 < M; j0 += mcmax) {
-    const int64_t mc = (M - j0) < mcmax ? (M - j0) : mcmax, mcp = gpx_round_up(mc, GPX_TILE), ldb = gpx_skew_ld(mcp);
-    GPX_TRY(launch_kfill(ctx, kpz, ds->S->p, nu, Z->p + j0 * d, mc, 0, nullptr, 0, 0.0, B, nup, mcp, ldb));
+  for (const ChunkRange::Step c : cr) {
+    const int64_t mc = c.mc, mcp = c.mcp, ldb = gpx_skew_ld(mcp);
+    GPX_TRY(launch_kfill(ctx, kpz, ds->S->p, nu, Z->p + c.j0 * d, mc, 0, nullptr, 0, 0.0, B, nup, mcp, ldb));
     GPX_TRY(launch_gemm(ctx, B, ldb, B, ldb, ds->Gz->p, ldn, nup, nup, mcp, true, true, true));
   }
   GPX_TRY(launch_sym(ctx, nullptr, 0, ds->Gz->p, ldn, -(double)M, nup, ds->Gz->p, ldn));

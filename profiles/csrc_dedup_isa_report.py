@@ -37,7 +37,7 @@ w("    python profiles/csrc_dedup_isa_report.py PARENT_OUT CHANGE_OUT   (runs pr
 w("For every function that differs: instruction counts (parent, change), whether the opcode sequence and the sequence of floating-point")
 w("opcodes are the same, and VGPRs / SGPRs / scratch / spills of both builds.")
 w("")
-for f in ['kfill','gemm_f64','chol','reduce','dist','fitc','loo','api','design','hyper','grad','acq']:
+for f in ['kfill','gemm_f64','chol','reduce','dist','fitc','loo','api','design','hyper','grad','acq','sample','paths','vfe_design']:
     w("== %s.hip" % f)
     out = subprocess.run([sys.executable, os.path.join(HERE, 'strassen2_isa_compare.py'), P+f+'.s', Cg+f+'.s'], capture_output=True, text=True).stdout
     a, b = functions(P+f+'.s'), functions(Cg+f+'.s')

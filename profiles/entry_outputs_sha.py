@@ -4,6 +4,8 @@ seeds) -- the comparison behind profiles/csrc_dedup_ab.txt and profiles/err_ladd
 
     python profiles/entry_outputs_sha.py > A.txt                                   one line per entry, in a fresh process
     GPX_LIB_PATH=/path/to/another/libgpx_hip.so python profiles/entry_outputs_sha.py > B.txt
+    GPX_CROSS_BYTES=1 python profiles/entry_outputs_sha.py --skip ivar_keep+ivar_update > A1.txt     chunks of 128 (the kept solve
+                                                                                   exists for one chunk only)
     python profiles/entry_outputs_sha.py A.txt B.txt                               side by side, EQUAL / DIFFERENT per entry
 
 What an entry returns is hashed as it comes: arrays and scalars as float64 / int64 bytes, a device matrix as its logical
@@ -37,7 +39,7 @@ def feed(h, obj):
 
 
 def main():
-    if len(sys.argv) == 3:
+    if len(sys.argv) == 3 and "--skip" not in sys.argv:
         a, b = (dict(l.split() for l in open(p) if l.strip()) for p in sys.argv[1:])
         for name in a:
             print("%-28s %-10s parent %s  change %s" % (name, "EQUAL" if a[name] == b.get(name) else "DIFFERENT", a[name], b.get(name)))
@@ -45,7 +47,10 @@ def main():
         return 0 if all(a[n] == b.get(n) for n in a) and len(a) == len(b) else 1
     sys.path.append(os.path.join(ROOT, "tests"))
     import test_gpu_scratch_balance as t
+    skip = sys.argv[sys.argv.index("--skip") + 1].split(",") if "--skip" in sys.argv else []
     for name, make, n in t.ENTRIES:
+        if name in skip:
+            continue
         ctx, call = make(n)
         out = call()
         h = hashlib.sha256()

@@ -203,8 +203,12 @@ def check_within(got, ref, bound, label="", margin=MARGIN):
 
 
 def first_argbest(rows, minimize=True):
-    rows = np.asarray(rows)
-    return np.argmin(rows, axis=1) if minimize else np.argmax(rows, axis=1)
+    """Per row the FIRST index of the minimum (maximum) among the entries that are not NaN -- np.argmin / np.argmax on a row without
+    NaN; a NaN never wins, and a row of nothing but NaN gives index 0 (np.argmin's answer there)."""
+    rows = np.asarray(rows, dtype=float)
+    nan = np.isnan(rows)
+    key = np.where(nan, np.inf, rows if minimize else -rows)
+    return np.argmax(~nan & (key == key.min(axis=1)[:, None]), axis=1)
 
 
 def mutant_argbest_last(rows, minimize=True):

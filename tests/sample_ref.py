@@ -168,8 +168,23 @@ def check_draw(out, mean, F, xi, label=""):
 
 
 def first_argbest(rows, minimize=True):
+    """Per row the FIRST index of the minimum (maximum) among the entries that are not NaN -- np.argmin / np.argmax on a row without
+    NaN; a NaN never wins, and a row of nothing but NaN gives index 0 (np.argmin's answer there)."""
     rows = np.asarray(rows, dtype=float)
-    return (np.argmin(rows, axis=1) if minimize else np.argmax(rows, axis=1)).astype(np.int64)
+    nan = np.isnan(rows)
+    key = np.where(nan, np.inf, rows if minimize else -rows)
+    return np.argmax(~nan & (key == key.min(axis=1)[:, None]), axis=1).astype(np.int64)
+
+
+def check_argbest_bits(idx, val, rows, minimize=True, label=""):
+    """check_argbest for rows that may hold NaN: the indices exactly; the values bit for bit where finite, NaN where NaN."""
+    idx, val, rows = np.asarray(idx), np.asarray(val, dtype=float), np.asarray(rows, dtype=float)
+    want = first_argbest(rows, minimize)
+    assert idx.dtype == np.int64 and np.array_equal(idx, want), "%s: arg-best %r, first arg-best of the rows %r" % (label, idx, want)
+    wv = rows[np.arange(rows.shape[0]), want]
+    assert np.array_equal(np.isnan(val), np.isnan(wv)), "%s: NaN values %r against %r" % (label, val, wv)
+    ok = ~np.isnan(wv)
+    assert np.array_equal(val[ok].view(np.int64), wv[ok].view(np.int64)), "%s: values %r against %r" % (label, val, wv)
 
 
 def check_argbest(idx, val, rows, minimize=True, label=""):

@@ -267,6 +267,53 @@ def test_argbest_across_chunks_and_ties():
     assert eval(small)[0] == [0, 0] and eval(small)[1] == [0, 0]
 
 
+ARGBEST_M = (1, 255, 256, 257)    # below, at and above the 256 threads a row is dealt to; 257: three chunks under the small budget
+
+
+@pytest.mark.parametrize("budget", [None, "1"], ids=["one-chunk", "chunks-of-128"])
+@pytest.mark.parametrize("m", ARGBEST_M)
+def test_argbest_of_rows_with_ties_zeros_and_nan(dev, ctx, m, budget, monkeypatch):
+    """The row arg-best and its merge across chunks on rows made to order: prior paths on three features -- a constant, cos(z_0), and
+    cos(1e308 z_1), which is cos(inf) = NaN where z_1 = 10 and 1 where z_1 = 0.  The candidates at 127, 128 and m - 1 repeat candidate
+    1 bit for bit, where cos(z_0) = 1: the winner of the maximum of path 1 and of the minimum of path 2, tied across the chunk
+    boundaries.  Path 0 is constant (every candidate ties), path 3 is exactly 0 (weights 0), path 4 is NaN everywhere (a NaN weight).
+    Evaluated twice: without NaN candidates, and with NaN at candidate 0 and at 130 (the start of the first and inside the second
+    chunk).  Checked on the rows the device itself returns: the first arg-best among the entries that are not NaN, the value there bit
+    for bit, index 0 and NaN for a row of NaNs.  (A -0 cannot come out of the evaluation, whose sums start from +0: the tie of +0
+    with -0 reaches the reduction as a tie of +0 with +0, path 3.)"""
+    if budget:
+        monkeypatch.setenv("GPX_CROSS_BYTES", budget)
+    sp = SR.device_spec(dev, dict(SR.kernel_spec("se", 2), signalSize=1.0))
+    omega, phase = np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1e308]]), np.zeros(3)
+    w = np.array([[1.0, 0.0, 0.0], [0.5, 1.0, 0.0], [0.5, -1.0, 0.0], [0.0, -0.0, 0.0], [np.nan, 0.0, 0.0]])
+    Z = np.zeros((m, 2))
+    Z[:, 0] = np.random.default_rng(m).uniform(0.5, 3.0, m)
+    Z[[j for j in (1, 127, 128, m - 1) if j < m], 0] = 0.0
+    Znan = Z.copy()
+    Znan[[j for j in (0, 130) if j < m], 1] = 10.0
+    smp = dev.PathSampler(ctx, sp, None, None, None, omega, phase, w, None)
+    try:
+        for pts, with_nan in ((Z, False), (Znan, True)):
+            for minimize in (True, False):
+                idx, val, rows = smp.argbest(dev.points(ctx, pts), minimize=minimize, want_values=True)
+                assert np.all(rows[0] == rows[0, -1]) or with_nan
+                assert np.all(np.isnan(rows[4])) and np.array_equal(np.isnan(rows[0]), pts[:, 1] != 0.0)
+                assert np.all(rows[3][pts[:, 1] == 0.0] == 0.0)
+                if m > 128 and not with_nan:
+                    assert rows[1, 1] == rows[1, 127] == rows[1, 128] == rows[1, m - 1] == rows[1].max()
+                    assert rows[2, 1] == rows[2, 127] == rows[2, 128] == rows[2, m - 1] == rows[2].min()
+                SR.check_argbest_bits(idx, val, rows, minimize, "m = %d, %s" % (m, "min" if minimize else "max"))
+                assert idx[4] == 0 and np.isnan(val[4])
+                if m > 1:
+                    assert idx[0] == idx[3] == (1 if with_nan else 0)
+                    if not with_nan:
+                        assert idx[2 if minimize else 1] == 1
+                idx2, val2 = smp.argbest(dev.points(ctx, pts), minimize=minimize)
+                assert np.array_equal(idx2, idx) and np.array_equal(val2, val, equal_nan=True)
+    finally:
+        smp.close()
+
+
 # ---- the class API ---------------------------------------------------------------------------------------------------------------------------
 class _Space(object):
     def __init__(self, d):

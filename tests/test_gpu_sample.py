@@ -155,6 +155,46 @@ def test_prior_of_far_apart_points_is_the_identity(dev, ctx, kind, m):
         smp.close()
 
 
+ARGBEST_M = (1, 255, 256, 257)    # below, at and above the 256 threads a row is dealt to
+
+
+def argbest_base_samples(m):
+    """Base samples whose rows -- on the identity factor -- hold: nothing special; one value everywhere; the best value twice, at the
+    two ends of the thread stride (m - 2, m - 1) and at 0 when m allows; exact zeros of both signs; a NaN in the last place; NaN only."""
+    xi = np.random.default_rng(m).standard_normal((7, m))
+    xi[1] = 1.5
+    xi[2, [0, max(m - 2, 0), m - 1]] = -9.0
+    xi[3, [max(m - 2, 0), m - 1]] = 9.0
+    xi[4] = np.where(np.arange(m) % 2 == 0, 0.0, -0.0)
+    xi[5, m - 1] = np.nan
+    xi[6] = np.nan
+    return xi
+
+
+@pytest.mark.parametrize("m", ARGBEST_M)
+def test_argbest_of_rows_with_ties_zeros_and_nan(dev, ctx, m):
+    """The row arg-best on rows made to order: the prior of far-apart points with signalSize 1 and no nugget has K = I, so a sample
+    is its base sample times the diagonal of F.  Checked on the rows the device itself returns: the first arg-best among the entries
+    that are not NaN, the value there bit for bit, index 0 and NaN for a row of NaNs.  (A -0 cannot come out of the sampler --
+    mean + F xi adds to +0 -- so the tie of +0 with -0 is fed in but reaches the reduction as a tie of +0 with +0.)"""
+    spec = dict(SR.kernel_spec("se", 2), signalSize=1.0)
+    Z = 1e4 * np.arange(1.0, m + 1.0)[:, None] * np.array([[1.0, -1.0]])
+    smp = dev.PosteriorSampler(ctx, SR.device_spec(dev, spec), None, None, None, dev.points(ctx, Z), 0.0)
+    try:
+        xi = argbest_base_samples(m)
+        for minimize in (True, False):
+            idx, val, rows = smp.argbest(xi, minimize=minimize, want_samples=True)
+            assert np.all(rows[1] == rows[1, 0]) and np.all(rows[4] == 0.0) and np.all(np.isnan(rows[6]))
+            assert rows[2, m - 1] == rows[2, 0] == rows[2].min() and rows[3, m - 1] == rows[3, max(m - 2, 0)] == rows[3].max()
+            assert np.isnan(rows[5, m - 1]) and (m < 257 or not np.any(np.isnan(rows[5, :256])))
+            SR.check_argbest_bits(idx, val, rows, minimize, "m = %d, %s" % (m, "min" if minimize else "max"))
+            assert idx[6] == 0 and np.isnan(val[6]) and idx[1] == 0 and idx[4] == 0
+            idx2, val2 = smp.argbest(xi, minimize=minimize)
+            assert np.array_equal(idx2, idx) and np.array_equal(val2, val, equal_nan=True)
+    finally:
+        smp.close()
+
+
 # ---- 6: nugget 0 on repeated points, and the pivot policy --------------------------------------------------------------------------
 @pytest.mark.parametrize("case", SR.SAMPLER_CASES[:4], ids=SR.case_id)
 @pytest.mark.parametrize("drop_before", [False, True])

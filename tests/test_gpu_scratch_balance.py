@@ -9,6 +9,8 @@ Shapes (d = 3): the smallest that reach each allocation branch --
     N = 300,  M = 260   in-place solve, ragged against the 128-tile, three arg-min partials of 128 candidates
     N = 2100            the out-of-place solve of gpx_posterior / gpx_acq / gpx_acq_batch's set-up (padded order >= 2048)
     N = 4100, M = 260   the block-inverse scratch of gpx_acq_grad's backward solve (padded order >= 4096)
+    257 / 2049 inducing points (at N = 300 / 2100)   the in-place and the out-of-place set-up of the sparse predictors
+The entries whose passes are chunked (CHUNKED) run a second time with GPX_CROSS_BYTES=1: chunks of 128, 128 and 4 points.
 The factor's explicit block inverses are a cache inside the factor, built by the first solve against it: the model fixture's
 gpx_potrs builds them, so that the entries under test start from the steady state.
 
@@ -192,6 +194,107 @@ def _fitc(n):
     return ctx, call
 
 
+def _var_grad(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    return ctx, lambda: dev.var_grad(ctx, spec, L, X, Z)
+
+
+def _posterior_cov(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    return ctx, lambda: dev.posterior_cov(ctx, spec, L, X, Z)
+
+
+def _greedy_ivar_step(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    Zmc = dev.points(ctx, np.random.RandomState(7).uniform(-1.0, 1.0, (150, D)))
+    return ctx, lambda: dev.greedy_ivar_step(ctx, spec, L, X, Z, Zmc, NOISE)
+
+
+def _psampler(n, prior=False):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    xi = np.random.RandomState(11).standard_normal((5, M))
+
+    def call():
+        ps = dev.PosteriorSampler(ctx, spec, *((None, None, None) if prior else (L, X, alpha)), Z, 1e-6)
+        out = (ps.draw(xi),) + ps.argbest(xi) + ps.argbest(xi, minimize=False)
+        ps.close()
+        return out
+    return ctx, call
+
+
+def _psampler_prior(n):
+    return _psampler(n, prior=True)
+
+
+def _acq_qei(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    rng = np.random.RandomState(13)
+    Zb, xi = dev.points(ctx, rng.uniform(-1.0, 1.0, (5 * 3, D))), rng.standard_normal((8, 3))
+    return ctx, lambda: dev.acq_qei(ctx, spec, L, X, alpha, Zb, 3, xi, float(y.min()), 1e-8)
+
+
+def _paths(n):
+    from gpexp_amd import device as dev
+    ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+    rng = np.random.RandomState(17)
+    omega, phase = rng.standard_normal((40, D)) / np.array([0.5, 0.7, 0.6]), rng.uniform(0.0, 2.0 * np.pi, 40)
+    w, eps = rng.standard_normal((3, 40)), np.sqrt(NOISE) * rng.standard_normal((3, n))
+    Zp = dev.points(ctx, rng.uniform(-1.0, 1.0, (4, D)))
+
+    def call():
+        ps = dev.PathSampler(ctx, spec, L, X, alpha, omega, phase, w, eps)
+        out = ps.argbest(Z, want_values=True) + ps.argbest(Z, minimize=False) + ps.gradient(Zp, [0, 2, 1, 0], want_values=True)
+        ps.close()
+        return out
+    return ctx, call
+
+
+_sparse = {}
+
+
+def sparse_model(n, nu, vfe):
+    """(model, coeff) on the first nu training points as inducing points; built once per shape and left unchanged."""
+    from gpexp_amd import device as dev
+    if (n, nu, vfe) not in _sparse:
+        ctx, spec, X, L, y, alpha, Z, Xh = model(n)
+        f = (dev.VfeModel if vfe else dev.FitcModel)(ctx, spec, X, dev.points(ctx, Xh[:nu]), NOISE)
+        _sparse[(n, nu, vfe)] = (f, f.solve(y)[0])
+    return _sparse[(n, nu, vfe)]
+
+
+def _fitc_posterior(n):
+    ctx, (f, coeff), Z = model(n)[0], sparse_model(n, 257, False), model(n)[6]
+    return ctx, lambda: f.posterior(coeff, Z)
+
+
+def _vfe(what, nu):
+    def make(n):
+        from gpexp_amd import device as dev
+        ctx, (f, coeff), y, Z = model(n)[0], sparse_model(n, nu, True), model(n)[4], model(n)[6]
+        return ctx, {
+            "posterior": lambda: f.posterior(coeff, Z),
+            "acq": lambda: f.acq(coeff, Z, dev.ACQ_EI, float(y.max())),
+            "acq_grad": lambda: f.acq_grad(coeff, Z, dev.ACQ_EI, float(y.max())),
+            "acq_batch": lambda: f.acq_batch(coeff, Z, dev.ACQ_EI, float(y.max()), True, dev.LIE_BELIEVER, 0.0, 3, want_all=True),
+        }[what]
+    return make
+
+
+VFE_CALLS = ("posterior", "acq", "acq_grad", "acq_batch")
+# the entries whose passes are chunked under GPX_CROSS_BYTES: run at the default budget (with ENTRIES) and at a budget of one
+# byte, where every rule clamps to chunks of 128 -- M = 260 in three chunks, the last of 4 points
+CHUNKED = [
+    ("posterior_cov", _posterior_cov, 300), ("greedy_ivar_step", _greedy_ivar_step, 300),
+    ("psampler", _psampler, 300), ("psampler_prior", _psampler_prior, 300),
+    ("acq_qei", _acq_qei, 300), ("acq_qei", _acq_qei, 2100),
+    ("paths", _paths, 300), ("fitc_posterior", _fitc_posterior, 300), ("var_grad", _var_grad, 300),
+] + [("vfe_%s" % c, _vfe(c, 257), 300) for c in VFE_CALLS] + [("vfe_%s_nu2049" % c, _vfe(c, 2049), 2100) for c in VFE_CALLS]
+
 ENTRIES = [
     ("posterior", _posterior, 300), ("posterior", _posterior, 2100),
     ("ivar", _ivar, 300), ("ivar_keep+ivar_update", _ivar_keep_update, 300),
@@ -204,12 +307,19 @@ ENTRIES = [
     ("dbg_greedy_var_scores", _dbg_greedy_var_scores, 300),
     ("loo", _loo, 300), ("loo_grad", _loo_grad, 300),
     ("fitc_fit+fitc_solve", _fitc, 300),
-]
+] + CHUNKED
 
 
 @pytest.mark.parametrize("name,make,n", ENTRIES, ids=["%s-N%d" % (e[0], e[2]) for e in ENTRIES])
 def test_outstanding_bytes_return_to_their_value(name, make, n):
     ctx, call = make(n)
+    balanced(ctx, call)
+
+
+@pytest.mark.parametrize("name,make,n", CHUNKED, ids=["%s-N%d" % (e[0], e[2]) for e in CHUNKED])
+def test_outstanding_bytes_return_in_chunks_of_128(name, make, n, monkeypatch):
+    ctx, call = make(n)
+    monkeypatch.setenv("GPX_CROSS_BYTES", "1")
     balanced(ctx, call)
 
 
