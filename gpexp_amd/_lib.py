@@ -218,6 +218,8 @@ _SIGS = {
     "gpx_dbg_event_elapsed": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp]),
     "gpx_dbg_leaf_stamps": (C.c_int, [c_vp, c_vp, C.c_int, C.POINTER(c_i64)]),
     "gpx_dbg_greedy_var_scores": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_ip, c_i64, c_dp]),
+    "gpx_dbg_acq_epilogue": (C.c_int, [c_vp, C.c_int, C.c_double, c_dp, c_dp, c_i64, c_i64, c_dp, c_dp, C.POINTER(c_i64),
+                                       c_dp]),
 }
 
 _lib = None

@@ -639,3 +639,69 @@ int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, co
 }
 
 }  // extern "C"
+
+// test hook (gpx_debug.h): AcqOut's epilogue chunk by chunk and its arg-min on host vectors of means and SIGNED variances (ssq ==
+// NULL, the VFE predictor's form).  Every device buffer the two kernels write carries DBG_BAND words of a sentinel behind its last
+// entry; a launch that writes there fails the call.
+namespace {
+
+constexpr int64_t DBG_BAND = 32;
+constexpr int64_t DBG_SENTINEL = 0x5A5AA5A5C3C33C3CLL;   // (as a double: 2.6e127, no value an epilogue makes)
+
+template <typename T>
+int dbg_banded(gpx_ctx* ctx, Scratch& sc, int64_t count, T** p) {
+  static_assert(sizeof(T) == 8, "eight-byte words");
+  std::vector<int64_t> h((size_t)(count + DBG_BAND), DBG_SENTINEL);
+  GPX_TRY(sc.get((count + DBG_BAND) * 8, p));
+  GPX_HIP(hipMemcpyAsync(*p, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));   // (h goes out of scope)
+  return 0;
+}
+
+int dbg_band_intact(gpx_ctx* ctx, const void* p, int64_t count) {
+  int64_t h[DBG_BAND];
+  GPX_HIP(hipMemcpyAsync(h, (const int64_t*)p + count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  for (int64_t i = 0; i < DBG_BAND; ++i)
+    GPX_ARG(h[i] == DBG_SENTINEL, "the acquisition epilogue or its arg-min wrote behind the last entry of a result");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* var, int64_t m,
+                                    int64_t chunk, double* cost, double* coef, int64_t* best, double* best_cost) {
+  GPX_ARG(ctx && mean && var && cost && best && best_cost, "NULL argument");
+  GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
+  GPX_ARG(m >= 1, "need at least one candidate");
+  GPX_ARG(chunk >= 0 && chunk % ACQ_EPI == 0, "chunk must be 0 (one launch) or a multiple of 128");
+  const int64_t step = chunk > 0 && chunk < m ? chunk : m;
+  double *dmean = nullptr, *dvar = nullptr;
+  AcqOut out;
+  Scratch sc(ctx);
+  out.M = m;
+  out.nparts = (m + ACQ_EPI - 1) / ACQ_EPI;
+  GPX_TRY(sc.get(m * 8, &dmean));
+  GPX_TRY(sc.get(m * 8, &dvar));
+  GPX_TRY(dbg_banded(ctx, sc, m, &out.cost));
+  GPX_TRY(dbg_banded(ctx, sc, out.nparts, &out.part_c));
+  GPX_TRY(dbg_banded(ctx, sc, out.nparts, &out.part_i));
+  GPX_TRY(dbg_banded(ctx, sc, 1, &out.best_c));
+  GPX_TRY(dbg_banded(ctx, sc, 1, &out.best_i));
+  if (coef) GPX_TRY(dbg_banded(ctx, sc, 2 * step, &out.coef));
+  GPX_HIP(hipMemcpyAsync(dmean, mean, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(dvar, var, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+  for (int64_t j0 = 0; j0 < m; j0 += step) {
+    const int64_t mc = m - j0 < step ? m - j0 : step;
+    GPX_TRY(out.epilogue(ctx, acq, param, dmean + j0, dvar + j0, nullptr, mc, j0, 8.0 * 4.0 * (double)mc));
+    if (coef) GPX_HIP(hipMemcpyAsync(coef + 2 * j0, out.coef, (size_t)(2 * mc) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GPX_TRY(out.finish(ctx, cost, best, best_cost, nullptr));
+  GPX_TRY(dbg_band_intact(ctx, out.cost, m));
+  GPX_TRY(dbg_band_intact(ctx, out.part_c, out.nparts));
+  GPX_TRY(dbg_band_intact(ctx, out.part_i, out.nparts));
+  GPX_TRY(dbg_band_intact(ctx, out.best_c, 1));
+  GPX_TRY(dbg_band_intact(ctx, out.best_i, 1));
+  if (coef) GPX_TRY(dbg_band_intact(ctx, out.coef, 2 * step));
+  return 0;
+}

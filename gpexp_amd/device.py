@@ -676,6 +676,21 @@ def acq(ctx, spec, L, X, alpha, Z, kind, param, want_costs=True):
     return best.value, best_cost.value, costs
 
 
+def dbg_acq_epilogue(ctx, kind, param, mean, var, chunk=0, want_coef=True):
+    """The cost epilogue and the arg-min of gpx_acq alone on host vectors of means and SIGNED variances (test hook,
+    gpx_dbg_acq_epilogue), `chunk` candidates per launch (a multiple of 128; 0: one launch): (first arg-min among the non-NaN costs
+    or -1, its cost, costs (m,), (a, b) = (dA/dmu, dA/dvar) as (m, 2) or None)."""
+    mean, var = as_f64(np.ravel(mean)), as_f64(np.ravel(var))
+    assert mean.shape == var.shape
+    m = mean.size
+    costs = np.empty(m)
+    coef = np.empty((m, 2)) if want_coef else None
+    best, best_cost = c_i64(), C.c_double()
+    check(ctx.lib.gpx_dbg_acq_epilogue(ctx.h, int(kind), float(param), dptr(mean), dptr(var), m, int(chunk), dptr(costs),
+                                       dptr(coef), C.byref(best), C.byref(best_cost)))
+    return best.value, best_cost.value, costs, coef
+
+
 def acq_grad(ctx, spec, L, X, alpha, Z, kind, param):
     """(costs (M,), d cost_m / d z_m (M, d)) of the M candidates Z (gpx_acq_grad)."""
     m, d = Z.shape

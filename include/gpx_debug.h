@@ -97,6 +97,14 @@ int gpx_dbg_greedy_var_scores(gpx_ctx* ctx, int kind, int d, const double* hyp, 
 int gpx_dbg_qei_blocks(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                        const double* alpha, const gpx_mat* Zb, int64_t q, double nugget, double* mean, double* Cb, double* Fb);
 
+/* The cost epilogue of gpx_acq / gpx_vfe_acq and its arg-min alone, by their own launches, on host vectors: mean[m] and the SIGNED
+   variances var[m] (any doubles: negative, zero, infinite, NaN).  The epilogue runs in chunks of `chunk` candidates (a multiple of
+   128; 0: one launch), then the arg-min over all partials.  cost (host m), coef (host 2m, nullable: (a, b) = (dA/dmu, dA/dvar) per
+   candidate), best / best_cost: the first minimum among the non-NaN costs, (-1, NaN) when there is none.  Every device result
+   carries a sentinel band behind its last entry: a launch that writes there fails the call.  tests/test_gpu_acq_bounds.py. */
+int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* var, int64_t m, int64_t chunk,
+                         double* cost, double* coef /* 2m, nullable */, int64_t* best, double* best_cost);
+
 #ifdef __cplusplus
 }
 #endif
