@@ -78,6 +78,10 @@
 // That per-chunk step is vfe_posterior_chunk, shared with the acquisition costs on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad: their
 // bodies and gpx_vfe_acq_batch's are in acq.hip beside the kernels they share with the dense calls; the entries and their argument
 // checks are here, where the struct is).
+// Sampling from that predictor's distribution is offered the same way: gpx_vfe_paths_create (decoupled paths, V = 1 beta_u^T -
+// (F~_S + eps_u) Quu^-1 + Xi2 La^-1; body in paths.hip), gpx_vfe_posterior_cov (K(Z,Z) - Wu^T Wu + Wa^T Wa, the predictor's variance
+// on its diagonal) and gpx_vfe_psampler_create (the exact joint sampler on it; bodies in sample.hip) have their entries and argument
+// checks here -- a VFE model, its own S, for the paths a stationary kernel -- and reach the model through fitc_view and vfe_beta_u.
 #include "gpx_device.h"
 #include <math.h>
 #include <stdlib.h>
@@ -1333,6 +1337,39 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
   GPX_ARG(q <= C->rows, "more picks than candidates");
   return vfe_acq_batch_impl(ctx, f, S, coeff, C, acq, param, track_best != 0, lie, lie_value, q, out_idx, out_cost, out_lie,
                             all_costs);
+}
+
+// Posterior sampling on a VFE model (bodies: paths.hip and sample.hip, beside the code they share with the dense samplers; the
+// argument checks are here, where the struct is)
+int gpx_vfe_paths_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,
+                         const double* phase, int64_t nfeat, const double* w, const double* eps_u, const double* xi_q,
+                         int64_t nPaths, gpx_paths** out) {
+  GPX_ARG(ctx && f && S && coeff && omega && phase && w && out, "NULL argument");
+  FITC_KIND(f, true, "vfe_paths_create", "pathwise sampling is offered on dense models (gpx_paths_create) and VFE models only");
+  FITC_ARG(f->kp.kind == GPX_K_SE || f->kp.kind == GPX_K_MATERN32 || f->kp.kind == GPX_K_MATERN52, "vfe_paths_create",
+           "paths: stationary kernels only (squared exponential, Matern 3/2, Matern 5/2)");
+  GPX_TRY(vfe_point_sets(f, S, S));
+  GPX_ARG(nfeat >= 1, "paths: needs at least one feature");
+  GPX_ARG(nPaths >= 1, "paths: needs at least one path");
+  return vfe_paths_create_impl(ctx, f, S, coeff, omega, phase, nfeat, w, eps_u, xi_q, nPaths, out);
+}
+
+int gpx_vfe_posterior_cov(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov) {
+  GPX_ARG(ctx && f && S && Z && cov, "NULL argument");
+  FITC_KIND(f, true, "vfe_posterior_cov", "a FITC model's covariance comes from gpx_fitc_dense's precision");
+  GPX_TRY(vfe_point_sets(f, S, Z));
+  if (Z->rows == 0) return 0;
+  return vfe_posterior_cov_impl(ctx, f, S, Z, cov);
+}
+
+int gpx_vfe_psampler_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
+                            gpx_psampler** out) {
+  GPX_ARG(ctx && f && S && coeff && Z && out, "NULL argument");
+  FITC_KIND(f, true, "vfe_psampler_create", "joint sampling is offered on dense models (gpx_psampler_create) and VFE models only");
+  GPX_TRY(vfe_point_sets(f, S, Z));
+  GPX_ARG(nugget >= 0.0, "psampler: the nugget must not be negative");
+  GPX_ARG(Z->rows >= 1, "psampler: needs at least one point");
+  return vfe_psampler_create_impl(ctx, f, S, coeff, Z, nugget, out);
 }
 
 // Point-wise derivatives of the variational variance (bodies: vfe_design.hip; the argument checks are here, where the struct is)

@@ -513,6 +513,14 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
                        double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
                        double* out_lie, double* all_costs);
+// paths.hip / sample.hip: the bodies of gpx_vfe_paths_create, gpx_vfe_posterior_cov and gpx_vfe_psampler_create, behind fitc.hip's
+// argument checks (a VFE model, its own S, unpadded Z of at least one row, a stationary kernel for the paths)
+int vfe_paths_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,
+                          const double* phase, int64_t nfeat, const double* w, const double* eps_u, const double* xi_q, int64_t nPaths,
+                          gpx_paths** out);
+int vfe_posterior_cov_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov);
+int vfe_psampler_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
+                             gpx_psampler** out);
 // acq.hip: out_c[0], out_i[0] (device) = the first minimum among the nparts arg-min partials {cost, index} with index >= 0
 // (argmin_merge; index -1 and a NaN cost when there is none) -- gpx_acq's final reduction, for sample.hip's q-EI partials
 int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i, int64_t nparts, double* out_c, int64_t* out_i);

@@ -30,6 +30,18 @@
 // paths_grad_kernel: one workgroup per point, thread t takes r = t, t + 256, ... in ascending order, block_sum_256 adds the 256
 // partial sums in a fixed tree.  The kernel derivative is radial_pair's factor times the coordinate difference: nothing divides
 // by the distance, and at z = x_i the term is exactly 0.
+//
+// VFE models (gpx_vfe_paths_create; the entry and its argument checks are in fitc.hip, where the struct is).  Nothing in the two
+// kernels knows that the point block holds TRAINING points: a path of the variational posterior is the same resident object with the
+// nu inducing points S in the point block and other weights (decoupled sampling, Wilson et al. 2020, section 4.2).  With Quu = K(S,S)
+// + noise I = Lu Lu^T (the inducing variables are u = f(S) + eps), A = Quu + Kuf Kfu / noise = La La^T and beta_u = Quu^-1 Kuf alpha,
+// Matheron's rule on (f, u) with u ~ q(u) = N(Quu beta_u, Quu A^-1 Quu) gives
+//     V = 1 beta_u^T - (F~_S + eps_u) Quu^-1 + Xi2 La^-1                   (S_paths x nu;  F~_S[s][u] = f~_s(s_u), eps_u = sqrt(noise) Xi1)
+// -- zero draws: the predictor's mean; exact prior in place of the features: covariance k - k_u^T Quu^-1 k_u' + k_u^T A^-1 k_u', the
+// predictor's.  The build is on the device for all paths at once: f~ at S by launch_paths_eval over the feature rows, eps_u added,
+// both sweeps against Lu and the one against La as blocked RIGHT solves on the (S_paths padded to 128) x nup matrices
+// (chol_trsm_right, chol_trsm_right_n: O(nu^2) per path, nothing of size N), and vfe_paths_setv_kernel writes V into Ct.  No atomics;
+// a path's weights depend on its own row of the draws alone.
 #include "gpx_device.h"
 #include <math.h>
 #include <vector>
@@ -230,7 +242,92 @@ int launch_paths_eval(gpx_ctx* ctx, const gpx_paths* ps, int64_t R, const double
 
 const char* const kPointsMsg = "point sets must be unpadded (n x d)";
 
+// What the two constructors share: G and Ct of a new object (its shape fields set), all 0, with the feature block uploaded -- G
+// rows [0, Lp) = (omega_j, b_j), Ct rows [0, Lp) = c = sqrt(2 sig / L) w.  hG, hC: the caller's (empty) host images, which must
+// outlive the queued copies.
+int paths_begin(gpx_ctx* ctx, gpx_paths* ps, const double* omega, const double* phase, const double* w, std::vector<double>& hG,
+                std::vector<double>& hC) {
+  const int d = ps->kp.d;
+  const int64_t S = ps->S, Sp = ps->Sp, nfeat = ps->nfeat, Lp = ps->Lp, gs = d + 1, R = Lp + ps->Np;
+  hG.assign((size_t)(Lp * gs), 0.0);
+  hC.assign((size_t)(Lp * Sp), 0.0);
+  const double amp = sqrt(2.0 * ps->kp.sig / (double)nfeat);
+  for (int64_t j = 0; j < nfeat; ++j) {
+    for (int l = 0; l < d; ++l) hG[(size_t)(j * gs + l)] = omega[j * d + l];
+    hG[(size_t)(j * gs + d)] = phase[j];
+    for (int64_t s = 0; s < S; ++s) hC[(size_t)(j * Sp + s)] = amp * w[s * nfeat + j];
+  }
+  GPX_TRY(gpx_dev_alloc(ctx, R * gs * 8, &ps->G));
+  ps->G_bytes = R * gs * 8;
+  GPX_TRY(gpx_dev_alloc(ctx, R * Sp * 8, &ps->Ct));
+  ps->Ct_bytes = R * Sp * 8;
+  GPX_HIP(hipMemsetAsync(ps->G, 0, (size_t)ps->G_bytes, ctx->stream));
+  GPX_HIP(hipMemsetAsync(ps->Ct, 0, (size_t)ps->Ct_bytes, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(ps->G, hG.data(), hG.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_HIP(hipMemcpyAsync(ps->Ct, hC.data(), hC.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+// T (Sq x ld, Sq = S padded to 128) <- the S x n host draws, 0 elsewhere (a NULL host array: all 0)
+int paths_stage_rows(gpx_ctx* ctx, const double* host, int64_t S, int64_t n, double* T, int64_t Sq, int64_t ld) {
+  GPX_HIP(hipMemsetAsync(T, 0, (size_t)(Sq * ld * 8), ctx->stream));
+  if (host)
+    GPX_HIP(hipMemcpy2DAsync(T, (size_t)ld * 8, host, (size_t)n * 8, (size_t)n * 8, (size_t)S, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+// V = 1 bu^T - T + Q into the point block of Ct (T, Q: S rows of stride ld; bu: n)
+__global__ __launch_bounds__(256) void vfe_paths_setv_kernel(const double* __restrict__ T, const double* __restrict__ Q, int64_t ld,
+                                                             const double* __restrict__ bu, int64_t n, int64_t S,
+                                                             double* __restrict__ Ct, int64_t Sp, int64_t Lp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double b = bu[i];
+  for (int64_t s = blockIdx.y; s < S; s += gridDim.y) Ct[(Lp + i) * Sp + s] = (b - T[s * ld + i]) + Q[s * ld + i];
+}
+
 }  // namespace
+
+// (gpx_internal.h; the header comment has the formulas)
+int vfe_paths_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* Sm, const double* coeff, const double* omega,
+                          const double* phase, int64_t nfeat, const double* w, const double* eps_u, const double* xi_q, int64_t S,
+                          gpx_paths** out) {
+  FitcView v;
+  fitc_view(f, &v);
+  const KParams& kp = *v.kp;
+  const int d = kp.d;
+  const int64_t nu = v.nu, nup = v.nup, gs = d + 1;
+  const int64_t Sp = gpx_round_up(S, 16), Sq = gpx_round_up(S, GPX_TILE), Lp = gpx_round_up(nfeat, PT_R), Np = gpx_round_up(nu, PT_R);
+  const int64_t ld = gpx_skew_ld(nup);
+  std::vector<double> hG, hC;   // (declared first, as in gpx_paths_create)
+  Held<gpx_paths, gpx_paths_free> ps(ctx, new gpx_paths{S, Sp, nfeat, Lp, nu, Np, kp, nullptr, nullptr, 0, 0});
+  GPX_TRY(paths_begin(ctx, ps.get(), omega, phase, w, hG, hC));
+  GPX_HIP(hipMemcpy2DAsync(ps->G + Lp * gs, (size_t)gs * 8, Sm->p, (size_t)Sm->ld * 8, (size_t)d * 8, (size_t)nu,
+                           hipMemcpyDeviceToDevice, ctx->stream));
+  double *T, *Q, *F, *bu;
+  Scratch sc(ctx);
+  GPX_TRY(sc.get(Sq * ld * 8, &T));
+  GPX_TRY(sc.get(Sq * ld * 8, &Q));
+  GPX_TRY(sc.get(S * nu * 8, &F));
+  GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
+  GPX_TRY(paths_stage_rows(ctx, eps_u, S, nu, T, Sq, ld));
+  GPX_TRY(paths_stage_rows(ctx, xi_q, S, nu, Q, Sq, ld));
+  // T = f~(S) + eps_u: the prior paths at S by the evaluation kernel itself (generator rows [0, Lp) only), added to the staged draw
+  GPX_TRY(launch_paths_eval(ctx, ps.get(), Lp, Sm->p, nu, F, nu));
+  const dim3 grid((unsigned)((nu + 255) / 256), (unsigned)(S < 1024 ? S : 1024));
+  hipLaunchKernelGGL(paths_addeps_kernel, grid, dim3(256), 0, ctx->stream, T, ld, (const double*)F, nu, S);
+  GPX_HIP(hipGetLastError());
+  // T <- T Lu^-T Lu^-1 = T Quu^-1;  Q <- Xi2 La^-1 (row s: (La^-T xi2_s)^T).  The padding of both stays 0: the factors' is the identity.
+  GPX_TRY(chol_trsm_right(ctx, v.Lu->p, v.Lu->ld, v.Lu->aux, T, ld, Sq, nup));
+  GPX_TRY(chol_trsm_right_n(ctx, v.Lu->p, v.Lu->ld, v.Lu->aux, T, ld, Sq, nup));
+  GPX_TRY(chol_trsm_right_n(ctx, v.La->p, v.La->ld, v.La->aux, Q, ld, Sq, nup));
+  hipLaunchKernelGGL(vfe_paths_setv_kernel, grid, dim3(256), 0, ctx->stream, (const double*)T, (const double*)Q, ld,
+                     (const double*)bu, nu, S, ps->Ct, Sp, Lp);
+  GPX_HIP(hipGetLastError());
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ps.release();
+  return 0;
+}
 
 extern "C" {
 
@@ -266,24 +363,11 @@ int gpx_paths_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp,
   if (prior) GPX_TRY(gpx_make_kparams(kind, d, hyp, nhyp, &kp));
   else GPX_TRY(gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, nullptr, nullptr, kPointsMsg, &kp));
   const int64_t n = prior ? 0 : L->rows, gs = d + 1;
-  const int64_t Sp = gpx_round_up(S, 16), Lp = gpx_round_up(nfeat, PT_R), Np = gpx_round_up(n, PT_R), R = Lp + Np;
+  const int64_t Sp = gpx_round_up(S, 16), Lp = gpx_round_up(nfeat, PT_R), Np = gpx_round_up(n, PT_R);
   // host images of the feature block (declared first: the holder and the scratch below synchronise before these go)
-  std::vector<double> hG((size_t)(Lp * gs), 0.0), hC((size_t)(Lp * Sp), 0.0);
-  const double amp = sqrt(2.0 * kp.sig / (double)nfeat);
-  for (int64_t j = 0; j < nfeat; ++j) {
-    for (int l = 0; l < d; ++l) hG[(size_t)(j * gs + l)] = omega[j * d + l];
-    hG[(size_t)(j * gs + d)] = phase[j];
-    for (int64_t s = 0; s < S; ++s) hC[(size_t)(j * Sp + s)] = amp * w[s * nfeat + j];
-  }
+  std::vector<double> hG, hC;
   Held<gpx_paths, gpx_paths_free> ps(ctx, new gpx_paths{S, Sp, nfeat, Lp, n, Np, kp, nullptr, nullptr, 0, 0});
-  GPX_TRY(gpx_dev_alloc(ctx, R * gs * 8, &ps->G));
-  ps->G_bytes = R * gs * 8;
-  GPX_TRY(gpx_dev_alloc(ctx, R * Sp * 8, &ps->Ct));
-  ps->Ct_bytes = R * Sp * 8;
-  GPX_HIP(hipMemsetAsync(ps->G, 0, (size_t)ps->G_bytes, ctx->stream));
-  GPX_HIP(hipMemsetAsync(ps->Ct, 0, (size_t)ps->Ct_bytes, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(ps->G, hG.data(), hG.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  GPX_HIP(hipMemcpyAsync(ps->Ct, hC.data(), hC.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  GPX_TRY(paths_begin(ctx, ps.get(), omega, phase, w, hG, hC));
   if (!prior) {
     const int64_t np = L->prows;
     GPX_HIP(hipMemcpy2DAsync(ps->G + Lp * gs, (size_t)gs * 8, X->p, (size_t)X->ld * 8, (size_t)d * 8, (size_t)n,

@@ -22,6 +22,12 @@
 // nor on the other samples of the call.  psampler_epilogue_kernel adds the mean and turns Y (M x S) into sample-major rows;
 // launch_row_argbest (reduce.hip) reduces a row to its first minimum / maximum (the smaller index wins a tie).
 //
+// On a VFE model (gpx_vfe_psampler_create, gpx_vfe_posterior_cov: entries in fitc.hip, bodies here) the mean is taken by
+// vfe_posterior_chunk's sequence (gpx_vfe_posterior's bits) and C = (K(Z,Z) - Wu^T Wu) + Wa^T Wa, Wu = Lu^-1 K(S,Z), Wa = La^-1 K(S,Z),
+// by posterior_cov_into's steps once per factor under the cross-solve rule (vfe_posterior_cov_into); everything from the nugget on
+// is psampler_factor, the one tail both constructors call; here it also MEASURES the residual after the refinement step and repeats
+// the step while it is above half the factor contract (`verify`; the dense constructor keeps its one step and its bits).
+//
 // q-EI (gpx_acq_qei).  cost_b = -(1/S) sum_s max(0, fBest - min_j (mu_bj + (F_b xi_s)_j)), F_b = chol(C_b + nugget I).  The means
 // and W = L^-1 K(X, Zb) come from gpx_posterior_chunk, chunked over WHOLE batches; qei_kernel does the rest.  A workgroup owns a
 // span of G = 32 / q consecutive batches (G q <= 32 contiguous doubles per row of W: one 256-byte line at most) and
@@ -113,6 +119,145 @@ __global__ __launch_bounds__(256) void psampler_epilogue_kernel(const double* __
   const double mj = j0 + tx < m ? mean[j0 + tx] : 0.0;
   for (int r = ty; r < 32; r += 8)
     if (s0 + r < sc && j0 + tx < m) out[(s0 + r) * m + j0 + tx] = mj + tile[tx][r];
+}
+
+// rmax[i] = max_j |R[i][j]| / sqrt(C[i][i] C[j][j]) over j < m: one workgroup per row i < m (the backward error of a factor, entry by
+// entry in the measure the factor contract is stated in; a maximum, so no order matters)
+__global__ __launch_bounds__(256) void psampler_resid_kernel(const double* __restrict__ R, int64_t ldr, const double* __restrict__ C,
+                                                             int64_t ldc, int64_t m, double* __restrict__ rmax) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  const int64_t i = blockIdx.x;
+  const double cii = C[i * ldc + i];
+  double v = 0.0;
+  for (int64_t j = t; j < m; j += 256) {
+    const double q = fabs(R[i * ldr + j]) / sqrt(cii * C[j * ldc + j]);
+    v = q > v ? q : v;
+  }
+  red[t] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] = red[t + w] > red[t] ? red[t + w] : red[t];
+    __syncthreads();
+  }
+  if (t == 0) rmax[i] = red[0];
+}
+
+// One step of refinement from the residual R = Chat - F F^T in pR (consumed):  G = F^-1 R F^-T (the leaf inverses of the
+// factorisation serve both solves);  F += F Phi(G).  pY: mp x mp of scratch.
+int psampler_refine(gpx_ctx* ctx, gpx_mat* F, const double* invd, double* pR, double* pY, int64_t m, int64_t mp) {
+  const dim3 gridM((unsigned)mp, (unsigned)((mp + 255) / 256));
+  GPX_TRY(chol_trsm_left(ctx, F->p, F->ld, invd, pR, mp, mp, mp));
+  GPX_TRY(chol_trsm_right(ctx, F->p, F->ld, invd, pR, mp, mp, mp));
+  hipLaunchKernelGGL(psampler_phi_kernel, gridM, dim3(256), 0, ctx->stream, pR, mp, mp);
+  GPX_HIP(hipGetLastError());
+  GPX_TRY(launch_gemm_tri(ctx, F->p, F->ld, pR, mp, pY, mp, mp, mp, mp, false, false, false, 1));
+  hipLaunchKernelGGL(psampler_addlower_kernel, gridM, dim3(256), 0, ctx->stream, F->p, F->ld, (const double*)pY, mp, m);
+  GPX_HIP(hipGetLastError());
+  return 0;
+}
+
+constexpr int PSAMPLER_MAX_EXTRA = 4;   // refinement steps `verify` may add to the first
+
+// The tail of both constructors (gpx_psampler_create, gpx_vfe_psampler_create): ps->F holds the covariance C on entry (mp x mp, the
+// padding 0) and chol(C + nugget I), finished and refined, on return.  Runs under the caller's PolicyScope; a pivot <= 0 is returned
+// (> 0) with the message that names the point.  Synchronises the stream.
+// verify: after the refinement step the residual is MEASURED on the device, max_ij |Chat - F F^T|_ij / sqrt(Chat_ii Chat_jj), and while
+// it is above 4 (M + 1) u -- half the factor contract's 8 (M + 1) u -- the step is repeated, PSAMPLER_MAX_EXTRA times at most.  One step
+// is first order in G = F^-1 R F^-T, and on a covariance of low numerical rank whose other eigenvalues are the nugget (many points on a
+// line under a squared exponential: condition 1e11, several tiles) the explicit leaf inverses of chol_potrf leave an R for which G is
+// not small: the step then leaves a residual of the order |G|^2, which the next step takes as its R (the iteration is Newton's,
+// the later steps' solves use the first factor's leaf inverses: an inexact Newton step).  Costs one more mp^2 buffer and one product
+// per check.  The dense constructor passes false: its launches and its bits stay what they were.
+int psampler_factor(gpx_ctx* ctx, gpx_psampler* ps, Scratch& sc, double nugget, bool verify) {
+  const int64_t m = ps->m, mp = ps->mp;
+  gpx_mat* F = ps->F;
+  double* invd;
+  GPX_TRY(sc.get(mp * GPX_TILE * 8, &invd));
+  hipLaunchKernelGGL(psampler_nugget_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, F->p, F->ld, m, nugget);
+  GPX_HIP(hipGetLastError());
+  // Chat is kept for one step of refinement: chol_potrf's leaf multiplies by explicit inverses of its diagonal blocks, and on a
+  // covariance whose spectrum reaches down to the nugget that leaves |F F^T - Chat| an order above what a plain Cholesky leaves
+  double *pR, *pY, *pC = nullptr, *rmax = nullptr;
+  GPX_TRY(sc.get(mp * mp * 8, &pR));
+  GPX_TRY(sc.get(mp * mp * 8, &pY));
+  GPX_TRY(gpx_copy2d(ctx, F->p, F->ld, pR, mp, mp, mp));
+  if (verify) {
+    GPX_TRY(sc.get(mp * mp * 8, &pC));
+    GPX_TRY(sc.get(mp * 8, &rmax));
+    GPX_TRY(gpx_copy2d(ctx, F->p, F->ld, pC, mp, mp, mp));
+  }
+  GPX_TRY(chol_potrf(ctx, F->p, F->ld, mp, invd, m));
+  int info = 0;
+  GPX_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipDeviceSynchronize());   // (the blocked factorisation of a large C uses three streams)
+  if (info != 0) {
+    gpx_set_error("psampler: C + nugget I is not positive definite (pivot %d <= 0, nugget %g): the point repeats an earlier one "
+                  "or lies on a training point of a noise-free model; a larger nugget factors it", info, nugget);
+    return info;
+  }
+  hipLaunchKernelGGL(psampler_finish_kernel, dim3((unsigned)mp, (unsigned)((mp + 255) / 256)), dim3(256), 0, ctx->stream, F->p,
+                     F->ld, m, mp);
+  GPX_HIP(hipGetLastError());
+  // R = Chat - F F^T;  G = F^-1 R F^-T;  F += F Phi(G)
+  GPX_TRY(launch_gemm(ctx, F->p, F->ld, F->p, F->ld, pR, mp, mp, mp, mp, true, true, false));
+  GPX_TRY(psampler_refine(ctx, F, invd, pR, pY, m, mp));
+  if (verify) {
+    std::vector<double> h((size_t)m);
+    const double cap = 4.0 * (double)(m + 1) * 0x1p-53;
+    for (int extra = 0; extra < PSAMPLER_MAX_EXTRA; ++extra) {
+      GPX_TRY(gpx_copy2d(ctx, pC, mp, pR, mp, mp, mp));
+      GPX_TRY(launch_gemm(ctx, F->p, F->ld, F->p, F->ld, pR, mp, mp, mp, mp, true, true, false));
+      hipLaunchKernelGGL(psampler_resid_kernel, dim3((unsigned)m), dim3(256), 0, ctx->stream, (const double*)pR, mp,
+                         (const double*)pC, mp, m, rmax);
+      GPX_HIP(hipGetLastError());
+      GPX_HIP(hipMemcpyAsync(h.data(), rmax, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+      GPX_HIP(hipStreamSynchronize(ctx->stream));
+      double worst = 0.0;
+      for (int64_t i = 0; i < m; ++i) worst = h[(size_t)i] > worst ? h[(size_t)i] : worst;
+      if (worst <= cap) break;
+      GPX_TRY(psampler_refine(ctx, F, invd, pR, pY, m, mp));
+    }
+  }
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// C += D on the mp x mp storage (D: row stride mp)
+__global__ __launch_bounds__(256) void vfe_cov_add_kernel(double* __restrict__ C, int64_t ldc, const double* __restrict__ D,
+                                                          int64_t mp) {
+  const int64_t j = (int64_t)blockIdx.y * 256 + threadIdx.x, i = blockIdx.x;
+  if (j < mp) C[i * ldc + j] += D[i * mp + j];
+}
+
+// C (mp x mp, row stride ldc; mp = Z's rows padded to 128) = (K(Z,Z) - Wu^T Wu) + Wa^T Wa with Wu = Lu^-1 K(S,Z), Wa = La^-1 K(S,Z):
+// the full covariance of the variational posterior -- vfe_posterior_chunk's variance on the diagonal, in its order of operations.
+// posterior_cov_into's steps once per factor: fill, the cross-solve rule, transpose, its GEMM; nothing N x M.  kpz: the model's
+// kernel re-centred on S and Z.
+int vfe_posterior_cov_into(gpx_ctx* ctx, const FitcView& v, const KParams& kpz, const gpx_mat* S, const gpx_mat* Z, Scratch& sc,
+                           double* C, int64_t ldc) {
+  const int64_t nu = v.nu, nup = v.nup, m = Z->rows, mp = gpx_round_up(m, GPX_TILE), ldb = gpx_skew_ld(mp);
+  const bool oop = chol_cross_oop(nup);
+  double *B, *W = nullptr, *Wt, *D;
+  GPX_TRY(sc.get(nup * ldb * 8, &B));
+  if (oop) GPX_TRY(sc.get(nup * ldb * 8, &W));
+  GPX_TRY(sc.get(mp * nup * 8, &Wt));
+  GPX_TRY(sc.get(mp * mp * 8, &D));
+  GPX_TRY(launch_kfill(ctx, kpz, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, C, mp, mp, ldc));
+  for (int which = 0; which < 2; ++which) {
+    GPX_TRY(launch_kfill(ctx, kpz, S->p, nu, Z->p, m, 0, nullptr, 0, 0.0, B, nup, mp, ldb));   // (each solve consumes it)
+    GPX_TRY(chol_cross_solve(ctx, which == 0 ? v.Lu : v.La, B, ldb, W, ldb, mp));
+    GPX_TRY(launch_transpose(ctx, oop ? W : B, nup, mp, ldb, Wt, nup));
+    if (which == 0) {
+      GPX_TRY(launch_gemm(ctx, Wt, nup, Wt, nup, C, ldc, mp, mp, nup, true, true, false));
+    } else {
+      GPX_TRY(launch_gemm(ctx, Wt, nup, Wt, nup, D, mp, mp, mp, nup, true, false, false));
+      hipLaunchKernelGGL(vfe_cov_add_kernel, dim3((unsigned)mp, (unsigned)((mp + 255) / 256)), dim3(256), 0, ctx->stream, C, ldc,
+                         (const double*)D, mp);
+      GPX_HIP(hipGetLastError());
+    }
+  }
+  return 0;
 }
 
 // draw / argbest: S samples in chunks whose work matrices stay under the cross-matrix budget
@@ -458,6 +603,52 @@ int qei_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const g
 
 }  // namespace
 
+// The bodies of gpx_vfe_posterior_cov and gpx_vfe_psampler_create, behind fitc.hip's argument checks (gpx_internal.h)
+int vfe_posterior_cov_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov) {
+  FitcView v;
+  fitc_view(f, &v);
+  KParams kpz = *v.kp;   // the evaluation points may reach beyond the training domain
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
+  const int64_t m = Z->rows, mp = gpx_round_up(m, GPX_TILE);
+  Scratch sc(ctx);
+  double* pK;
+  GPX_TRY(sc.get(mp * mp * 8, &pK));
+  GPX_TRY(vfe_posterior_cov_into(ctx, v, kpz, S, Z, sc, pK, mp));
+  GPX_HIP(hipMemcpy2DAsync(cov, (size_t)m * 8, pK, (size_t)mp * 8, (size_t)m * 8, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int vfe_psampler_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
+                             gpx_psampler** out) {
+  FitcView v;
+  fitc_view(f, &v);
+  KParams kpz = *v.kp;
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Z));
+  const int64_t m = Z->rows, mp = gpx_round_up(m, GPX_TILE), d = kpz.d;
+  PolicyScope policy(ctx);   // a design loop may have left the drop policy on
+  Held<gpx_psampler, gpx_psampler_free> ps(ctx, new gpx_psampler{m, mp, nullptr, nullptr, 0});
+  GPX_TRY(gpx_mat_new(ctx, m, m, 1, &ps->F));
+  GPX_TRY(gpx_dev_alloc(ctx, mp * 8, &ps->mean));
+  ps->mean_bytes = mp * 8;
+  Scratch sc(ctx);
+  {
+    // the mean: gpx_vfe_posterior's chunks and launches (the bits it returns), each chunk straight into the resident vector
+    const ChunkRange cr(m, gpx_eval_chunk(v.nup));
+    VfePosteriorWork w(v.nup, cr.mc_alloc, false);
+    GPX_TRY(w.take(sc, false));
+    GPX_TRY(w.beta(ctx, f, coeff, sc));
+    for (const ChunkRange::Step c : cr) {
+      w.pm = ps->mean + c.j0;
+      GPX_TRY(w.run(ctx, f, kpz, S, Z->p + c.j0 * d, c.mc));
+    }
+  }
+  GPX_TRY(vfe_posterior_cov_into(ctx, v, kpz, S, Z, sc, ps->F->p, ps->F->ld));
+  GPX_TRY(psampler_factor(ctx, ps.get(), sc, nugget, true));
+  *out = ps.release();
+  return 0;
+}
+
 extern "C" {
 
 int gpx_psampler_free(gpx_ctx* ctx, gpx_psampler* ps) {
@@ -499,8 +690,6 @@ int gpx_psampler_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nh
   ps->mean_bytes = mp * 8;
   gpx_mat* F = ps->F;
   Scratch sc(ctx);
-  double* invd;
-  GPX_TRY(sc.get(mp * GPX_TILE * 8, &invd));
   if (prior) {
     GPX_HIP(hipMemsetAsync(ps->mean, 0, (size_t)mp * 8, ctx->stream));
     GPX_TRY(launch_kfill(ctx, kp, Z->p, m, Z->p, m, 1, nullptr, 0, 0.0, F->p, mp, mp, F->ld));
@@ -513,37 +702,7 @@ int gpx_psampler_create(gpx_ctx* ctx, int kind, int d, const double* hyp, int nh
     for (const ChunkRange::Step c : cr) GPX_TRY(w.run(ctx, kp, L, X, Z->p + c.j0 * d, c.mc, nullptr, ps->mean + c.j0));
     GPX_TRY(posterior_cov_into(ctx, kp, L, X, Z, sc, F->p, F->ld));
   }
-  hipLaunchKernelGGL(psampler_nugget_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, F->p, F->ld, m, nugget);
-  GPX_HIP(hipGetLastError());
-  // Chat is kept for one step of refinement: chol_potrf's leaf multiplies by explicit inverses of its diagonal blocks, and on a
-  // covariance whose spectrum reaches down to the nugget that leaves |F F^T - Chat| an order above what a plain Cholesky leaves
-  double *pR, *pY;
-  GPX_TRY(sc.get(mp * mp * 8, &pR));
-  GPX_TRY(sc.get(mp * mp * 8, &pY));
-  GPX_TRY(gpx_copy2d(ctx, F->p, F->ld, pR, mp, mp, mp));
-  GPX_TRY(chol_potrf(ctx, F->p, F->ld, mp, invd, m));
-  int info = 0;
-  GPX_HIP(hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  GPX_HIP(hipDeviceSynchronize());   // (the blocked factorisation of a large C uses three streams)
-  if (info != 0) {
-    gpx_set_error("psampler: C + nugget I is not positive definite (pivot %d <= 0, nugget %g): the point repeats an earlier one "
-                  "or lies on a training point of a noise-free model; a larger nugget factors it", info, nugget);
-    return info;
-  }
-  hipLaunchKernelGGL(psampler_finish_kernel, dim3((unsigned)mp, (unsigned)((mp + 255) / 256)), dim3(256), 0, ctx->stream, F->p,
-                     F->ld, m, mp);
-  GPX_HIP(hipGetLastError());
-  // R = Chat - F F^T;  G = F^-1 R F^-T (the leaf inverses of the factorisation serve both solves);  F += F Phi(G)
-  const dim3 gridM((unsigned)mp, (unsigned)((mp + 255) / 256));
-  GPX_TRY(launch_gemm(ctx, F->p, F->ld, F->p, F->ld, pR, mp, mp, mp, mp, true, true, false));
-  GPX_TRY(chol_trsm_left(ctx, F->p, F->ld, invd, pR, mp, mp, mp));
-  GPX_TRY(chol_trsm_right(ctx, F->p, F->ld, invd, pR, mp, mp, mp));
-  hipLaunchKernelGGL(psampler_phi_kernel, gridM, dim3(256), 0, ctx->stream, pR, mp, mp);
-  GPX_HIP(hipGetLastError());
-  GPX_TRY(launch_gemm_tri(ctx, F->p, F->ld, pR, mp, pY, mp, mp, mp, mp, false, false, false, 1));
-  hipLaunchKernelGGL(psampler_addlower_kernel, gridM, dim3(256), 0, ctx->stream, F->p, F->ld, (const double*)pY, mp, m);
-  GPX_HIP(hipGetLastError());
-  GPX_HIP(hipStreamSynchronize(ctx->stream));
+  GPX_TRY(psampler_factor(ctx, ps.get(), sc, nugget, false));
   *out = ps.release();
   return 0;
 }

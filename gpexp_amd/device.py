@@ -517,6 +517,39 @@ class VfeModel(FitcModel):
         check(self.ctx.lib.gpx_vfe_var_grad_newpt(self.ctx.h, self.h, S.h, Z.h, dptr(out)))
         return out
 
+    def path_sampler(self, S, coeff, omega, phase, w, eps_u, xi_q):
+        """A PathSampler of decoupled paths of the variational posterior (gpx_vfe_paths_create): f_s(z) = sum_j c_sj cos(omega_j . z
+        + phase_j) + sum_u v_su k(s_u, z) with V = 1 beta_u^T - (f~(S) + eps_u) Quu^-1 + xi_q La^-1.  S = the model's inducing
+        points, coeff = alpha from `solve`; omega (L, d), phase (L,), w (P, L) as device.PathSampler takes them; eps_u = sqrt(noise)
+        Xi1 and xi_q = Xi2, (P, nu) each or None (zeros), Xi1 and Xi2 standard normal.  `coefficients()` of the result is (P, nu)."""
+        d = S.shape[1]
+        omega, phase, w = as_f64(omega), as_f64(phase), as_f64(w)
+        assert omega.ndim == 2 and omega.shape[1] == d and phase.shape == (omega.shape[0],), "omega is (L, d), phase (L,)"
+        assert w.ndim == 2 and w.shape[1] == omega.shape[0], "w is (P, L)"
+        ep = as_f64(eps_u) if eps_u is not None else None
+        xq = as_f64(xi_q) if xi_q is not None else None
+        for a in (ep, xq):
+            assert a is None or a.shape == (w.shape[0], S.shape[0]), "eps_u and xi_q are (P, nu)"
+        co, h = as_f64(coeff), c_vp()
+        check(self.ctx.lib.gpx_vfe_paths_create(self.ctx.h, self.h, S.h, dptr(co), dptr(omega), dptr(phase),
+                                                omega.shape[0], dptr(w), dptr(ep), dptr(xq), w.shape[0], C.byref(h)))
+        return PathSampler.adopt(self.ctx, h, d)
+
+    def posterior_cov(self, Z):
+        """(M, M): the full covariance of the variational posterior at Z (gpx_vfe_posterior_cov), K(Z,Z) - Wu^T Wu + Wa^T Wa."""
+        cov = np.empty((Z.shape[0], Z.shape[0]))
+        check(self.ctx.lib.gpx_vfe_posterior_cov(self.ctx.h, self.h, self.S.h, Z.h, dptr(cov)))
+        return cov
+
+    def posterior_sampler(self, coeff, Z, nugget):
+        """A PosteriorSampler at the M points Z (gpx_vfe_psampler_create): `posterior`'s mean and chol(posterior_cov + nugget I)."""
+        co, h = as_f64(coeff), c_vp()
+        rc = self.ctx.lib.gpx_vfe_psampler_create(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, float(nugget), C.byref(h))
+        if rc > 0:
+            raise _sampler_not_pd(rc, float(nugget))
+        check(rc)
+        return PosteriorSampler.adopt(self.ctx, h, Z.shape[0], nugget)
+
 
 class VfeDesign:
     """Device-resident state of IVAR design on a VFE model (gpx_vfe_design_*): chol(Quu), the Gram matrix of the Monte-Carlo points
@@ -745,6 +778,13 @@ class PosteriorSampler:
         check(rc)
         self.h = h
 
+    @classmethod
+    def adopt(cls, ctx, handle, m, nugget):
+        """The sampler of a gpx_psampler handle another constructor made (VfeModel.posterior_sampler): it owns the handle from here on."""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self.m, self.nugget = ctx, handle, int(m), float(nugget)
+        return self
+
     def draw(self, xi):
         """(S, M) joint samples: row s = mean + F xi[s]."""
         xi = as_f64(xi)
@@ -796,6 +836,17 @@ class PathSampler:
         check(ctx.lib.gpx_paths_create(ctx.h, *spec.args(), L.h if L is not None else None, X.h if X is not None else None,
                                        dptr(al), dptr(omega), dptr(phase), self.nfeat, dptr(w), dptr(ep), self.S, C.byref(h)))
         self.h = h
+
+    @classmethod
+    def adopt(cls, ctx, handle, d):
+        """The sampler of a gpx_paths handle another constructor made (VfeModel.path_sampler): it owns the handle from here on; S,
+        nfeat and n (the rows of the point block: nu on a VFE model) are the handle's own."""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self.d = ctx, handle, int(d)
+        s, nf, n = c_i64(), c_i64(), c_i64()
+        check(ctx.lib.gpx_paths_shape(handle, C.byref(s), C.byref(nf), C.byref(n)))
+        self.S, self.nfeat, self.n = s.value, nf.value, n.value
+        return self
 
     def evaluate(self, Z):
         """(S, M): row s = path s at the rows of the device point set Z."""

@@ -729,10 +729,22 @@ class _costFuncBO(costFunctionBase):
         `jitter`: the sampler's nugget (default 1e-10 * max k(c, c)).  Dense models only (NotImplementedError on FITC / VFE)."""
         gp = self.gaussianProcess
         gp._sampling_ready("thompsonBatch")
+        return self._thompsonBatch(gp.posteriorSampler, candidates, nPoints, baseSamples, jitter, minimize)
+
+    def vfeThompsonBatch(self, candidates, nPoints, baseSamples=None, jitter=None, minimize=True):
+        """thompsonBatch on a VFE model: the same picks from EXACT joint draws of the variational posterior at the candidates
+        (GP.vfePosteriorSampler -> gpx_vfe_psampler_create).  ValueError on a dense or FITC model."""
+        return self._thompsonBatch(self.gaussianProcess.vfePosteriorSampler, candidates, nPoints, baseSamples, jitter, minimize)
+
+    def _thompsonCandidates(self, candidates):
         candidates = np.asarray(candidates, dtype=float)
         assert candidates.ndim == 2 and candidates.shape[1] == self.space.dimension, \
             ("candidates are the wrong size: ", candidates.shape)
-        smp = gp.posteriorSampler(candidates, jitter=jitter)
+        return candidates
+
+    def _thompsonBatch(self, posteriorSampler, candidates, nPoints, baseSamples, jitter, minimize):
+        """The body of thompsonBatch / vfeThompsonBatch; `posteriorSampler`: the GP's constructor of the joint sampler."""
+        smp = posteriorSampler(self._thompsonCandidates(candidates), jitter=jitter)
         try:
             idx, val = smp.argbest(int(nPoints), baseSamples, minimize=minimize)
         finally:
@@ -752,10 +764,21 @@ class _costFuncBO(costFunctionBase):
         bounding box).  A polished point replaces the discrete winner only where its value is better, so no value is worse than
         the discrete one; `indices` stays the discrete index.  Pathwise samples are approximate draws (GP.pathSampler);
         thompsonBatch draws exactly.  Stationary kernels and dense models only (NotImplementedError otherwise)."""
-        gp = self.gaussianProcess
-        candidates = np.asarray(candidates, dtype=float)
-        assert candidates.ndim == 2 and candidates.shape[1] == self.space.dimension, \
-            ("candidates are the wrong size: ", candidates.shape)
+        return self._thompsonPaths(self.gaussianProcess.pathSampler, candidates, nPoints, nFeatures, base, minimize, polish, lbounds,
+                                   rbounds, maxiter)
+
+    def vfeThompsonPaths(self, candidates, nPoints, nFeatures=1024, base=None, minimize=True, polish=False, lbounds=None,
+                         rbounds=None, maxiter=50):
+        """thompsonPaths on a VFE model, with decoupled paths of the variational posterior (GP.vfePathSampler ->
+        gpx_vfe_paths_create): a pick costs O(nFeatures + nu) per candidate whatever the training-set size.  `base`: a PathBase
+        drawn with nTrain = 2 nu.  Everything else, `polish` included, as thompsonPaths.  ValueError on a dense or FITC model,
+        NotImplementedError for a Mehler kernel."""
+        return self._thompsonPaths(self.gaussianProcess.vfePathSampler, candidates, nPoints, nFeatures, base, minimize, polish,
+                                   lbounds, rbounds, maxiter)
+
+    def _thompsonPaths(self, pathSampler, candidates, nPoints, nFeatures, base, minimize, polish, lbounds, rbounds, maxiter):
+        """The body of thompsonPaths / vfeThompsonPaths; `pathSampler`: the GP's constructor of the paths."""
+        candidates = self._thompsonCandidates(candidates)
         q, d = int(nPoints), candidates.shape[1]
         inside = None
         if polish:
@@ -765,7 +788,7 @@ class _costFuncBO(costFunctionBase):
             inside = np.flatnonzero(np.all((candidates >= lb) & (candidates <= ub), axis=1))
             if len(inside) == 0:
                 raise ValueError("thompsonPaths: no candidate lies inside the bounds")
-        smp = gp.pathSampler(q, nFeatures, base)
+        smp = pathSampler(q, nFeatures, base)
         try:
             q = smp.nPaths
             if inside is None or len(inside) == len(candidates):

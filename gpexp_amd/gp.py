@@ -594,7 +594,8 @@ class GP:
                                                                       draw the first index of its minimum / maximum
             close()
         The device makes no random numbers: `baseSamples` (S, M) are the standard-normal base samples, drawn with
-        np.random.standard_normal when None -- the same base samples give the same bits.  Dense models only; under a multi-process
+        np.random.standard_normal when None -- the same base samples give the same bits.  Dense models only (a VFE model has
+        vfePosteriorSampler); under a multi-process
         session the calls run replicated, and baseSamples=None raises ValueError there (every rank would draw its own)."""
         self._sampling_ready("posteriorSampler")
         newpt = np.asarray(newpt, dtype=float)
@@ -668,7 +669,7 @@ class GP:
         with NumPy when None -- the same base gives the same bits.  These are NOT exact posterior samples: with finitely many
         features the prior part has covariance Phi Phi^T instead of K (the mean is exact, the covariance tends to the posterior's as
         nFeatures grows); posteriorSampler stays the exact one.  Stationary kernels, dense models and scalar noise only
-        (NotImplementedError); under a multi-process session the calls run replicated, and base=None raises ValueError there."""
+        (NotImplementedError; a VFE model has vfePathSampler); under a multi-process session the calls run replicated, and base=None raises ValueError there."""
         self._sampling_ready("pathSampler")
         if np.ndim(self.noise) != 0:
             raise NotImplementedError("pathSampler needs a scalar noise: there is no pathwise sampler for per-point noise")
@@ -698,6 +699,74 @@ class GP:
         spec = self.kernel._spec()
         state = _dev.PathSampler(ctx, spec, None, None, None, _spectralFrequencies(spec, base.g, base.u), base.phase, base.w, None)
         return PathSampler(state, base, self.kernel.dimension)
+
+    # ---- the same samplers on a VFE model: of the optimal variational posterior, in the inducing space -----------------------------
+    def _vfe_sampling_ready(self, name, denseName):
+        if not self._vfe():
+            raise ValueError("%s samples the variational posterior of VFE models (GP(..., FITC=fraction, sparse='vfe')); on a dense "
+                             "model use %s; there is no sampler for FITC models" % (name, denseName))
+        if self.pts is None or self._fitc is None or self.coeff is None:
+            raise ValueError("%s needs a trained model: call train first" % name)
+
+    def vfePathSampler(self, nPaths=1, nFeatures=1024, base=None):
+        """pathSampler on a VFE model (gpx_vfe_paths_create; decoupled sampling, Wilson et al. 2020): `nPaths` paths of the optimal
+        variational posterior, f_s(z) = sum_j c_sj cos(omega_j . z + b_j) + sum_u v_su k(s_u, z) over the nu inducing points with
+            V = 1 beta_u^T - (f~(S) + sqrt(noise) Xi1) Quu^-1 + Xi2 La^-1,
+        Xi1 the nugget draw of the inducing variables u = f(S) + eps and Xi2 the draw of q(u).  A path costs O(nFeatures + nu) per
+        point, whatever the training-set size, and the build two nu-order solves for all paths at once.  Returns the object
+        pathSampler returns (evaluate, argbest, gradient, base, close).  `base`: a PathBase drawn with nTrain = 2 nu
+        (PathBase.draw(nPaths, nFeatures, 2 * nu, d, kernel, rng)): xi[:, :nu] is Xi1 and xi[:, nu:] is Xi2; drawn with NumPy when
+        None -- the same base gives the same bits.  Zero draws give evaluate's mean; as nFeatures grows the covariance tends to
+        vfePosteriorCovariance's (vfePosteriorSampler is the exact sampler).  ValueError on a dense or FITC model and before train;
+        NotImplementedError for a Mehler kernel; under a multi-process session the calls run replicated, and base=None raises
+        ValueError there."""
+        self._vfe_sampling_ready("vfePathSampler", "pathSampler")
+        nu = self.fitcnodes.shape[0]
+        base = self._pathBase("vfePathSampler", nPaths, nFeatures, base, 2 * nu)
+        spec = self.kernel._spec()
+        state = self._fitc.path_sampler(self._fitc.S, self.coeff, _spectralFrequencies(spec, base.g, base.u), base.phase, base.w,
+                                        np.sqrt(float(self.noise)) * base.xi[:, :nu], base.xi[:, nu:])
+        return PathSampler(state, base, self.kernel.dimension)
+
+    def vfeSamplePaths(self, newpt, nPaths=1, nFeatures=1024, base=None):
+        """(nPaths, M) pathwise samples of the variational posterior at `newpt`: vfePathSampler(...).evaluate(newpt)."""
+        smp = self.vfePathSampler(nPaths, nFeatures, base)
+        try:
+            return smp.evaluate(newpt)
+        finally:
+            smp.close()
+
+    def _vfe_points(self, newpt):
+        newpt = np.asarray(newpt, dtype=float)
+        assert newpt.ndim == 2 and newpt.shape[1] == self.kernel.dimension, "evaluation points for GP is incorrect shape"
+        return newpt, _dev.points(_dev.context(), newpt)
+
+    def vfePosteriorCovariance(self, newpt):
+        """(M, M): the full covariance of the variational posterior of the latent function at `newpt` (gpx_vfe_posterior_cov),
+        k(z,z') - k_u^T Quu^-1 k_u' + k_u^T A^-1 k_u' -- what evaluate(compvar=2) is on a dense model; its diagonal is
+        evaluateVariance.  Every kernel.  ValueError on a dense or FITC model and before train."""
+        self._vfe_sampling_ready("vfePosteriorCovariance", "evaluate(compvar=2)")
+        return self._fitc.posterior_cov(self._vfe_points(newpt)[1])
+
+    def vfePosteriorSampler(self, newpt, jitter=None, addNoise=False):
+        """posteriorSampler on a VFE model (gpx_vfe_psampler_create): the EXACT joint sampler of the variational posterior at the M
+        rows of `newpt` -- evaluate's mean and F = chol(vfePosteriorCovariance + nugget I) stay on the device.  The nugget, its
+        default (1e-10 * max k(z, z)), `addNoise`, NotPositiveDefinite and the object returned (draw, argbest, close) are
+        posteriorSampler's.  Every kernel.  ValueError on a dense or FITC model and before train."""
+        self._vfe_sampling_ready("vfePosteriorSampler", "posteriorSampler")
+        newpt, Z = self._vfe_points(newpt)
+        nugget = self._jitter(_dev.context(), self.kernel._spec(), Z, jitter, "vfePosteriorSampler")
+        if addNoise:
+            nugget += float(self.noise)
+        return JointSampler(self._fitc.posterior_sampler(self.coeff, Z, nugget), newpt.shape[0])
+
+    def vfeSamplePosterior(self, newpt, nSamples=1, baseSamples=None, jitter=None):
+        """(nSamples, M) joint samples of the variational posterior at `newpt`: vfePosteriorSampler(newpt, jitter).draw(...)."""
+        smp = self.vfePosteriorSampler(newpt, jitter=jitter)
+        try:
+            return smp.draw(nSamples, baseSamples)
+        finally:
+            smp.close()
 
     # ---- marginal likelihood -------------------------------------------------------------------------------------
     def computeLogLike(self, pts, evals):

@@ -37,7 +37,10 @@ class PathBase(object):
     """The base draws of S paths with L features on N training points in d dimensions:
         g (L, d) standard normal;  u (L,) chi^2(2 nu) or None (squared exponential);  phase (L,) uniform in [0, 2 pi);
         w (S, L) standard normal;  xi (S, N) standard normal -- the noise draw is eps = sqrt(noise) xi.
-    The same PathBase gives the same paths, bit for bit."""
+    The same PathBase gives the same paths, bit for bit.
+    On a VFE model (GP.vfePathSampler) the update lives in the inducing space and takes TWO draws per inducing point: the base is
+    drawn with nTrain = 2 nu, xi[:, :nu] is Xi1 (the nugget draw of the inducing variables, eps_u = sqrt(noise) Xi1) and xi[:, nu:]
+    is Xi2 (the draw of the variational distribution q(u))."""
 
     def __init__(self, g, u, phase, w, xi):
         self.g = np.ascontiguousarray(g, dtype=np.float64)

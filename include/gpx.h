@@ -557,6 +557,40 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
                       int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie,
                       double* all_costs);
 
+/* ---- posterior sampling on a VFE model --------------------------------------------------------------------------------------------
+ * The two samplers above for the model gpx_vfe_fit built; the kernel parameters are the model's, S its inducing points, coeff =
+ * alpha from gpx_fitc_solve (host N, required); notation as for gpx_vfe_acq.  The samplers' two rules hold (no random numbers on
+ * the device; a nugget and the pivot policy (0, report)).  A FITC model is refused with an argument error.
+ *
+ * gpx_vfe_paths_create: DECOUPLED paths of the variational posterior (Wilson et al. 2020): Matheron's rule on (f, u) with the
+ *   inducing variables u = f(S) + eps drawn from the optimal q(u) = N(Quu beta_u, Quu A^-1 Quu),
+ *       f_s(z) = sum_j c_sj cos(omega_j . z + b_j) + sum_u v_su k(s_u, z),       c = sqrt(2 signalSize / nfeat) w
+ *       V      = 1 beta_u^T - (F~_S + eps_u) Quu^-1 + xi_q La^-1                 (nPaths x nu;  F~_S[s][u] = f~_s(s_u))
+ *   omega, phase, nfeat, w: as gpx_paths_create.  eps_u = sqrt(noise) Xi1 (the nugget draw of the inducing variables) and xi_q =
+ *   Xi2 (the draw of q(u); row s of xi_q La^-1 is (La^-T xi2_s)^T): host nPaths x nu, each nullable (NULL = zeros), Xi1, Xi2
+ *   standard normal.  Zero draws give the predictor's mean; the exact prior in place of the features would give the predictor's
+ *   covariance (gpx_vfe_posterior_cov); with nfeat features the covariance at Z is A_J (Phi_J Phi_J^T) A_J^T + noise G_u G_u^T +
+ *   K_zu A^-1 K_uz with G_u = K_zu Quu^-1, A_J = [I, -G_u] and Phi_J the features at (Z; S).  The result is an ordinary gpx_paths
+ *   whose point block holds S and V: gpx_paths_eval, _grad, _coeff (nPaths x nu), _shape (n = nu) and _free serve it unchanged, with
+ *   every bit-for-bit property they have.  The build runs on the device for all paths at once: f~ at S by gpx_paths_eval's own
+ *   kernel, two blocked right solves against Lu and one against La (O(nu^2) per path; nothing of size N but beta_u's reduction).
+ *   Stationary kernels only (a Mehler model is an argument error); nfeat < 1 and nPaths < 1 are argument errors.
+ * gpx_vfe_posterior_cov: cov (host M x M) = (K(Z,Z) - Wu^T Wu) + Wa^T Wa with Wu = Lu^-1 K(S,Z), Wa = La^-1 K(S,Z), the full
+ *   covariance of the variational posterior; its diagonal is gpx_vfe_posterior's variance up to the order of summation.  Every
+ *   kernel kind; nothing N x M is formed; no chunking over Z.
+ * gpx_vfe_psampler_create: the exact joint sampler at the M points of Z: the mean holds the bits gpx_vfe_posterior returns, C is
+ *   formed as by gpx_vfe_posterior_cov, and the nugget, the factorisation, its refinement step and the pivot report are
+ *   gpx_psampler_create's own, and its tail with one addition: the residual max |Chat - F F^T|_ij / sqrt(Chat_ii Chat_jj) is
+ *   measured on the device after the refinement step, and while it is above 4 (M + 1) u the step is repeated (four more times at
+ *   most) -- many points on a line under a squared exponential need it; a covariance that does not is left with one step.
+ *   gpx_psampler_draw, _argbest, _shape and _free serve the result.  Every kernel kind. */
+int gpx_vfe_paths_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,
+                         const double* phase, int64_t nfeat, const double* w, const double* eps_u, const double* xi_q,
+                         int64_t nPaths, gpx_paths** out);
+int gpx_vfe_posterior_cov(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov);
+int gpx_vfe_psampler_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
+                            gpx_psampler** out);
+
 /* ---- IVAR design on a VFE model, in the inducing space (none in the reference) -----------------------------------------------------
  * With k_u(.) = K(S, .), Quu = K(S,S) + noise I = Lu Lu^T and, for design points X, A = Quu + sum_i k_u(x_i) k_u(x_i)^T / noise =
  * La La^T, the variational variance is var(z) = k(z,z) - k_u(z)^T Quu^-1 k_u(z) + k_u(z)^T A^-1 k_u(z): the design enters through the
