@@ -69,6 +69,8 @@ _SIGS = {
     "gpx_vfe_paths_create": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp, c_dp, c_i64, C.POINTER(c_vp)]),
     "gpx_vfe_posterior_cov": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_dp]),
     "gpx_vfe_psampler_create": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_double, C.POINTER(c_vp)]),
+    "gpx_vfe_acq_qei": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_i64, c_dp, c_i64, C.c_double, C.c_double, c_dp, c_ip, c_dp, c_ip]),
+    "gpx_dbg_vfe_qei_blocks": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_i64, C.c_double, c_dp, c_dp, c_dp]),
     "gpx_potrs_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gpx_logdet": (C.c_int, [c_vp, c_vp, c_dp]),
     "gpx_potri": (C.c_int, [c_vp, c_vp, C.POINTER(c_vp)]),

@@ -1372,6 +1372,36 @@ int gpx_vfe_psampler_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, c
   return vfe_psampler_create_impl(ctx, f, S, coeff, Z, nugget, out);
 }
 
+// The argument rules of gpx_vfe_acq_qei and its debug hook: gpx_acq_qei's, on a VFE model and its own S (body: sample.hip)
+static int vfe_qei_args(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q,
+                        double nugget) {
+  GPX_ARG(ctx && f && S && coeff && Zb, "NULL argument");
+  FITC_KIND(f, true, "vfe_acq_qei", "joint expected improvement is offered on dense models (gpx_acq_qei) and VFE models only");
+  GPX_ARG(q >= 1 && q <= GPX_QEI_MAX_Q, "q-EI: the batch size q must be in 1 .. GPX_QEI_MAX_Q (32)");
+  GPX_ARG(nugget >= 0.0, "q-EI: the nugget must not be negative");
+  GPX_TRY(vfe_point_sets(f, S, Zb));
+  GPX_ARG(Zb->rows >= q && Zb->rows % q == 0, "q-EI: the rows of Zb must be a positive multiple of q (consecutive q rows form one batch)");
+  return 0;
+}
+
+int gpx_vfe_acq_qei(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q,
+                    const double* xi, int64_t nS, double fBest, double nugget, double* cost, int64_t* best, double* best_cost,
+                    int64_t* n_bad) {
+  GPX_TRY(vfe_qei_args(ctx, f, S, coeff, Zb, q, nugget));
+  GPX_ARG(nS >= 1 && nS < ((int64_t)1 << 31), "q-EI: needs at least one base sample (and fewer than 2^31)");
+  GPX_ARG(xi != nullptr, "q-EI: xi is NULL");
+  return vfe_qei_impl(ctx, f, S, coeff, Zb, q, xi, nS, fBest, nugget, cost, best, best_cost, n_bad, nullptr, nullptr, nullptr);
+}
+
+// debug (gpx_debug.h): the blocks qei_kernel works on -- gpx_vfe_acq_qei's launches with one zero base sample
+int gpx_dbg_vfe_qei_blocks(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q,
+                           double nugget, double* mean, double* Cb, double* Fb) {
+  GPX_TRY(vfe_qei_args(ctx, f, S, coeff, Zb, q, nugget));
+  GPX_ARG(mean && Cb && Fb, "NULL argument");
+  const std::vector<double> xi0((size_t)q, 0.0);
+  return vfe_qei_impl(ctx, f, S, coeff, Zb, q, xi0.data(), 1, 0.0, nugget, nullptr, nullptr, nullptr, nullptr, mean, Cb, Fb);
+}
+
 // Point-wise derivatives of the variational variance (bodies: vfe_design.hip; the argument checks are here, where the struct is)
 int gpx_vfe_var_grad(gpx_ctx* ctx, const gpx_fitc* f, int kind, int d, const double* hyp, int nhyp, const gpx_mat* X,
                      const gpx_mat* S, const gpx_mat* Z, double* out) {

@@ -521,6 +521,11 @@ int vfe_paths_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, con
 int vfe_posterior_cov_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov);
 int vfe_psampler_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
                              gpx_psampler** out);
+// sample.hip: the body of gpx_vfe_acq_qei and gpx_dbg_vfe_qei_blocks (dbg_*: host B x q, B x q x q, B x q x q; all three or none),
+// behind fitc.hip's argument checks (a VFE model, its own S, q in range, rows of Zb a positive multiple of q, nS >= 1, nugget >= 0)
+int vfe_qei_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q, const double* xi,
+                 int64_t nS, double fBest, double nugget, double* cost_host, int64_t* best, double* best_cost, int64_t* n_bad,
+                 double* dbg_mean, double* dbg_C, double* dbg_F);
 // acq.hip: out_c[0], out_i[0] (device) = the first minimum among the nparts arg-min partials {cost, index} with index >= 0
 // (argmin_merge; index -1 and a NaN cost when there is none) -- gpx_acq's final reduction, for sample.hip's q-EI partials
 int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i, int64_t nparts, double* out_c, int64_t* out_i);

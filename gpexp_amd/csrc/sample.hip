@@ -40,6 +40,11 @@
 // G, T and nsl depend on q alone and every batch is worked with the same arithmetic wherever it sits: permuting the batches
 // permutes the costs bit for bit.  A batch whose factorisation meets a pivot <= 0 gets cost NaN and is counted; the arg-min is
 // the first minimum among the non-NaN costs (argmin_merge), one partial per workgroup, reduced by gpx_acq's own kernel.
+//
+// On a VFE model (gpx_vfe_acq_qei: entry in fitc.hip, body vfe_qei_impl here) the means, Wu = Lu^-1 K(S, Zb) and Wa = La^-1 K(S, Zb)
+// come from vfe_posterior_chunk and step 1 runs twice, qei_kernel<.., true>: C_b = (k - Wu_b^T Wu_b) + Wa_b^T Wa_b, a SIGNED Gram of two
+// factors, each sum by the rule of step 1 over the nu inducing rows; steps 2 and 3 are the same code.  QeiRun holds what the two
+// drivers share.
 #include "gpx_device.h"
 #include <math.h>
 #include <vector>
@@ -319,16 +324,57 @@ QeiPlan qei_plan(int q) {
   return p;
 }
 
+// One Gram pass of qei_kernel over one factor W (n rows used, row stride ldw; the workgroup's columns [c0, c0 + ncols)): on return
+// part[p nsl + sl] holds slice sl of entry p -- sum over the rows r = sl (mod nsl), r < n, of W[r][ci] W[r][cj], one fma chain in
+// ascending r -- and the workgroup is synchronised.  Rows pass through `tile` in tiles of QEI_TR; rows >= n are never read.
+__device__ __forceinline__ void qei_gram_pass(const double* __restrict__ W, int64_t ldw, int64_t n, int64_t c0, int ncols, int gb,
+                                              int q, const QeiPlan& pl, double* __restrict__ tile, double* __restrict__ part,
+                                              const unsigned char* __restrict__ pi_, const unsigned char* __restrict__ pj_) {
+  const int t = threadIdx.x, nsl = pl.nsl, npair = pl.npair;
+  const int nitems = pl.G * npair * nsl;
+  double acc[QEI_ITEMS];
+#pragma unroll
+  for (int k = 0; k < QEI_ITEMS; ++k) acc[k] = 0.0;
+  for (int64_t r0 = 0; r0 < n; r0 += QEI_TR) {
+    const int rows = (n - r0) < QEI_TR ? (int)(n - r0) : QEI_TR;
+    __syncthreads();   // the previous tile is consumed (first pass: the tables are written; second: the slices are added up)
+    for (int e = t; e < rows * ncols; e += 256) {
+      const int r = e / ncols, c = e - r * ncols;
+      tile[r * QEI_TS + c] = W[(r0 + r) * ldw + c0 + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < QEI_ITEMS; ++k) {
+      const int it = t + 256 * k;
+      if (it >= nitems) continue;
+      const int p = it / nsl, sl = it - p * nsl, g = p / npair;
+      if (g >= gb) continue;
+      const int pp = p - g * npair, ci = g * q + pi_[pp], cj = g * q + pj_[pp];
+      double a = acc[k];
+      for (int r = sl; r < rows; r += nsl) a = fma(tile[r * QEI_TS + ci], tile[r * QEI_TS + cj], a);
+      acc[k] = a;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < QEI_ITEMS; ++k)
+    if (t + 256 * k < nitems) part[t + 256 * k] = acc[k];
+  __syncthreads();
+}
+
 // One workgroup = the batches [gb0, gb0 + G) of the chunk (fewer at the chunk's end).  W: the chunk's solved cross matrix (n rows
 // used, row stride ldw), batch b its columns [b q, (b + 1) q); Zc / mean: the chunk's points and posterior means; b0: the chunk's
 // first batch in the call (cost, the partials' indices and the debug blocks are addressed by the global batch).
-template <int QMAX>
-__global__ __launch_bounds__(256) void qei_kernel(KParams kp, const double* __restrict__ W, int64_t ldw, int64_t n,
-                                                  const double* __restrict__ Zc, const double* __restrict__ mean, int q, QeiPlan pl,
-                                                  int64_t nb, int64_t b0, const double* __restrict__ xi, int64_t S, double fBest,
-                                                  double nugget, double* __restrict__ cost, double* __restrict__ part_c,
-                                                  int64_t* __restrict__ part_i, int* __restrict__ nbad, double* __restrict__ dbgC,
-                                                  double* __restrict__ dbgF) {
+// VFE: the signed two-factor Gram of a variational model, C_b = (k - Wu^T Wu) + Wa^T Wa with W = Wu = Lu^-1 K(S, Zb) and W2 = Wa =
+// La^-1 K(S, Zb) (same stride, n = nu rows each): two passes of the one tile loop, first Wu then Wa, `tile` and `part` reused;
+// after the first A = k - su, after the second A += sa -- vfe_posterior_chunk's pv = (kd - su) + sa, entry by entry.  The dense
+// instantiation ignores W2 and is the kernel it was.
+template <int QMAX, bool VFE>
+__global__ __launch_bounds__(256) void qei_kernel(KParams kp, const double* __restrict__ W, const double* __restrict__ W2, int64_t ldw,
+                                                  int64_t n, const double* __restrict__ Zc, const double* __restrict__ mean, int q,
+                                                  QeiPlan pl, int64_t nb, int64_t b0, const double* __restrict__ xi, int64_t S,
+                                                  double fBest, double nugget, double* __restrict__ cost,
+                                                  double* __restrict__ part_c, int64_t* __restrict__ part_i, int* __restrict__ nbad,
+                                                  double* __restrict__ dbgC, double* __restrict__ dbgF) {
   __shared__ double tile[QEI_TR * QEI_TS];
   __shared__ double part[256 * QEI_ITEMS];
   __shared__ double A[32 * 32];          // G blocks of q x q
@@ -353,34 +399,7 @@ __global__ __launch_bounds__(256) void qei_kernel(KParams kp, const double* __re
     bad[t] = 0;
   }
   // ---- 1. W_b^T W_b, entry by entry ----
-  const int nitems = G * npair * nsl;
-  double acc[QEI_ITEMS];
-#pragma unroll
-  for (int k = 0; k < QEI_ITEMS; ++k) acc[k] = 0.0;
-  for (int64_t r0 = 0; r0 < n; r0 += QEI_TR) {
-    const int rows = (n - r0) < QEI_TR ? (int)(n - r0) : QEI_TR;
-    __syncthreads();   // the previous tile is consumed (first pass: the tables are written)
-    for (int e = t; e < rows * ncols; e += 256) {
-      const int r = e / ncols, c = e - r * ncols;
-      tile[r * QEI_TS + c] = W[(r0 + r) * ldw + c0 + c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < QEI_ITEMS; ++k) {
-      const int it = t + 256 * k;
-      if (it >= nitems) continue;
-      const int p = it / nsl, sl = it - p * nsl, g = p / npair;
-      if (g >= gb) continue;
-      const int pp = p - g * npair, ci = g * q + pi_[pp], cj = g * q + pj_[pp];
-      double a = acc[k];
-      for (int r = sl; r < rows; r += nsl) a = fma(tile[r * QEI_TS + ci], tile[r * QEI_TS + cj], a);
-      acc[k] = a;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < QEI_ITEMS; ++k)
-    if (t + 256 * k < nitems) part[t + 256 * k] = acc[k];
-  __syncthreads();
+  qei_gram_pass(W, ldw, n, c0, ncols, gb, q, pl, tile, part, pi_, pj_);
   for (int p = t; p < G * npair; p += 256) {
     const int g = p / npair;
     if (g >= gb) continue;
@@ -390,6 +409,19 @@ __global__ __launch_bounds__(256) void qei_kernel(KParams kp, const double* __re
     const double v = kpair(kp, Zc + (c0 + g * q + i) * d, Zc + (c0 + g * q + j) * d) - s;
     A[g * qq + i * q + j] = v;
     A[g * qq + j * q + i] = v;
+  }
+  if (VFE) {
+    qei_gram_pass(W2, ldw, n, c0, ncols, gb, q, pl, tile, part, pi_, pj_);   // (its first barrier: `part` and A are settled)
+    for (int p = t; p < G * npair; p += 256) {
+      const int g = p / npair;
+      if (g >= gb) continue;
+      const int pp = p - g * npair, i = pi_[pp], j = pj_[pp];
+      double s = part[p * nsl];
+      for (int sl = 1; sl < nsl; ++sl) s += part[p * nsl + sl];
+      const double v = A[g * qq + i * q + j] + s;
+      A[g * qq + i * q + j] = v;
+      A[g * qq + j * q + i] = v;
+    }
   }
   __syncthreads();
   if (dbgC)
@@ -515,52 +547,47 @@ __global__ __launch_bounds__(256) void qei_kernel(KParams kp, const double* __re
   }
 }
 
-// Shared body of gpx_acq_qei and gpx_dbg_qei_blocks (dbg_*: host B x q, B x q x q, B x q x q; all three or none).
-int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Zb, int64_t q,
-             const double* xi, int64_t S, double fBest, double nugget, double* cost_host, int64_t* best, double* best_cost,
-             int64_t* n_bad, double* dbg_mean, double* dbg_C, double* dbg_F) {
-  const int64_t n = L->rows, np = L->prows, B = Zb->rows / q, d = kp.d;
-  const QeiPlan pl = qei_plan((int)q);
+// What gpx_acq_qei and gpx_vfe_acq_qei share around qei_kernel: the chunking over whole batches, the call's buffers, the launch of
+// one chunk and the final reduction with its copies.  np: the padded order of the factor(s) the chunk is solved against.
+struct QeiRun {
+  const int64_t q, B, S;
+  const QeiPlan pl;
+  int64_t bc, ngroups, g0 = 0;   // batches per chunk, workgroups of the call, workgroups launched so far
+  double *dxi = nullptr, *dcost = nullptr, *part_c = nullptr, *best_c = nullptr, *dC = nullptr, *dF = nullptr;
+  int64_t *part_i = nullptr, *best_i = nullptr;
+  int* dbad = nullptr;
+
   // whole batches per chunk (whole workgroup spans while the chunk holds one): its own step rule, not ChunkRange's
-  const int64_t mcmax = gpx_eval_chunk(np);
-  int64_t bc = mcmax / q;
-  if (bc >= pl.G) bc = bc / pl.G * pl.G;
-  if (bc > B) bc = B;
-  const int64_t nchunks = (B + bc - 1) / bc, ngroups = (bc + pl.G - 1) / pl.G * nchunks;
-  double *dxi, *dcost, *part_c, *best_c, *dC = nullptr, *dF = nullptr;
-  int64_t *part_i, *best_i;
-  int* dbad;
-  PosteriorWork w(np, gpx_round_up(bc * q, GPX_TILE), true);
-  std::vector<int> hbad((size_t)ngroups, 0);
-  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
-  GPX_TRY(w.take(sc, true, true));
-  GPX_TRY(sc.get(S * q * 8, &dxi));
-  GPX_TRY(sc.get(B * 8, &dcost));
-  GPX_TRY(sc.get(ngroups * 8, &part_c));
-  GPX_TRY(sc.get(ngroups * 8, &part_i));
-  GPX_TRY(sc.get(ngroups * 4, &dbad));
-  GPX_TRY(sc.get(8, &best_c));
-  GPX_TRY(sc.get(8, &best_i));
-  if (dbg_C) {
-    GPX_TRY(sc.get(B * q * q * 8, &dC));
-    GPX_TRY(sc.get(B * q * q * 8, &dF));
+  QeiRun(int64_t np, int64_t q_, int64_t B_, int64_t S_) : q(q_), B(B_), S(S_), pl(qei_plan((int)q_)) {
+    bc = gpx_eval_chunk(np) / q;
+    if (bc >= pl.G) bc = bc / pl.G * pl.G;
+    if (bc > B) bc = B;
+    ngroups = (bc + pl.G - 1) / pl.G * ((B + bc - 1) / bc);
   }
-  GPX_TRY(w.upload_alpha(ctx, alpha, n));
-  GPX_HIP(hipMemcpyAsync(dxi, xi, (size_t)(S * q * 8), hipMemcpyHostToDevice, ctx->stream));
-  int64_t g0 = 0;
-  for (int64_t b0 = 0; b0 < B; b0 += bc) {
-    const int64_t nb = (B - b0) < bc ? (B - b0) : bc, mc = nb * q;
-    const int64_t ldb = gpx_skew_ld(gpx_round_up(mc, GPX_TILE)), groups = (nb + pl.G - 1) / pl.G;
-    const double* Zc = Zb->p + b0 * q * d;
-    // gpx_posterior's own per-chunk step: the means are GP.evaluate's, W the solve every variance comes from
-    GPX_TRY(w.run(ctx, kp, L, X, Zc, mc, dbg_mean ? dbg_mean + b0 * q : nullptr));
-    const double *Wsol = w.solution(), *pmean = w.mean;
-    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nb * ((double)n * (double)(q * (q + 1)) + (double)S * (double)(q * (q + 1))),
-                 8.0 * (double)n * (double)mc);
+  int64_t mc_alloc() const { return gpx_round_up(bc * q, GPX_TILE); }
+  int take(gpx_ctx* ctx, Scratch& sc, const double* xi, bool dbg) {
+    GPX_TRY(sc.get(S * q * 8, &dxi));
+    GPX_TRY(sc.get(B * 8, &dcost));
+    GPX_TRY(sc.get(ngroups * 8, &part_c));
+    GPX_TRY(sc.get(ngroups * 8, &part_i));
+    GPX_TRY(sc.get(ngroups * 4, &dbad));
+    GPX_TRY(sc.get(8, &best_c));
+    GPX_TRY(sc.get(8, &best_i));
+    if (dbg) {
+      GPX_TRY(sc.get(B * q * q * 8, &dC));
+      GPX_TRY(sc.get(B * q * q * 8, &dF));
+    }
+    GPX_HIP(hipMemcpyAsync(dxi, xi, (size_t)(S * q * 8), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+  }
+  // the chunk of nb batches from batch b0: W (and Wa on a VFE model: the signed Gram) with n rows used and row stride ldw
+  template <bool VFE>
+  int launch(gpx_ctx* ctx, const KParams& kp, const double* W, const double* Wa, int64_t ldw, int64_t n, const double* Zc,
+             const double* pmean, int64_t nb, int64_t b0, double fBest, double nugget) {
+    const int64_t groups = (nb + pl.G - 1) / pl.G;
 #define GPX_QEI(QM_)                                                                                                            \
-  hipLaunchKernelGGL((qei_kernel<QM_>), dim3((unsigned)groups), dim3(256), 0, ctx->stream, kp, Wsol, ldb, n, Zc,                \
-                     (const double*)pmean, (int)q, pl, nb, b0, (const double*)dxi, S, fBest, nugget, dcost, part_c + g0,        \
-                     part_i + g0, dbad + g0, dC, dF)
+  hipLaunchKernelGGL((qei_kernel<QM_, VFE>), dim3((unsigned)groups), dim3(256), 0, ctx->stream, kp, W, Wa, ldw, n, Zc, pmean,   \
+                     (int)q, pl, nb, b0, (const double*)dxi, S, fBest, nugget, dcost, part_c + g0, part_i + g0, dbad + g0, dC, dF)
     if (q <= 1) GPX_QEI(1);
     else if (q <= 2) GPX_QEI(2);
     else if (q <= 4) GPX_QEI(4);
@@ -570,25 +597,53 @@ int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
 #undef GPX_QEI
     GPX_HIP(hipGetLastError());
     g0 += groups;
+    return 0;
   }
-  if (best || best_cost) {
-    GPX_TRY(launch_acq_argmin(ctx, part_c, part_i, g0, best_c, best_i));
-    if (best) GPX_HIP(hipMemcpyAsync(best, best_i, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, best_c, 8, hipMemcpyDeviceToHost, ctx->stream));
+  int finish(gpx_ctx* ctx, double* cost_host, int64_t* best, double* best_cost, int64_t* n_bad, double* dbg_C, double* dbg_F) {
+    if (best || best_cost) {
+      GPX_TRY(launch_acq_argmin(ctx, part_c, part_i, g0, best_c, best_i));
+      if (best) GPX_HIP(hipMemcpyAsync(best, best_i, 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (best_cost) GPX_HIP(hipMemcpyAsync(best_cost, best_c, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, dcost, (size_t)B * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (dbg_C) {
+      GPX_HIP(hipMemcpyAsync(dbg_C, dC, (size_t)(B * q * q * 8), hipMemcpyDeviceToHost, ctx->stream));
+      GPX_HIP(hipMemcpyAsync(dbg_F, dF, (size_t)(B * q * q * 8), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (n_bad) {
+      std::vector<int> hbad((size_t)g0, 0);
+      GPX_HIP(hipMemcpyAsync(hbad.data(), dbad, (size_t)g0 * 4, hipMemcpyDeviceToHost, ctx->stream));
+      GPX_HIP(hipStreamSynchronize(ctx->stream));
+      int64_t s = 0;
+      for (int64_t g = 0; g < g0; ++g) s += hbad[(size_t)g];
+      *n_bad = s;
+    }
+    return 0;
   }
-  if (cost_host) GPX_HIP(hipMemcpyAsync(cost_host, dcost, (size_t)B * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (dbg_C) {
-    GPX_HIP(hipMemcpyAsync(dbg_C, dC, (size_t)(B * q * q * 8), hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipMemcpyAsync(dbg_F, dF, (size_t)(B * q * q * 8), hipMemcpyDeviceToHost, ctx->stream));
+};
+
+// Shared body of gpx_acq_qei and gpx_dbg_qei_blocks (dbg_*: host B x q, B x q x q, B x q x q; all three or none).
+int qei_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Zb, int64_t q,
+             const double* xi, int64_t S, double fBest, double nugget, double* cost_host, int64_t* best, double* best_cost,
+             int64_t* n_bad, double* dbg_mean, double* dbg_C, double* dbg_F) {
+  const int64_t n = L->rows, np = L->prows, B = Zb->rows / q, d = kp.d;
+  QeiRun r(np, q, B, S);
+  PosteriorWork w(np, r.mc_alloc(), true);
+  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
+  GPX_TRY(w.take(sc, true, true));
+  GPX_TRY(r.take(ctx, sc, xi, dbg_C != nullptr));
+  GPX_TRY(w.upload_alpha(ctx, alpha, n));
+  for (int64_t b0 = 0; b0 < B; b0 += r.bc) {
+    const int64_t nb = (B - b0) < r.bc ? (B - b0) : r.bc, mc = nb * q;
+    const int64_t ldb = gpx_skew_ld(gpx_round_up(mc, GPX_TILE));
+    const double* Zc = Zb->p + b0 * q * d;
+    // gpx_posterior's own per-chunk step: the means are GP.evaluate's, W the solve every variance comes from
+    GPX_TRY(w.run(ctx, kp, L, X, Zc, mc, dbg_mean ? dbg_mean + b0 * q : nullptr));
+    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nb * ((double)n * (double)(q * (q + 1)) + (double)S * (double)(q * (q + 1))),
+                 8.0 * (double)n * (double)mc);
+    GPX_TRY(r.launch<false>(ctx, kp, w.solution(), nullptr, ldb, n, Zc, w.mean, nb, b0, fBest, nugget));
   }
-  if (n_bad) {
-    GPX_HIP(hipMemcpyAsync(hbad.data(), dbad, (size_t)g0 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    GPX_HIP(hipStreamSynchronize(ctx->stream));
-    int64_t s = 0;
-    for (int64_t g = 0; g < g0; ++g) s += hbad[(size_t)g];
-    *n_bad = s;
-  }
-  return 0;
+  return r.finish(ctx, cost_host, best, best_cost, n_bad, dbg_C, dbg_F);
 }
 
 int qei_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
@@ -647,6 +702,38 @@ int vfe_psampler_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, 
   GPX_TRY(psampler_factor(ctx, ps.get(), sc, nugget, true));
   *out = ps.release();
   return 0;
+}
+
+// The body of gpx_vfe_acq_qei and gpx_dbg_vfe_qei_blocks (dbg_*: all three or none), qei_impl on a VFE model: the means and both
+// solutions come from vfe_posterior_chunk (gpx_vfe_posterior's bits), chunked over whole batches under gpx_eval_chunk(nup), and
+// qei_kernel<.., true> forms C_b = (k - Wu^T Wu) + Wa^T Wa from the nu used rows of each.  Wa has a block of its own: from the order
+// at which the solves run out of place both would land in the one buffer and only the La solution would survive.
+int vfe_qei_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q, const double* xi,
+                 int64_t nS, double fBest, double nugget, double* cost_host, int64_t* best, double* best_cost, int64_t* n_bad,
+                 double* dbg_mean, double* dbg_C, double* dbg_F) {
+  FitcView v;
+  fitc_view(f, &v);
+  KParams kpz = *v.kp;   // re-centred on S and the WHOLE of Zb: the chunking cannot move a fill
+  GPX_TRY(gpx_kparams_sets(ctx, &kpz, S, Zb));
+  const int64_t nu = v.nu, B = Zb->rows / q, d = kpz.d;
+  QeiRun r(v.nup, q, B, nS);
+  VfePosteriorWork w(v.nup, r.mc_alloc(), true);
+  Scratch sc(ctx);   // its scope exit is the synchronisation the host results wait for
+  GPX_TRY(w.take(sc, true));
+  if (w.oop()) GPX_TRY(sc.get(w.bytesB, &w.Wa));
+  GPX_TRY(r.take(ctx, sc, xi, dbg_C != nullptr));
+  GPX_TRY(w.beta(ctx, f, coeff, sc));
+  for (int64_t b0 = 0; b0 < B; b0 += r.bc) {
+    const int64_t nb = (B - b0) < r.bc ? (B - b0) : r.bc, mc = nb * q;
+    const int64_t ldb = gpx_skew_ld(gpx_round_up(mc, GPX_TILE));
+    const double* Zc = Zb->p + b0 * q * d;
+    GPX_TRY(w.run(ctx, f, kpz, S, Zc, mc));
+    if (dbg_mean) GPX_HIP(hipMemcpyAsync(dbg_mean + b0 * q, w.pm, (size_t)mc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    ProfScope ps(ctx, GPX_PROF_GREEDY, (double)nb * (2.0 * (double)nu + (double)nS) * (double)(q * (q + 1)),
+                 8.0 * 2.0 * (double)nu * (double)mc);
+    GPX_TRY(r.launch<true>(ctx, kpz, w.solU(), w.solA(), ldb, nu, Zc, w.pm, nb, b0, fBest, nugget));
+  }
+  return r.finish(ctx, cost_host, best, best_cost, n_bad, dbg_C, dbg_F);
 }
 
 extern "C" {

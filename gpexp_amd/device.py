@@ -550,6 +550,31 @@ class VfeModel(FitcModel):
         check(rc)
         return PosteriorSampler.adopt(self.ctx, h, Z.shape[0], nugget)
 
+    def acq_qei(self, coeff, Zb, q, xi, fBest, nugget, want_costs=True):
+        """Monte-Carlo joint expected improvement of the B batches of q consecutive rows of Zb on the (S, q) base samples xi, on
+        the variational posterior (gpx_vfe_acq_qei), coeff = alpha from `solve`: what `acq_qei` returns -- (first arg-min among the
+        non-NaN costs or -1, its cost, costs (B,) or None, batches whose covariance did not factor)."""
+        xi = as_f64(xi)
+        assert xi.ndim == 2 and xi.shape[1] == int(q), "base samples are (S, q)"
+        nb = Zb.shape[0] // max(int(q), 1)
+        costs = np.empty(nb) if want_costs else None
+        best, best_cost, nbad = c_i64(), C.c_double(), c_i64()
+        co = as_f64(coeff)
+        check(self.ctx.lib.gpx_vfe_acq_qei(self.ctx.h, self.h, self.S.h, dptr(co), Zb.h, int(q), dptr(xi), xi.shape[0],
+                                           float(fBest), float(nugget), dptr(costs), C.byref(best), C.byref(best_cost),
+                                           C.byref(nbad)))
+        return best.value, best_cost.value, costs, nbad.value
+
+    def dbg_qei_blocks(self, coeff, Zb, q, nugget):
+        """(means (B, q), C_b (B, q, q), F_b (B, q, q)) of gpx_vfe_acq_qei's kernel (test hook, gpx_dbg_vfe_qei_blocks)."""
+        q = int(q)
+        nb = Zb.shape[0] // q
+        mean, Cb, Fb = np.empty((nb, q)), np.empty((nb, q, q)), np.empty((nb, q, q))
+        co = as_f64(coeff)
+        check(self.ctx.lib.gpx_dbg_vfe_qei_blocks(self.ctx.h, self.h, self.S.h, dptr(co), Zb.h, q, float(nugget), dptr(mean),
+                                                  dptr(Cb), dptr(Fb)))
+        return mean, Cb, Fb
+
 
 class VfeDesign:
     """Device-resident state of IVAR design on a VFE model (gpx_vfe_design_*): chol(Quu), the Gram matrix of the Monte-Carlo points

@@ -917,9 +917,13 @@ class costFuncEI(_costFuncBO):
         return cost[0]
 
     # ---- joint (q-point) expected improvement by Monte Carlo ------------------------------------------------------------------
-    def _jointCall(self, batches, nSamples, baseSamples, jitter, name, want_costs):
+    def _jointCall(self, model, batches, nSamples, baseSamples, jitter, name, want_costs):
+        """The body of jointEI / bestJointBatch and of vfeJointEI / vfeBestJointBatch.  `model()` (`_jointDense`, `_jointVfe`)
+        returns (ready(name), the model's readiness rule, and call(ctx, spec, Zb, q, xi, fBest, nugget, want_costs=), its device
+        entry) -- the way _thompsonBatch takes the sampler's constructor."""
         gp = self.gaussianProcess
-        gp._sampling_ready(name)
+        ready, call = model()
+        ready(name)
         assert type(gp).gpPriorMean is _GP.gpPriorMean and "gpPriorMean" not in vars(gp), \
             "joint expected improvement assumes the base class's zero gpPriorMean"
         b = np.asarray(batches, dtype=float)
@@ -936,7 +940,16 @@ class costFuncEI(_costFuncBO):
         spec = gp.kernel._spec()
         Zb = _dev.points(ctx, b.reshape(nb * q, b.shape[2]))
         nugget = gp._jitter(ctx, spec, Zb, jitter, name)
-        return _dev.acq_qei(ctx, spec, gp._L, gp._X, gp.coeff, Zb, q, xi, self._fBest(), nugget, want_costs=want_costs)
+        return call(ctx, spec, Zb, q, xi, self._fBest(), nugget, want_costs=want_costs)
+
+    def _jointDense(self):
+        gp = self.gaussianProcess
+        return gp._sampling_ready, lambda ctx, spec, Zb, *a, **kw: _dev.acq_qei(ctx, spec, gp._L, gp._X, gp.coeff, Zb, *a, **kw)
+
+    def _jointVfe(self):
+        gp = self.gaussianProcess
+        return (lambda name: gp._vfe_sampling_ready(name, "jointEI"),
+                lambda ctx, spec, Zb, *a, **kw: gp._fitc.acq_qei(gp.coeff, Zb, *a, **kw))
 
     def jointEI(self, batches, nSamples=256, baseSamples=None, jitter=None):
         """(B,) joint expected improvement of B batches of q points, minimisation form like `evaluate` (gpx_acq_qei):
@@ -948,12 +961,12 @@ class costFuncEI(_costFuncBO):
         `batches`: (B, q, d) or one batch (q, d), q <= 32.  `jitter`: nugget on every batch's q x q posterior covariance (default
         1e-10 * max k(z, z)).  A batch whose covariance does not factor with it (two identical points and jitter=0) costs NaN.
         With q = 1 the cost tends to evaluateBatch's closed form as S grows.  Dense models only."""
-        return self._jointCall(batches, nSamples, baseSamples, jitter, "jointEI", True)[2]
+        return self._jointCall(self._jointDense, batches, nSamples, baseSamples, jitter, "jointEI", True)[2]
 
     def bestJointBatch(self, batches, nSamples=256, baseSamples=None, jitter=None):
         """(index, cost) of the batch with the lowest jointEI cost: the first minimum among the non-NaN costs, (-1, NaN) when every
         cost is NaN.  Arguments as jointEI; only the winner reaches the host."""
-        best, cost, _, _ = self._jointCall(batches, nSamples, baseSamples, jitter, "bestJointBatch", False)
+        best, cost, _, _ = self._jointCall(self._jointDense, batches, nSamples, baseSamples, jitter, "bestJointBatch", False)
         return best, cost
 
     def selectBatchJoint(self, candidates, nPoints, lies=("believer", "min", "max", "mean"), nSamples=256, baseSamples=None,
@@ -961,15 +974,43 @@ class costFuncEI(_costFuncBO):
         """The best of several greedy batches by their JOINT expected improvement: `selectBatch(candidates, nPoints, lie)` proposes
         one batch per entry of `lies`, one gpx_acq_qei call scores them all on common base samples, and the winner comes back as
         (indices (nPoints,) int64, its jointEI cost, its lie).  Arguments as selectBatch and jointEI."""
+        return self._selectBatchJoint(self.bestJointBatch, "selectBatchJoint", candidates, nPoints, lies, nSamples, baseSamples,
+                                      jitter)
+
+    def _selectBatchJoint(self, bestJointBatch, name, candidates, nPoints, lies, nSamples, baseSamples, jitter):
+        """The body of selectBatchJoint / vfeSelectBatchJoint; `bestJointBatch`: the scorer of the proposals."""
         lies = list(lies)
         if not lies:
-            raise ValueError("selectBatchJoint: needs at least one lie")
+            raise ValueError("%s: needs at least one lie" % name)
         candidates = np.asarray(candidates, dtype=float)
         picks = [self.selectBatch(candidates, nPoints, lie=lie)[0] for lie in lies]
-        best, cost = self.bestJointBatch(np.stack([candidates[idx] for idx in picks]), nSamples, baseSamples, jitter)
+        best, cost = bestJointBatch(np.stack([candidates[idx] for idx in picks]), nSamples, baseSamples, jitter)
         if best < 0:
-            raise _dev._lib.GpxError("selectBatchJoint: no proposed batch has a non-NaN joint cost (a larger jitter factors them)")
+            raise _dev._lib.GpxError("%s: no proposed batch has a non-NaN joint cost (a larger jitter factors them)" % name)
         return picks[best], cost, lies[best]
+
+    def vfeJointEI(self, batches, nSamples=256, baseSamples=None, jitter=None):
+        """jointEI on a VFE model (gpx_vfe_acq_qei): (B,) joint expected improvement of B batches of q points under the variational
+        posterior -- evaluate's means, and per batch the q x q block of vfePosteriorCovariance, (k - Wu^T Wu) + Wa^T Wa, formed in
+        the inducing space: O(nu q^2) a batch, whatever the training-set size.  Arguments, the common base samples, the jitter and
+        the NaN rule as jointEI.  Every kernel.  ValueError on a dense or FITC model and before train; under a multi-process
+        session the call runs replicated, and baseSamples=None raises ValueError there."""
+        return self._jointCall(self._jointVfe, batches, nSamples, baseSamples, jitter, "vfeJointEI", True)[2]
+
+    def vfeBestJointBatch(self, batches, nSamples=256, baseSamples=None, jitter=None):
+        """bestJointBatch on a VFE model: (index, cost) of the batch with the lowest vfeJointEI cost, the first minimum among the
+        non-NaN costs, (-1, NaN) when every cost is NaN; only the winner reaches the host."""
+        best, cost, _, _ = self._jointCall(self._jointVfe, batches, nSamples, baseSamples, jitter, "vfeBestJointBatch", False)
+        return best, cost
+
+    def vfeSelectBatchJoint(self, candidates, nPoints, lies=("believer", "min", "max", "mean"), nSamples=256, baseSamples=None,
+                            jitter=None):
+        """selectBatchJoint on a VFE model: `selectBatch` (gpx_vfe_acq_batch) proposes one batch per entry of `lies`, one
+        gpx_vfe_acq_qei call scores them on common base samples, and the winner comes back as (indices (nPoints,) int64, its
+        vfeJointEI cost, its lie)."""
+        self.gaussianProcess._vfe_sampling_ready("vfeSelectBatchJoint", "jointEI")
+        return self._selectBatchJoint(self.vfeBestJointBatch, "vfeSelectBatchJoint", candidates, nPoints, lies, nSamples,
+                                      baseSamples, jitter)
 
 
 def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rbounds=None, maxiter=50):

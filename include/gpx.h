@@ -583,13 +583,25 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
  *   gpx_psampler_create's own, and its tail with one addition: the residual max |Chat - F F^T|_ij / sqrt(Chat_ii Chat_jj) is
  *   measured on the device after the refinement step, and while it is above 4 (M + 1) u the step is repeated (four more times at
  *   most) -- many points on a line under a squared exponential need it; a covariance that does not is left with one step.
- *   gpx_psampler_draw, _argbest, _shape and _free serve the result.  Every kernel kind. */
+ *   gpx_psampler_draw, _argbest, _shape and _free serve the result.  Every kernel kind.
+ * gpx_vfe_acq_qei: gpx_acq_qei on the variational posterior: Monte-Carlo joint expected improvement of B batches of q points (Zb:
+ *   (B q) x d, consecutive q rows one batch; xi: host nS x q, common to all batches).  mu_b holds the bits gpx_vfe_posterior
+ *   returns; C_b = (k(z_i, z_j) - su_ij) + sa_ij with su = Wu_b^T Wu_b, sa = Wa_b^T Wa_b over the nu inducing rows, in the order of
+ *   gpx_vfe_posterior's variance and each sum by gpx_acq_qei's rule (row slices, one fma chain per slice in ascending row, slices
+ *   added in order); from the nugget on the kernel is gpx_acq_qei's: F_b = chol(C_b + nugget I), a pivot <= 0 gives cost NaN and is
+ *   counted in *n_bad, a point repeated bit for bit is certain to meet one when the nugget is 0.  cost, best, best_cost, n_bad:
+ *   nullable, as gpx_acq_qei; permuting the batches permutes the costs bit for bit, whatever the chunking (whole batches under
+ *   GPX_CROSS_BYTES).  A batch costs O(nu q^2).  q outside 1 .. GPX_QEI_MAX_Q, rows of Zb no positive multiple of q, nS < 1 and a
+ *   negative nugget are argument errors.  Every kernel kind. */
 int gpx_vfe_paths_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,
                          const double* phase, int64_t nfeat, const double* w, const double* eps_u, const double* xi_q,
                          int64_t nPaths, gpx_paths** out);
 int gpx_vfe_posterior_cov(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const gpx_mat* Z, double* cov);
 int gpx_vfe_psampler_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, double nugget,
                             gpx_psampler** out);
+int gpx_vfe_acq_qei(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q,
+                    const double* xi, int64_t nS, double fBest, double nugget, double* cost, int64_t* best, double* best_cost,
+                    int64_t* n_bad);
 
 /* ---- IVAR design on a VFE model, in the inducing space (none in the reference) -----------------------------------------------------
  * With k_u(.) = K(S, .), Quu = K(S,S) + noise I = Lu Lu^T and, for design points X, A = Quu + sum_i k_u(x_i) k_u(x_i)^T / noise =

@@ -97,6 +97,11 @@ int gpx_dbg_greedy_var_scores(gpx_ctx* ctx, int kind, int d, const double* hyp, 
 int gpx_dbg_qei_blocks(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
                        const double* alpha, const gpx_mat* Zb, int64_t q, double nugget, double* mean, double* Cb, double* Fb);
 
+/* The same three blocks of gpx_vfe_acq_qei's kernel, by its own launches with one zero base sample: Cb = (k - Wu^T Wu) + Wa^T Wa of
+   every batch before the nugget.  tests/test_gpu_vfe_qei.py. */
+int gpx_dbg_vfe_qei_blocks(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Zb, int64_t q,
+                           double nugget, double* mean, double* Cb, double* Fb);
+
 /* The cost epilogue of gpx_acq / gpx_vfe_acq and its arg-min alone, by their own launches, on host vectors: mean[m] and the SIGNED
    variances var[m] (any doubles: negative, zero, infinite, NaN).  The epilogue runs in chunks of `chunk` candidates (a multiple of
    128; 0: one launch), then the arg-min over all partials.  cost (host m), coef (host 2m, nullable: (a, b) = (dA/dmu, dA/dvar) per

@@ -3,13 +3,13 @@
 entry point with its size, best-of-3 time, the algorithmic work and the achieved rate against the roof that bounds it.
 Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel table (profiles/r03_frows_kernel_stats.csv).
 
-    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo,vfedesign,sample,qei] [--kernel se,matern52] [--out FILE]
+    python scripts/bench_frows.py [--quick] [--only f1,design,mi,fitc,refit,f3,acq,loo,vfedesign,sample,qei,vfeqei] [--kernel se,matern52] [--out FILE]
 
 --kernel: the kernels the `f1` and `design` entries are timed with, one after the other in this process (se, matern32,
 matern52; default se) -- the other entries keep their own kernels.
 --out: the `loo` section also appends its lines to this file (profiles/loo_frows.jsonl), the `fitc` section its two
 leave-one-out lines (profiles/fitc_loo_frows.jsonl).
---sample-out: where the `sample` and `qei` sections append their lines (default profiles/sample_qei_frows.jsonl).
+--sample-out: where the `sample`, `qei` and `vfeqei` sections append their lines (default profiles/sample_qei_frows.jsonl).
 --vfe-out: where the `fitc` section appends its gpx_vfe_* lines (default profiles/vfe_frows.jsonl).
 """
 import json
@@ -601,7 +601,7 @@ def sample_report(line):
         f.write(json.dumps(line) + "\n")
 
 
-if want("sample") or want("qei"):
+if want("sample") or want("qei") or want("vfeqei"):
     from gpExp.kernels import KernelIsoMatern
     from gpExp.gp import GP
     from gpExp.experimentalDesign import costFuncEI
@@ -666,3 +666,44 @@ if want("qei"):
     sample_report(dict(entry="host path per batch: evaluate(compvar=2) + NumPy", size=dict(size, B=nbh), **spread(th),
                        note="%d batches timed, one gpx_posterior_cov call each; scaled to B = %d: %.1f ms (median)"
                             % (nbh, Bq, 1e3 * float(np.median(th)) * Bq / nbh)))
+
+# ---- vfeqei: Monte-Carlo q-EI on a VFE model (gpx_vfe_acq_qei) beside the dense jointEI on the same data, batches and base samples,
+# and beside the host route a user had before it: vfePosteriorCovariance per batch, NumPy Cholesky, the sample average
+if want("vfeqei"):
+    Bv, qv, Sv = (512, 8, 256) if quick else (4096, 8, 256)
+    np.random.seed(7)                                   # the inducing points are drawn with np.random.permutation
+    cfv = costFuncEI(GP(KernelIsoMatern(1.5, 1.0, 8, nu=2.5), 1e-2, FITC=0.125, sparse="vfe"), Xs, ys, 2, _Space8())
+    gpv = cfv.gaussianProcess
+    Zv8 = rs.uniform(-1, 1, (Bv, qv, 8))
+    xiv = rs.standard_normal((Sv, qv))
+    fbv = float(np.max(ys))
+
+    def dev_vfeqei():
+        return cfv.vfeJointEI(Zv8, baseSamples=xiv, jitter=1e-10)
+
+    def dev_denseqei():
+        return cfs.jointEI(Zv8, baseSamples=xiv, jitter=1e-10)
+
+    def host_vfeqei(nb):
+        out = []
+        for b in range(nb):
+            mean, cov = gpv.evaluate(Zv8[b]), gpv.vfePosteriorCovariance(Zv8[b])
+            F = np.linalg.cholesky(cov + 1e-10 * np.eye(qv))
+            out.append(-np.mean(np.maximum(fbv - np.min(mean[None, :] + xiv @ F.T, axis=1), 0.0)))
+        return np.array(out)
+
+    nbv = 16                                    # the host loop is timed on 16 batches and scaled: two device calls per batch
+    cv, ch = dev_vfeqei(), host_vfeqei(2)
+    dev_denseqei()
+    tv, tdn = alternate(dev_vfeqei, dev_denseqei, reps)
+    tv2, thv = alternate(dev_vfeqei, lambda: host_vfeqei(nbv), reps)
+    size = dict(N=Ns, nu=int(gpv.fitcnodes.shape[0]), d=8, B=Bv, q=qv, S=Sv, kernel="Matern-5/2")
+    sample_report(dict(entry="gpx_vfe_acq_qei (vfeJointEI)", size=size, **spread(tv + tv2),
+                       note="vfe_posterior_chunk over all B q points + one kernel: the signed Gram (k - Wu^T Wu) + Wa^T Wa, chol in LDS, "
+                            "S samples per batch; against the host route on the first two batches: max |difference| %.2e"
+                            % float(np.max(np.abs(cv[:2] - ch)))))
+    sample_report(dict(entry="gpx_acq_qei (jointEI), dense model on the same data, batches and base samples", size=dict(size, nu=None),
+                       **spread(tdn), note="alternated with the line above"))
+    sample_report(dict(entry="host path per batch: evaluate + vfePosteriorCovariance + NumPy", size=dict(size, B=nbv), **spread(thv),
+                       note="%d batches timed, one gpx_vfe_posterior and one gpx_vfe_posterior_cov call each; scaled to B = %d: %.1f ms "
+                            "(median)" % (nbv, Bv, 1e3 * float(np.median(thv)) * Bv / nbv)))
