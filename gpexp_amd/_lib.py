@@ -66,6 +66,10 @@ _SIGS = {
     "gpx_vfe_acq_grad": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, c_dp, c_dp]),
     "gpx_vfe_acq_batch": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, c_i64, c_ip,
                                     c_dp, c_dp, c_dp]),
+    "gpx_vfe_acq_mes": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, C.c_int, c_dp, c_ip, c_dp]),
+    "gpx_vfe_acq_mes_grad": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, C.c_int, c_dp, c_dp]),
+    "gpx_vfe_acq_mes_batch": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, C.c_int, C.c_int, C.c_double, c_i64, c_ip, c_dp,
+                                        c_dp, c_dp]),
     "gpx_vfe_paths_create": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp, c_dp, c_i64, C.POINTER(c_vp)]),
     "gpx_vfe_posterior_cov": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_dp]),
     "gpx_vfe_psampler_create": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_vp, C.c_double, C.POINTER(c_vp)]),
@@ -97,6 +101,10 @@ _SIGS = {
     "gpx_acq_grad": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_int, C.c_double, c_dp, c_dp]),
     "gpx_acq_batch": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_double, C.c_int, C.c_double,
                                 C.c_int, C.c_int, C.c_double, c_i64, c_ip, c_dp, c_dp, c_dp]),
+    "gpx_acq_mes": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, C.c_int, c_dp, c_ip, c_dp]),
+    "gpx_acq_mes_grad": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, C.c_int, c_dp, c_dp]),
+    "gpx_acq_mes_batch": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_double, c_dp, c_i64, C.c_int,
+                                    C.c_int, C.c_double, c_i64, c_ip, c_dp, c_dp, c_dp]),
     "gpx_psampler_create": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_vp, c_dp, c_vp, C.c_double, C.POINTER(c_vp)]),
     "gpx_psampler_draw": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_dp]),
     "gpx_psampler_argbest": (C.c_int, [c_vp, c_vp, c_dp, c_i64, C.c_int, c_ip, c_dp, c_dp]),
@@ -225,6 +233,7 @@ _SIGS = {
     "gpx_dbg_greedy_var_scores": (C.c_int, [c_vp, C.c_int, C.c_int, c_dp, C.c_int, c_vp, c_ip, c_i64, c_dp]),
     "gpx_dbg_acq_epilogue": (C.c_int, [c_vp, C.c_int, C.c_double, c_dp, c_dp, c_i64, c_i64, c_dp, c_dp, C.POINTER(c_i64),
                                        c_dp]),
+    "gpx_dbg_acq_mes_epilogue": (C.c_int, [c_vp, c_dp, c_i64, C.c_int, c_dp, c_dp, c_i64, c_i64, c_dp, c_dp, C.POINTER(c_i64), c_dp]),
 }
 
 _lib = None

@@ -71,10 +71,96 @@ __device__ __forceinline__ double acq_cost(int acq, double param, double mu, dou
   return c;
 }
 
+// ---- max-value entropy search (gpx_acq_mes; Wang & Jegelka 2017) -----------------------------------------------------------------
+// K samples y*_k of the optimum VALUE (sign = +1: sampled minima, gamma_k = (mu - y*_k) / s; sign = -1: sampled maxima,
+// gamma_k = (y*_k - mu) / s), lambda = phi / Phi:
+//     h(gamma)  = gamma lambda / 2 - log Phi(gamma)            h'(gamma) = -(lambda / 2) (1 + gamma (gamma + lambda))
+//     A = -(1/K) sum_k h(gamma_k)      a = dA/dmu = -(sign / (K s)) sum_k h'      b = dA/dvar = (sgn(var) / (2 K s^2)) sum_k h' gamma_k
+// summed in the order k = 0 .. K-1.  Composed from erfc, exp and log, h loses the digits of two terms of size gamma^2 / 2 that
+// cancel and h' those of 1 + gamma (gamma + lambda) -> 2 / gamma^2, and both are NaN below gamma = -38.5 where Phi underflows.
+// With t = -gamma / sqrt 2 >= MES_T0 the continued fraction
+//     1 / (sqrt(pi) erfcx(t)) = t + (1/2) / (t + 1 / (t + (3/2) / (t + ..)))  =  t + D,   D = (1/2) / (t + C2),
+//     C2 = 1 / (t + (3/2) / (t + 2 / (t + ..)))
+// gives lambda = sqrt 2 (t + D), h = -t D + log(2 sqrt(pi) (t + D)) with t D = (1 - w) / 2, and 1 + gamma (gamma + lambda) = w =
+// C2 / (t + C2): nothing cancels, no exponential is taken, and |gamma| = 1e150 is served.  MES_CF_TERMS = the largest partial
+// numerator index kept (k / 2, k = 3 .. MES_CF_TERMS below C2): the fewest for which the truncation of D and of C2 at t = MES_T0 is
+// below u / 8 (tests/test_acq_mes_host.py pins both against mpmath).  Below MES_T0 (and for gamma > 0, through the upper tail Q
+// and log1p(-Q)) the composition with an exactly formed gamma^2 / 2; its cancellation is bounded by that of gamma = -sqrt 2 MES_T0.
+// (T0 = 3 would need 41 terms only, but the composition below it then loses 2 T0^2 times the library's error in h and gamma^4 / 2
+// times in h': 2000 u in h' at gamma = -4 on the device.  DESIGN.md section 2, "Acquisition accuracy".)
+// Beyond gamma = 40 phi and Q are zero in every double: h = h' = 0 (the formulas' own values, without inf * 0).
+constexpr double MES_T0 = 2.0;
+constexpr int MES_CF_TERMS = 73;
+
+__device__ __forceinline__ void mes_h(double g, double* h_out, double* hp_out) {
+  const double t = -g * M_SQRT1_2;
+  double h, hp;
+  if (t >= MES_T0) {
+    double f = t;
+    for (int k = MES_CF_TERMS; k >= 3; --k) f = t + (0.5 * k) / f;
+    const double C2 = 1.0 / f, den = t + C2;
+    const double w = C2 / den, td = t + 0.5 / den;
+    h = log(3.54490770181103205460 * td) - 0.5 * (1.0 - w);   // 2 sqrt(pi)
+    hp = -(M_SQRT1_2 * td) * w;
+  } else if (g <= 40.0) {
+    const double p = g * g, e = fma(g, g, -p);                 // gamma^2 = p + e exactly
+    const double E = exp(-0.5 * p);
+    const double phi = fma(-0.5 * e, E, E) * 0.39894228040143267794;   // 1 / sqrt(2 pi)
+    const double Q = 0.5 * erfc(fabs(g) * M_SQRT1_2);          // the tail beyond |gamma|
+    double lam;
+    if (g <= 0.0) {
+      lam = phi / Q;
+      h = 0.5 * g * lam - log(Q);
+    } else {
+      lam = phi / (1.0 - Q);
+      h = 0.5 * g * lam - log1p(-Q);
+    }
+    hp = -0.5 * lam * (1.0 + g * (g + lam));
+  } else if (g > 40.0) {
+    h = 0.0;
+    hp = 0.0;
+  } else {
+    h = hp = __builtin_nan("");
+  }
+  *h_out = h;
+  *hp_out = hp;
+}
+
+// the y* of a MES call on the device (K doubles), beside the scalar `param` of the three closed forms; y == NULL: not a MES call
+struct MesArg {
+  const double* y = nullptr;
+  int K = 0;
+  double sign = 1.0;
+};
+
+// acq_cost's counterpart: cost and (a, b) of one candidate from its posterior mean and SIGNED variance
+__device__ __forceinline__ double mes_cost(const MesArg& ms, double mu, double var, double* a_out, double* b_out) {
+  const double s = sqrt(fabs(var));
+  const double sg = var > 0.0 ? 1.0 : (var < 0.0 ? -1.0 : 0.0);
+  double sh = 0.0, shp = 0.0, shg = 0.0;
+  for (int k = 0; k < ms.K; ++k) {
+    const double g = (ms.sign > 0.0 ? mu - ms.y[k] : ms.y[k] - mu) / s;
+    double h, hp;
+    mes_h(g, &h, &hp);
+    sh += h;
+    shp += hp;
+    shg += hp * g;
+  }
+  const double Kd = (double)ms.K;
+  double a = -(ms.sign / (Kd * s)) * shp;
+  double b = (sg / (2.0 * Kd * s * s)) * shg;
+  if (var == 0.0) a = b = __builtin_nan("");
+  *a_out = a;
+  *b_out = b;
+  return -(sh / Kd);
+}
+
 // values epilogue of one chunk [j0, j0 + mc): var = kd - ssq (ssq == NULL: kd IS the signed variance -- the VFE predictor's), the
 // cost (written to cost[j0 + j]), the gradient coefficients (a, b) per candidate of the chunk (coef, nullable) and one arg-min
-// partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].
-__global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double param, const double* __restrict__ mean,
+// partial per block at part_*[j0 / ACQ_EPI + blockIdx.x].  MES: mes_cost on `ms` in place of acq_cost (the three closed forms never
+// enter it: their instantiation is the kernel as it was).
+template <bool MES>
+__global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double param, MesArg ms, const double* __restrict__ mean,
                                                                const double* __restrict__ kd, const double* __restrict__ ssq,
                                                                int64_t mc, int64_t j0, double* __restrict__ cost,
                                                                double* __restrict__ coef, double* __restrict__ part_c,
@@ -85,7 +171,8 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_epilogue_kernel(int acq, double p
   VI v{0.0, -1};
   if (j < mc) {
     double a, b;
-    const double c = acq_cost(acq, param, mean[j], ssq ? kd[j] - ssq[j] : kd[j], &a, &b);
+    const double var = ssq ? kd[j] - ssq[j] : kd[j];
+    const double c = MES ? mes_cost(ms, mean[j], var, &a, &b) : acq_cost(acq, param, mean[j], var, &a, &b);
     cost[j0 + j] = c;
     if (coef) {
       coef[2 * j] = a;
@@ -181,12 +268,24 @@ int launch_acq_grad(gpx_ctx* ctx, const KParams& kp, const double* X, int64_t n,
   return 0;
 }
 
+// the device copy of a call's y* (from its Scratch; the copy is queued: `spec->ystar` is the caller's and outlives the call)
+int mes_upload(gpx_ctx* ctx, Scratch& sc, const MesSpec* spec, MesArg* out) {
+  double* dy = nullptr;
+  GPX_TRY(sc.get(spec->K * 8, &dy));
+  GPX_HIP(hipMemcpyAsync(dy, spec->ystar, (size_t)spec->K * 8, hipMemcpyHostToDevice, ctx->stream));
+  out->y = dy;
+  out->K = (int)spec->K;
+  out->sign = (double)spec->sign;
+  return 0;
+}
+
 // The result side of the candidate-wise calls, dense (acq_impl) and VFE (vfe_acq_impl): the costs of all M candidates, one arg-min
 // partial per ACQ_EPI of them, the winner's slots and -- for a gradient -- the (a, b) of one chunk and the M x d result.
 struct AcqOut {
   int64_t M = 0, d = 0, nparts = 0;
   double *cost = nullptr, *part_c = nullptr, *best_c = nullptr, *coef = nullptr, *grad = nullptr;
   int64_t *part_i = nullptr, *best_i = nullptr;
+  MesArg mes;   // (set by mes_upload for acq == GPX_ACQ_MES)
 
   int take(Scratch& sc, int64_t M_, int64_t mc_alloc, int64_t d_, bool want_grad) {
     M = M_;
@@ -207,8 +306,13 @@ struct AcqOut {
   int epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* kd, const double* ssq, int64_t mc, int64_t j0,
                double prof_bytes) {
     ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, prof_bytes);
-    hipLaunchKernelGGL(acq_epilogue_kernel, dim3((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI)), dim3(ACQ_EPI), 0, ctx->stream, acq,
-                       param, mean, kd, ssq, mc, j0, cost, coef, part_c, part_i);
+    const dim3 grid((unsigned)((mc + ACQ_EPI - 1) / ACQ_EPI));
+    if (acq == GPX_ACQ_MES)
+      hipLaunchKernelGGL(acq_epilogue_kernel<true>, grid, dim3(ACQ_EPI), 0, ctx->stream, acq, param, mes, mean, kd, ssq, mc, j0, cost,
+                         coef, part_c, part_i);
+    else
+      hipLaunchKernelGGL(acq_epilogue_kernel<false>, grid, dim3(ACQ_EPI), 0, ctx->stream, acq, param, mes, mean, kd, ssq, mc, j0, cost,
+                         coef, part_c, part_i);
     GPX_HIP(hipGetLastError());
     return 0;
   }
@@ -230,7 +334,8 @@ struct AcqOut {
 
 // Shared body of gpx_acq / gpx_acq_grad.  cost_host (M), grad_host (M x d) nullable; best / best_cost nullable.
 int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Z,
-             int acq, double param, double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
+             int acq, double param, double* cost_host, int64_t* best, double* best_cost, double* grad_host,
+             const MesSpec* mes = nullptr) {
   const int64_t n = L->rows, np = L->prows, M = Z->rows, d = kp.d;
   const bool grad = grad_host != nullptr;
   const ChunkRange cr(M, gpx_eval_chunk(np));
@@ -243,6 +348,7 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
   if (grad && !w.oop()) GPX_TRY(sc.get(w.bytesB, &pBt));
   if (bytesT) GPX_TRY(sc.get(bytesT, &pT));
   GPX_TRY(out.take(sc, M, cr.mc_alloc, d, grad));
+  if (mes) GPX_TRY(mes_upload(ctx, sc, mes, &out.mes));
   GPX_TRY(w.upload_alpha(ctx, alpha, n));
   for (const ChunkRange::Step c : cr) {
     const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0;
@@ -265,9 +371,10 @@ int acq_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X
 
 // the acquisition entries' own checks in front of the shared prologue
 int acq_args(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
-             const gpx_mat* Z, int acq, KParams* kp) {
+             const gpx_mat* Z, int acq, KParams* kp, const MesSpec* mes = nullptr) {
   GPX_ARG(ctx && L && X && Z && alpha, "NULL argument");
-  GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
+  if (mes) GPX_TRY(mes_args(mes));   // (the gpx_acq_mes* entries: acq is theirs, GPX_ACQ_MES)
+  else GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
   return gpx_entry_args(ctx, kind, d, hyp, nhyp, L, X, Z, nullptr, "point sets must be unpadded (n x d)", kp);
 }
 
@@ -314,8 +421,9 @@ __global__ __launch_bounds__(256) void acq_pick_kernel(const double* __restrict_
 // W_C / U never enter a result.
 // VFE (gpx_vfe_acq_batch): hdot = Wa[:, s]^T Wa enters with the opposite sign and alone (no k(c_s, c_j): the observation acts through
 // the inducing variables), v holds t_j = |Wa[:, j]|^2 and the variance scored is rfix[j] + t_j.
-template <bool VFE>
-__global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq, const double* __restrict__ Cp, int64_t M,
+// MES: mes_cost on `ms` (the y* held fixed from pick to pick) in place of acq_cost, as in acq_epilogue_kernel.
+template <bool VFE, bool MES>
+__global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq, MesArg ms, const double* __restrict__ Cp, int64_t M,
                                                             int upd, int64_t s, int cur, const double* __restrict__ sc,
                                                             const double* __restrict__ uc, const double* __restrict__ hdot,
                                                             double* __restrict__ U, int64_t ldu, double* __restrict__ mu,
@@ -344,7 +452,8 @@ __global__ __launch_bounds__(ACQ_EPI) void acq_batch_kernel(KParams kp, int acq,
       U[(int64_t)cur * ldu + j] = u;
     }
     double a, b;
-    double c = acq_cost(acq, sc[SC_PARAM], m, VFE ? rfix[j] + var : var, &a, &b);
+    const double vs = VFE ? rfix[j] + var : var;
+    double c = MES ? mes_cost(ms, m, vs, &a, &b) : acq_cost(acq, sc[SC_PARAM], m, vs, &a, &b);
     if (mask[j]) c = __builtin_nan("");
     cost[j] = c;
     if (c == c) best = VI{c, j};
@@ -366,6 +475,7 @@ struct AcqBatchState {
   double *cost = nullptr, *part_c = nullptr, *best_c = nullptr, *sc = nullptr, *uc = nullptr, *w = nullptr;
   int64_t *part_i = nullptr, *best_i = nullptr;
   int* mask = nullptr;
+  MesArg mes;         // (set by mes_upload for acq == GPX_ACQ_MES)
   double sc0[SC_N];   // (lives as long as the call: the copy of the scalars is queued from it)
 
   // prows: the padded row count of W (np, or nup on a VFE model)
@@ -414,9 +524,14 @@ int acq_batch_picks(gpx_ctx* ctx, const KParams& kp, int acq, const gpx_mat* Cm,
   for (int64_t t = 0; t < q; ++t) {
     {
       ProfScope ps(ctx, GPX_PROF_GREEDY, 0.0, 8.0 * (double)M * (6.0 + (double)t));
-      hipLaunchKernelGGL(acq_batch_kernel<VFE>, gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, (const double*)Cm->p, M,
-                         t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)st.sc, (const double*)st.uc, (const double*)st.hd, st.U, Mp,
-                         st.mu, st.v, (const double*)st.rfix, (const int*)st.mask, st.cost, st.part_c, st.part_i);
+      if (acq == GPX_ACQ_MES)
+        hipLaunchKernelGGL((acq_batch_kernel<VFE, true>), gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, st.mes, (const double*)Cm->p,
+                           M, t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)st.sc, (const double*)st.uc, (const double*)st.hd, st.U,
+                           Mp, st.mu, st.v, (const double*)st.rfix, (const int*)st.mask, st.cost, st.part_c, st.part_i);
+      else
+        hipLaunchKernelGGL((acq_batch_kernel<VFE, false>), gEpi, dim3(ACQ_EPI), 0, ctx->stream, kp, acq, st.mes, (const double*)Cm->p,
+                           M, t > 0 ? 1 : 0, s, (int)(t - 1), (const double*)st.sc, (const double*)st.uc, (const double*)st.hd, st.U,
+                           Mp, st.mu, st.v, (const double*)st.rfix, (const int*)st.mask, st.cost, st.part_c, st.part_i);
       hipLaunchKernelGGL(acq_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)st.part_c,
                          (const int64_t*)st.part_i, st.nparts, st.best_c, st.best_i);
     }
@@ -446,7 +561,7 @@ int acq_batch_picks(gpx_ctx* ctx, const KParams& kp, int acq, const gpx_mat* Cm,
 
 int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_mat* X, const double* alpha, const gpx_mat* Cm,
                    double noise, int acq, double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx,
-                   double* out_cost, double* out_lie, double* all_costs) {
+                   double* out_cost, double* out_lie, double* all_costs, const MesSpec* mes = nullptr) {
   const int64_t n = L->rows, np = L->prows, M = Cm->rows, d = kp.d;
   const int64_t Mp = gpx_round_up(M, GPX_TILE), ld = gpx_skew_ld(Mp);
   // the solve of gpx_acq (chol_cross_solve), the cross matrix chunk by chunk into the resident W_C
@@ -460,6 +575,7 @@ int acq_batch_impl(gpx_ctx* ctx, const KParams& kp, const gpx_mat* L, const gpx_
   if (oop) GPX_TRY(sc.get(np * ldb * 8, &pB));
   GPX_TRY(gpx_upload_padded(ctx, sc, alpha, n, np, &pal));
   GPX_TRY(st.take(sc, M, np, q, false));
+  if (mes) GPX_TRY(mes_upload(ctx, sc, mes, &st.mes));
   GPX_TRY(st.init(ctx, param));
   // ---- set-up: the posterior pass with W kept.  Not gpx_posterior_chunk: the solve lands in the resident W_C with ITS row
   // stride, and the squares are reduced once over all of W_C (into hd).  Its own step rule, not ChunkRange's: the walk is over
@@ -490,6 +606,19 @@ int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i,
   return 0;
 }
 
+// (gpx_internal.h) the y* rules of the gpx_acq_mes* and gpx_vfe_acq_mes* entries
+int mes_args(const MesSpec* mes) {
+  GPX_ARG(mes->ystar != nullptr, "ystar is NULL");
+  GPX_ARG(mes->K >= 1 && mes->K <= GPX_MES_MAX_K, "K (the number of sampled optima in ystar) must be between 1 and GPX_MES_MAX_K");
+  GPX_ARG(mes->sign == 1 || mes->sign == -1, "sign must be +1 (ystar holds sampled minima) or -1 (sampled maxima)");
+  for (int64_t k = 0; k < mes->K; ++k)
+    if (!__builtin_isfinite(mes->ystar[k])) {
+      gpx_set_error("%s:%d bad argument: ystar[%lld] is not finite: every sampled optimum must be", __FILE__, __LINE__, (long long)k);
+      return -1;
+    }
+  return 0;
+}
+
 // ---- the same three calls on a VFE model (gpx_vfe_acq, gpx_vfe_acq_grad, gpx_vfe_acq_batch; argument checks: fitc.hip) -------------
 // Notation of fitc.hip: S the nu inducing points, Quu = K(S,S) + noise I = Lu Lu^T, A = Quu + Kuf Kfu / noise = La La^T,
 // beta_u = Quu^-1 Kuf alpha, k_u(z) = K(S, z);  mean = k_u^T beta_u,  var = k(z,z) - |Lu^-1 k_u|^2 + |La^-1 k_u|^2.
@@ -502,7 +631,7 @@ int launch_acq_argmin(gpx_ctx* ctx, const double* part_c, const int64_t* part_i,
 // candidate; chol_trsm_right_n at every order -- no branch of its own at order 4096), and acq_grad_kernel<.., TWO> reads both
 // rows and takes their difference in its one pass over the inducing points.
 int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
-                 double* cost_host, int64_t* best, double* best_cost, double* grad_host) {
+                 double* cost_host, int64_t* best, double* best_cost, double* grad_host, const MesSpec* mes) {
   FitcView fv;
   fitc_view(f, &fv);
   const int64_t nu = fv.nu, nup = fv.nup, M = Z->rows, d = fv.kp->d;
@@ -522,6 +651,7 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
     if (oop) w.Wa = T2;
   }
   GPX_TRY(out.take(sc, M, cr.mc_alloc, d, grad));
+  if (mes) GPX_TRY(mes_upload(ctx, sc, mes, &out.mes));
   GPX_TRY(w.beta(ctx, f, coeff, sc));   // (GPX_ACQ_VARIANCE: no coeff, no mean; its weight a is 0)
   for (const ChunkRange::Step c : cr) {
     const int64_t mc = c.mc, mcp = c.mcp, j0 = c.j0, ldb = gpx_skew_ld(mcp);
@@ -558,7 +688,7 @@ int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double
 // place it lands in the chunk's columns of Wa, which the La solve then overwrites).
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
                        double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
-                       double* out_lie, double* all_costs) {
+                       double* out_lie, double* all_costs, const MesSpec* mes) {
   FitcView fv;
   fitc_view(f, &fv);
   const int64_t nu = fv.nu, nup = fv.nup, M = Cm->rows, d = fv.kp->d;
@@ -574,6 +704,7 @@ int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const 
   GPX_TRY(sc.get(nup * ld * 8, &pW));
   GPX_TRY(sc.get(nup * ldb * 8, &pB));
   GPX_TRY(st.take(sc, M, nup, q, true));
+  if (mes) GPX_TRY(mes_upload(ctx, sc, mes, &st.mes));
   GPX_TRY(vfe_beta_u(ctx, f, coeff, sc, &bu));
   GPX_TRY(st.init(ctx, param));
   // ---- set-up: gpx_vfe_acq's chunks.  Not vfe_posterior_chunk: the La solve lands in the resident Wa with ITS row stride; the Lu
@@ -638,6 +769,48 @@ int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, co
                         all_costs);
 }
 
+// ---- max-value entropy search: the three calls above with mes_cost on the caller's K sampled optima in place of acq_cost ---------
+int gpx_acq_mes(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X, const double* alpha,
+                const gpx_mat* Z, const double* ystar, int64_t K, int sign, double* cost, int64_t* best, double* best_cost) {
+  const MesSpec mes{ystar, K, sign};
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, Z, GPX_ACQ_MES, &kp, &mes));
+  if (Z->rows == 0) {
+    if (best) *best = -1;
+    if (best_cost) *best_cost = __builtin_nan("");
+    return 0;
+  }
+  return acq_impl(ctx, kp, L, X, alpha, Z, GPX_ACQ_MES, 0.0, cost, best, best_cost, nullptr, &mes);
+}
+
+int gpx_acq_mes_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                     const double* alpha, const gpx_mat* Z, const double* ystar, int64_t K, int sign, double* cost, double* grad) {
+  GPX_ARG(grad != nullptr, "grad is NULL");
+  GPX_ARG(kind == GPX_K_SE || kind == GPX_K_MATERN32 || kind == GPX_K_MATERN52,
+          "acquisition gradients exist for the stationary kernels (SE, Matern 3/2, Matern 5/2) only: the Mehler kernel's "
+          "prior variance depends on the point");
+  const MesSpec mes{ystar, K, sign};
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, Z, GPX_ACQ_MES, &kp, &mes));
+  if (Z->rows == 0) return 0;
+  return acq_impl(ctx, kp, L, X, alpha, Z, GPX_ACQ_MES, 0.0, cost, nullptr, nullptr, grad, &mes);
+}
+
+int gpx_acq_mes_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                      const double* alpha, const gpx_mat* C, double noise, const double* ystar, int64_t K, int sign, int lie,
+                      double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs) {
+  GPX_ARG(out_idx != nullptr, "out_idx is NULL");
+  GPX_ARG(lie == GPX_LIE_BELIEVER || lie == GPX_LIE_CONSTANT, "lie must be GPX_LIE_BELIEVER or GPX_LIE_CONSTANT");
+  const MesSpec mes{ystar, K, sign};
+  KParams kp;
+  GPX_TRY(acq_args(ctx, kind, d, hyp, nhyp, L, X, alpha, C, GPX_ACQ_MES, &kp, &mes));
+  GPX_ARG(q >= 1, "need at least one pick");
+  GPX_ARG(q <= C->rows, "more picks than candidates");
+  GPX_ARG(noise >= 0.0, "noise variance must not be negative");
+  return acq_batch_impl(ctx, kp, L, X, alpha, C, noise, GPX_ACQ_MES, 0.0, 0, lie, lie_value, q, out_idx, out_cost, out_lie, all_costs,
+                        &mes);
+}
+
 }  // extern "C"
 
 // test hook (gpx_debug.h): AcqOut's epilogue chunk by chunk and its arg-min on host vectors of means and SIGNED variances (ssq ==
@@ -669,10 +842,12 @@ int dbg_band_intact(gpx_ctx* ctx, const void* p, int64_t count) {
 
 }  // namespace
 
-extern "C" int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* var, int64_t m,
-                                    int64_t chunk, double* cost, double* coef, int64_t* best, double* best_cost) {
+// the body of both hooks; mes != NULL: gpx_dbg_acq_mes_epilogue's (acq = GPX_ACQ_MES)
+static int dbg_acq_epilogue_impl(gpx_ctx* ctx, int acq, double param, const MesSpec* mes, const double* mean, const double* var,
+                                 int64_t m, int64_t chunk, double* cost, double* coef, int64_t* best, double* best_cost) {
   GPX_ARG(ctx && mean && var && cost && best && best_cost, "NULL argument");
-  GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
+  if (mes) GPX_TRY(mes_args(mes));
+  else GPX_ARG(acq == GPX_ACQ_UCB || acq == GPX_ACQ_PI || acq == GPX_ACQ_EI, "acq must be GPX_ACQ_UCB, GPX_ACQ_PI or GPX_ACQ_EI");
   GPX_ARG(m >= 1, "need at least one candidate");
   GPX_ARG(chunk >= 0 && chunk % ACQ_EPI == 0, "chunk must be 0 (one launch) or a multiple of 128");
   const int64_t step = chunk > 0 && chunk < m ? chunk : m;
@@ -689,6 +864,7 @@ extern "C" int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const d
   GPX_TRY(dbg_banded(ctx, sc, 1, &out.best_c));
   GPX_TRY(dbg_banded(ctx, sc, 1, &out.best_i));
   if (coef) GPX_TRY(dbg_banded(ctx, sc, 2 * step, &out.coef));
+  if (mes) GPX_TRY(mes_upload(ctx, sc, mes, &out.mes));
   GPX_HIP(hipMemcpyAsync(dmean, mean, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
   GPX_HIP(hipMemcpyAsync(dvar, var, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
   for (int64_t j0 = 0; j0 < m; j0 += step) {
@@ -704,4 +880,15 @@ extern "C" int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const d
   GPX_TRY(dbg_band_intact(ctx, out.best_i, 1));
   if (coef) GPX_TRY(dbg_band_intact(ctx, out.coef, 2 * step));
   return 0;
+}
+
+extern "C" int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* var, int64_t m,
+                                    int64_t chunk, double* cost, double* coef, int64_t* best, double* best_cost) {
+  return dbg_acq_epilogue_impl(ctx, acq, param, nullptr, mean, var, m, chunk, cost, coef, best, best_cost);
+}
+
+extern "C" int gpx_dbg_acq_mes_epilogue(gpx_ctx* ctx, const double* ystar, int64_t K, int sign, const double* mean, const double* var,
+                                        int64_t m, int64_t chunk, double* cost, double* coef, int64_t* best, double* best_cost) {
+  const MesSpec mes{ystar, K, sign};
+  return dbg_acq_epilogue_impl(ctx, GPX_ACQ_MES, 0.0, &mes, mean, var, m, chunk, cost, coef, best, best_cost);
 }

@@ -1339,6 +1339,53 @@ int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const d
                             all_costs);
 }
 
+// The same three with the MES cost on the caller's sampled optima (gpx_vfe_acq_mes*): vfe_acq_args' rules but for the cost kind,
+// then mes_args'
+static int vfe_acq_mes_args(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z,
+                            const MesSpec* mes, const char* what) {
+  GPX_ARG(ctx && f && S && Z && coeff, "NULL argument");
+  FITC_KIND(f, true, what, "the batched acquisition costs are offered on VFE models only");
+  GPX_TRY(mes_args(mes));
+  GPX_TRY(vfe_point_sets(f, S, Z));
+  return 0;
+}
+
+int gpx_vfe_acq_mes(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, const double* ystar,
+                    int64_t K, int sign, double* cost, int64_t* best, double* best_cost) {
+  const MesSpec mes{ystar, K, sign};
+  GPX_TRY(vfe_acq_mes_args(ctx, f, S, coeff, Z, &mes, "vfe_acq_mes"));
+  if (Z->rows == 0) {
+    if (best) *best = -1;
+    if (best_cost) *best_cost = __builtin_nan("");
+    return 0;
+  }
+  return vfe_acq_impl(ctx, f, S, coeff, Z, GPX_ACQ_MES, 0.0, cost, best, best_cost, nullptr, &mes);
+}
+
+int gpx_vfe_acq_mes_grad(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, const double* ystar,
+                         int64_t K, int sign, double* cost, double* grad) {
+  GPX_ARG(grad != nullptr, "grad is NULL");
+  const MesSpec mes{ystar, K, sign};
+  GPX_TRY(vfe_acq_mes_args(ctx, f, S, coeff, Z, &mes, "vfe_acq_mes_grad"));
+  FITC_ARG(f->kp.kind == GPX_K_SE || f->kp.kind == GPX_K_MATERN32 || f->kp.kind == GPX_K_MATERN52, "vfe_acq_mes_grad",
+           "acquisition gradients exist for the stationary kernels (SE, Matern 3/2, Matern 5/2) only: the Mehler kernel's "
+           "prior variance depends on the point");
+  if (Z->rows == 0) return 0;
+  return vfe_acq_impl(ctx, f, S, coeff, Z, GPX_ACQ_MES, 0.0, cost, nullptr, nullptr, grad, &mes);
+}
+
+int gpx_vfe_acq_mes_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* C,
+                          const double* ystar, int64_t K, int sign, int lie, double lie_value, int64_t q, int64_t* out_idx,
+                          double* out_cost, double* out_lie, double* all_costs) {
+  GPX_ARG(out_idx != nullptr, "out_idx is NULL");
+  GPX_ARG(lie == GPX_LIE_BELIEVER || lie == GPX_LIE_CONSTANT, "lie must be GPX_LIE_BELIEVER or GPX_LIE_CONSTANT");
+  const MesSpec mes{ystar, K, sign};
+  GPX_TRY(vfe_acq_mes_args(ctx, f, S, coeff, C, &mes, "vfe_acq_mes_batch"));
+  GPX_ARG(q >= 1, "need at least one pick");
+  GPX_ARG(q <= C->rows, "more picks than candidates");
+  return vfe_acq_batch_impl(ctx, f, S, coeff, C, GPX_ACQ_MES, 0.0, 0, lie, lie_value, q, out_idx, out_cost, out_lie, all_costs, &mes);
+}
+
 // Posterior sampling on a VFE model (bodies: paths.hip and sample.hip, beside the code they share with the dense samplers; the
 // argument checks are here, where the struct is)
 int gpx_vfe_paths_create(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,

@@ -508,11 +508,21 @@ int vfe_var_grad_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* X, const g
 // acq = GPX_ACQ_VARIANCE (internal, not in gpx.h): the "cost" is the signed variance itself, (a, b) = (0, 1), so the gradient is
 // d var(z)/dz (gpx_vfe_var_grad_newpt); coeff may then be NULL (beta_u = 0).
 #define GPX_ACQ_VARIANCE (-1)
+// acq = GPX_ACQ_MES (internal; the gpx_acq_mes* / gpx_vfe_acq_mes* entries' own): max-value entropy search on the K sampled optima
+// of `mes` (host memory, the caller's), which then stands beside the unused scalar `param`.  mes_args (acq.hip): 1 <= K <=
+// GPX_MES_MAX_K, every y* finite, sign +1 or -1 -- else an argument error that names what is wrong.
+#define GPX_ACQ_MES (-2)
+struct MesSpec {
+  const double* ystar;
+  int64_t K;
+  int sign;
+};
+int mes_args(const MesSpec* mes);
 int vfe_acq_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, int acq, double param,
-                 double* cost_host, int64_t* best, double* best_cost, double* grad_host);
+                 double* cost_host, int64_t* best, double* best_cost, double* grad_host, const MesSpec* mes = nullptr);
 int vfe_acq_batch_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Cm, int acq,
                        double param, int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost,
-                       double* out_lie, double* all_costs);
+                       double* out_lie, double* all_costs, const MesSpec* mes = nullptr);
 // paths.hip / sample.hip: the bodies of gpx_vfe_paths_create, gpx_vfe_posterior_cov and gpx_vfe_psampler_create, behind fitc.hip's
 // argument checks (a VFE model, its own S, unpadded Z of at least one row, a stationary kernel for the paths)
 int vfe_paths_create_impl(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const double* omega,

@@ -504,6 +504,40 @@ class VfeModel(FitcModel):
                                              dptr(cost), dptr(lies), dptr(allc)))
         return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
 
+    def acq_mes(self, coeff, Z, ystar, sign=1, want_costs=True):
+        """`acq` under the MES cost on the sampled optima `ystar` (gpx_vfe_acq_mes; the module's `acq_mes`)."""
+        costs = np.empty(Z.shape[0]) if want_costs else None
+        best, best_cost = c_i64(), C.c_double()
+        co = as_f64(coeff) if coeff is not None else None
+        ys, yp, K, sign = _mes_ystar(ystar, sign)
+        check(self.ctx.lib.gpx_vfe_acq_mes(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, yp, K, sign, dptr(costs), C.byref(best),
+                                           C.byref(best_cost)))
+        return best.value, best_cost.value, costs
+
+    def acq_mes_grad(self, coeff, Z, ystar, sign=1):
+        """`acq_grad` under the MES cost (gpx_vfe_acq_mes_grad); the costs hold `acq_mes`'s bits."""
+        m, d = Z.shape
+        costs = np.empty(m)
+        grad = np.empty((m, d))
+        co = as_f64(coeff) if coeff is not None else None
+        ys, yp, K, sign = _mes_ystar(ystar, sign)
+        check(self.ctx.lib.gpx_vfe_acq_mes_grad(self.ctx.h, self.h, self.S.h, dptr(co), Z.h, yp, K, sign, dptr(costs), dptr(grad)))
+        return costs, grad
+
+    def acq_mes_batch(self, coeff, Cpts, ystar, sign, lie, lie_value, q, want_all=False):
+        """`acq_batch` under the MES cost, ystar held fixed from pick to pick (gpx_vfe_acq_mes_batch)."""
+        q = int(q)
+        idx = np.empty(max(q, 0), dtype=np.int64)
+        cost = np.empty(max(q, 0))
+        lies = np.empty(max(q, 0))
+        allc = np.empty((max(q, 0), Cpts.shape[0])) if want_all else None
+        co = as_f64(coeff) if coeff is not None else None
+        ys, yp, K, sign = _mes_ystar(ystar, sign)
+        check(self.ctx.lib.gpx_vfe_acq_mes_batch(self.ctx.h, self.h, self.S.h, dptr(co), Cpts.h, yp, K, sign, int(lie),
+                                                 float(lie_value), q, idx.ctypes.data_as(_lib.c_ip), dptr(cost), dptr(lies),
+                                                 dptr(allc)))
+        return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
+
     def design_var_grad(self, spec, X, S, Z):
         """(N*d, M) matrix d var(z_m) / d X[k][l] of the variational variance (gpx_vfe_var_grad), in `var_grad`'s layout: TRUE
         derivatives, the inducing points held fixed.  `spec`, X, S = the kernel, nodes and inducing points of the model."""
@@ -777,6 +811,69 @@ def acq_batch(ctx, spec, L, X, alpha, C, noise, kind, param, track_best, lie, li
                                 int(bool(track_best)), int(lie), float(lie_value), q, idx.ctypes.data_as(_lib.c_ip),
                                 dptr(cost), dptr(lies), dptr(allc)))
     return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
+
+
+# ---- max-value entropy search (gpx_acq_mes*) -------------------------------------------------------------------------------------
+ACQ_MES = "mes"          # the cost kind the class layer dispatches on; its `param` is (ystar, sign)
+MES_MAX_K = 1024
+
+
+def _mes_ystar(ystar, sign):
+    """(ystar as float64 (K,), its pointer, K, sign) for the C calls; the library checks the values."""
+    ys = as_f64(np.ravel(ystar))
+    return ys, dptr(ys), int(ys.size), int(sign)
+
+
+def acq_mes(ctx, spec, L, X, alpha, Z, ystar, sign=1, want_costs=True):
+    """Max-value entropy search costs of the M candidates Z (gpx_acq_mes): `ystar` (K,) samples of the optimum VALUE -- minima with
+    sign = +1, maxima with sign = -1.  What `acq` returns."""
+    costs = np.empty(Z.shape[0]) if want_costs else None
+    best, best_cost = c_i64(), C.c_double()
+    al = as_f64(alpha)
+    ys, yp, K, sign = _mes_ystar(ystar, sign)
+    check(ctx.lib.gpx_acq_mes(ctx.h, *spec.args(), L.h, X.h, dptr(al), Z.h, yp, K, sign, dptr(costs), C.byref(best),
+                              C.byref(best_cost)))
+    return best.value, best_cost.value, costs
+
+
+def acq_mes_grad(ctx, spec, L, X, alpha, Z, ystar, sign=1):
+    """(costs (M,), d cost_m / d z_m (M, d)) of the M candidates Z (gpx_acq_mes_grad); the costs hold `acq_mes`'s bits."""
+    m, d = Z.shape
+    costs = np.empty(m)
+    grad = np.empty((m, d))
+    al = as_f64(alpha)
+    ys, yp, K, sign = _mes_ystar(ystar, sign)
+    check(ctx.lib.gpx_acq_mes_grad(ctx.h, *spec.args(), L.h, X.h, dptr(al), Z.h, yp, K, sign, dptr(costs), dptr(grad)))
+    return costs, grad
+
+
+def acq_mes_batch(ctx, spec, L, X, alpha, C_, noise, ystar, sign, lie, lie_value, q, want_all=False):
+    """q picks of batch acquisition under the MES cost (gpx_acq_mes_batch): `acq_batch`'s recurrence with ystar held fixed from pick
+    to pick.  What `acq_batch` returns."""
+    q = int(q)
+    idx = np.empty(max(q, 0), dtype=np.int64)
+    cost = np.empty(max(q, 0))
+    lies = np.empty(max(q, 0))
+    allc = np.empty((max(q, 0), C_.shape[0])) if want_all else None
+    al = as_f64(alpha)
+    ys, yp, K, sign = _mes_ystar(ystar, sign)
+    check(ctx.lib.gpx_acq_mes_batch(ctx.h, *spec.args(), L.h, X.h, dptr(al), C_.h, float(noise), yp, K, sign, int(lie),
+                                    float(lie_value), q, idx.ctypes.data_as(_lib.c_ip), dptr(cost), dptr(lies), dptr(allc)))
+    return (idx, cost, lies, allc) if want_all else (idx, cost, lies)
+
+
+def dbg_acq_mes_epilogue(ctx, ystar, sign, mean, var, chunk=0, want_coef=True):
+    """`dbg_acq_epilogue` for the MES cost (test hook, gpx_dbg_acq_mes_epilogue)."""
+    mean, var = as_f64(np.ravel(mean)), as_f64(np.ravel(var))
+    assert mean.shape == var.shape
+    m = mean.size
+    costs = np.empty(m)
+    coef = np.empty((m, 2)) if want_coef else None
+    best, best_cost = c_i64(), C.c_double()
+    ys, yp, K, sign = _mes_ystar(ystar, sign)
+    check(ctx.lib.gpx_dbg_acq_mes_epilogue(ctx.h, yp, K, sign, dptr(mean), dptr(var), m, int(chunk), dptr(costs), dptr(coef),
+                                           C.byref(best), C.byref(best_cost)))
+    return best.value, best_cost.value, costs, coef
 
 
 def _sampler_not_pd(pivot, nugget):

@@ -39,7 +39,7 @@ NLOPT = False
 __all__ = ["costFunctionBase", "costFunctionGP_IVAR", "costFunctionGP_MI", "ExperimentalDesign",
            "ExperimentalDesignDerivative", "performGreedyVarExperimentalDesign",
            "performGreedyMIExperimentalDesign", "greedyIVARStep", "performGreedyIVARExperimentalDesign", "costFuncGPUCbound",
-           "costFuncPI", "costFuncEI", "optimizeAcquisition", "costFunctionVFE_IVAR", "np"]
+           "costFuncPI", "costFuncEI", "optimizeAcquisition", "costFunctionVFE_IVAR", "costFuncMES", "np"]
 
 
 class costFunctionBase(object):
@@ -570,18 +570,31 @@ class _AcqCalls(object):
 
     def acq(self, Z, kind, param, want_costs=True):
         gp = self.gp
+        if kind == _dev.ACQ_MES:          # param = (yStar, sign): gpx_acq_mes / gpx_vfe_acq_mes
+            if self.vfe is not None:
+                return self.vfe.acq_mes(gp.coeff, Z, param[0], param[1], want_costs=want_costs)
+            return _dev.acq_mes(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, param[0], param[1], want_costs=want_costs)
         if self.vfe is not None:
             return self.vfe.acq(gp.coeff, Z, kind, param, want_costs=want_costs)
         return _dev.acq(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, kind, param, want_costs=want_costs)
 
     def acq_grad(self, Z, kind, param):
         gp = self.gp
+        if kind == _dev.ACQ_MES:
+            if self.vfe is not None:
+                return self.vfe.acq_mes_grad(gp.coeff, Z, param[0], param[1])
+            return _dev.acq_mes_grad(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, param[0], param[1])
         if self.vfe is not None:
             return self.vfe.acq_grad(gp.coeff, Z, kind, param)
         return _dev.acq_grad(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, Z, kind, param)
 
     def acq_batch(self, C, kind, param, track, lie, lieValue, q, want_all=False):
         gp = self.gp
+        if kind == _dev.ACQ_MES:          # (no track_best: the sampled optima stay fixed from pick to pick)
+            if self.vfe is not None:
+                return self.vfe.acq_mes_batch(gp.coeff, C, param[0], param[1], lie, lieValue, q, want_all=want_all)
+            return _dev.acq_mes_batch(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, C, float(gp.noise), param[0], param[1],
+                                      lie, lieValue, q, want_all=want_all)
         if self.vfe is not None:
             return self.vfe.acq_batch(gp.coeff, C, kind, param, track, lie, lieValue, q, want_all=want_all)
         return _dev.acq_batch(self.ctx, gp.kernel._spec(), gp._L, gp._X, gp.coeff, C, float(gp.noise), kind, param, track, lie,
@@ -1013,8 +1026,175 @@ class costFuncEI(_costFuncBO):
                                       baseSamples, jitter)
 
 
+_MES_T0, _MES_CF_TERMS = 2.0, 73      # acq.hip's MES_T0 / MES_CF_TERMS
+
+
+def mesEntropyTerm(gamma):
+    """h(gamma) = gamma lambda / 2 - log Phi(gamma), lambda = phi / Phi, in float64 for an array of gamma: the device's formulation
+    (acq.hip, mes_h) restated in NumPy -- the continued fraction of erfcx where -gamma / sqrt 2 >= 2, else the composition with an
+    exactly formed gamma^2 / 2 (through the upper tail and log1p for gamma > 0).  h(+inf) = 0, h(-inf) = +inf, NaN for NaN.
+    One of three hand-kept statements of the formulation -- mes_h on the device, this one, and tests/acq_mes_ref.terms_f64 -- each
+    with its own seam T0, term count and exact square; tests/test_acq_mes_host.py pins the constants and this function's values to
+    the other two.  Only h is formed here: `evaluate` needs no more, and the class has no host h' (gradients come from the
+    device, gpx_acq_mes_grad)."""
+    import math
+    erfc = np.vectorize(math.erfc, otypes=[float])      # (SciPy's erfc gives 0 beyond 26.6, where the C library's is a subnormal)
+    g = np.asarray(gamma, dtype=float)
+    with np.errstate(all="ignore"):
+        t = -g * np.sqrt(0.5)
+        cf = t >= _MES_T0
+        tt = np.where(cf, t, _MES_T0)
+        f = tt.copy()
+        for k in range(_MES_CF_TERMS, 2, -1):
+            f = tt + (0.5 * k) / f
+        C2 = 1.0 / f
+        den = tt + C2
+        h_cf = np.log(3.5449077018110320546 * (tt + 0.5 / den)) - 0.5 * (1.0 - C2 / den)
+        gm = np.where(cf | ~(g <= 40.0), 0.0, g)
+        p = gm * gm
+        # gamma^2 = p + e exactly (Dekker's product of the split halves)
+        c = 134217729.0 * gm
+        hi = c - (c - gm)
+        lo = gm - hi
+        e = ((hi * hi - p) + 2.0 * hi * lo) + lo * lo
+        E = np.exp(-0.5 * p)
+        phi = (E - 0.5 * e * E) * 0.3989422804014326779
+        Q = 0.5 * erfc(np.abs(gm) * np.sqrt(0.5))
+        neg = gm <= 0.0
+        lam = phi / np.where(neg, Q, 1.0 - Q)
+        h_c = 0.5 * gm * lam - np.where(neg, np.log(Q), np.log1p(-Q))
+        return np.where(cf, h_cf, np.where(g <= 40.0, h_c, np.where(g > 40.0, 0.0, np.nan)))
+
+
+def gumbelOptima(mean, std, uniforms, minimize=True):
+    """Samples of the optimum VALUE over a finite set by Wang & Jegelka's Gumbel approximation (host): the points' posterior means
+    and standard deviations (independent marginals), `uniforms` (K,) in (0, 1).  For a minimum, P(min_j f_j > y) = prod_j
+    Phi((mean_j - y) / std_j); its 25 / 50 / 75 % points are found by bisection on the sum of scipy.special.log_ndtr, a Gumbel
+    distribution is fitted to them (on -f), and it is sampled at the uniforms by its inverse: (K,) values.  minimize=False mirrors."""
+    from scipy.special import log_ndtr
+    m = np.asarray(mean, dtype=float).ravel()
+    s = np.asarray(std, dtype=float).ravel()
+    r = np.asarray(uniforms, dtype=float).ravel()
+    if m.size < 1 or m.shape != s.shape or not (np.all(np.isfinite(m)) and np.all(np.isfinite(s)) and np.all(s > 0)):
+        raise ValueError("gumbelOptima: needs finite means and positive finite standard deviations of the same length")
+    if r.size < 1 or not np.all((r > 0.0) & (r < 1.0)):
+        raise ValueError("gumbelOptima: uniforms must lie strictly between 0 and 1")
+    if minimize:
+        m = -m                                       # max(-f): P(max < z) = prod Phi((z - m_j) / s_j)
+
+    def logcdf(z):
+        return float(np.sum(log_ndtr((z - m) / s)))
+
+    def quantile(prob):
+        target = np.log(prob)
+        lo, hi = float(np.min(m - 5.0 * s)), float(np.max(m + 5.0 * s))
+        w = hi - lo
+        while logcdf(lo) > target:
+            lo -= w
+        while logcdf(hi) < target:
+            hi += w
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            if not lo < mid < hi:
+                break
+            if logcdf(mid) < target:
+                lo = mid
+            else:
+                hi = mid
+        return 0.5 * (lo + hi)
+
+    y1, y2, y3 = quantile(0.25), quantile(0.5), quantile(0.75)
+    b = (y1 - y3) / (np.log(np.log(4.0 / 3.0)) - np.log(np.log(4.0)))
+    a = y2 + b * np.log(np.log(2.0))
+    z = a - b * np.log(-np.log(r))
+    return -z if minimize else z
+
+
+class costFuncMES(_costFuncBO):
+    """Max-value entropy search (Wang & Jegelka 2017), minimisation form: with K samples y*_k of the global optimum VALUE,
+
+        cost = -(1/K) sum_k h(gamma_k),   h(gamma) = gamma lambda(gamma) / 2 - log Phi(gamma),   lambda = phi / Phi,
+
+    gamma_k = (mu - y*_k) / s when the y* are sampled minima (minimize=True), (y*_k - mu) / s for sampled maxima: the expected drop
+    in entropy of the candidate's predictive distribution once it is truncated at y*.  One posterior pass per call, like EI.
+
+    `yStar` (K,), K <= 1024, is given to the constructor, assigned, or drawn by `sampleOptima`; the batched calls raise ValueError
+    while it is None.  `evaluate` scores the last row of its argument through a single-row GP.evaluate and the float64 host
+    composition `mesEntropyTerm`; evaluateBatch, bestCandidate, evaluateBatchWithDerivative, derivativeBatch, derivative,
+    selectBatch (the sampled optima stay fixed from pick to pick) and optimizeAcquisition run on the device (gpx_acq_mes,
+    gpx_acq_mes_grad, gpx_acq_mes_batch and their gpx_vfe_ forms) on dense and VFE models.  A FITC model raises
+    NotImplementedError from the batched calls; gradients on a Mehler kernel raise the library's GpxError (an argument error of
+    gpx_acq_mes_grad, as for the other three costs).  Where the variance is exactly 0 and the mean lies on the optimum side of a
+    y*, the cost is -inf by the formula as written (include/gpx.h)."""
+
+    _acq = _dev.ACQ_MES
+
+    def __init__(self, gaussianProcess, xTrain, yTrain, nInputs, space, yStar=None, minimize=True, **kwargs):
+        super(costFuncMES, self).__init__(gaussianProcess, xTrain, yTrain, nInputs, space)
+        self.minimize = bool(minimize)
+        self.yStar = None if yStar is None else np.array(yStar, dtype=float).ravel()
+
+    def _sign(self):
+        return 1 if self.minimize else -1
+
+    def _param(self):
+        if self.yStar is None:
+            raise ValueError("costFuncMES: yStar is None -- give the sampled optima to the constructor or call sampleOptima first")
+        return (np.asarray(self.yStar, dtype=float).ravel(), self._sign())
+
+    def _trackBest(self):
+        return False
+
+    def evaluate(self, trainPoints):
+        yStar, sign = self._param()
+        predMean, predstd = self._posterior(trainPoints)
+        with np.errstate(all="ignore"):
+            gamma = sign * (float(np.ravel(predMean)[0]) - yStar) / float(np.ravel(predstd)[0])
+        h = mesEntropyTerm(gamma)
+        total = 0.0
+        for v in h:                       # (the device's order k = 0 .. K-1)
+            total += float(v)
+        return -(total / h.size)
+
+    def sampleOptima(self, candidates, nOptima=16, method="paths", nFeatures=1024, base=None, uniforms=None, polish=False,
+                     lbounds=None, rbounds=None, maxiter=50):
+        """Draw `nOptima` samples of the optimum value over the candidates, set `yStar` and return it (nOptima,).
+        method="paths": the `values` of thompsonPaths (vfeThompsonPaths on a VFE model) -- the optimum of every sampled posterior
+          path over the candidates, polished inside [lbounds, rbounds] when polish=True; `base`: the PathBase of the draws
+          (stationary kernels, scalar noise; None draws with NumPy, and raises ValueError under a multi-process session).
+        method="gumbel": Wang & Jegelka's approximation on the host (`gumbelOptima`) from the means and variances of ONE
+          GP.evaluate(candidates, compvar=1), sampled at `uniforms` (nOptima,) in (0, 1) (np.random.uniform when None; ValueError
+          under a multi-process session).  Serves every kernel and per-point noise.
+        minimize=False (the constructor's) samples maxima."""
+        K = int(nOptima)
+        if not 1 <= K <= _dev.MES_MAX_K:
+            raise ValueError("sampleOptima: nOptima must be in 1 .. %d, not %r" % (_dev.MES_MAX_K, nOptima))
+        if method == "paths":
+            gp = self.gaussianProcess
+            vfe = getattr(gp, "_fitc", None) is not None and gp._vfe()
+            draw = self.vfeThompsonPaths if vfe else self.thompsonPaths
+            values = draw(candidates, K, nFeatures=nFeatures, base=base, minimize=self.minimize, polish=polish, lbounds=lbounds,
+                          rbounds=rbounds, maxiter=maxiter)[1]
+        elif method == "gumbel":
+            if uniforms is None:
+                if _dist.session() is not None:
+                    raise ValueError("sampleOptima: under a multi-process session uniforms must be given (the call runs replicated "
+                                     "and every rank would draw its own)")
+                uniforms = np.random.uniform(size=K)
+            uniforms = np.asarray(uniforms, dtype=float).ravel()
+            if uniforms.shape != (K,):
+                raise ValueError("sampleOptima: uniforms must have shape (%d,), not %r" % (K, uniforms.shape))
+            candidates = self._thompsonCandidates(candidates)
+            mean, var = self.gaussianProcess.evaluate(candidates, compvar=1)
+            values = gumbelOptima(np.ravel(mean), np.sqrt(np.ravel(var)), uniforms, minimize=self.minimize)
+        else:
+            raise ValueError("sampleOptima: method must be 'paths' or 'gumbel', not %r" % (method,))
+        self.yStar = np.array(values, dtype=float).ravel()
+        return self.yStar
+
+
 def optimizeAcquisition(costFunction, candidates, nStarts=8, lbounds=None, rbounds=None, maxiter=50):
-    """Minimise a Bayesian-optimisation cost (costFuncGPUCbound / costFuncPI / costFuncEI) over a box: one discrete pass over the
+    """Minimise a Bayesian-optimisation cost (costFuncGPUCbound / costFuncPI / costFuncEI / costFuncMES) over a box: one discrete pass over the
     candidates on the device (gpx_acq), then SciPy L-BFGS-B from the `nStarts` best distinct candidates at once -- the objective is
     the SUM of the starts' costs over the stacked nStarts x d vector (separable), so every iteration is ONE gpx_acq_grad call.
     The box defaults to the candidates' bounding box; candidates outside it take no part.

@@ -241,6 +241,36 @@ int gpx_acq_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, co
                   int lie, double lie_value, int64_t q,
                   int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs);
 
+/* ---- max-value entropy search (MES; Wang & Jegelka 2017) ------------------------------------------------------------------------
+ * The three calls above for the information-theoretic cost: ystar (HOST, K doubles, 1 <= K <= GPX_MES_MAX_K, every one finite) holds
+ * K samples of the global optimum VALUE -- sampled minima with sign = +1, gamma_k = (mu - ystar_k) / s; sampled maxima with sign =
+ * -1, gamma_k = (ystar_k - mu) / s -- and a candidate is scored by the expected drop in entropy of its predictive distribution
+ * once truncated at ystar.  With s = sqrt(|var|), lambda = phi / Phi:
+ *     h(gamma)  = gamma lambda(gamma) / 2 - log Phi(gamma)     >= 0,  h(0) = log 2,  h -> 0 (gamma -> +inf),  h ~ log(-gamma) (-> -inf)
+ *     h'(gamma) = -(lambda / 2) (1 + gamma (gamma + lambda))   <= 0
+ *     cost = -(1/K) sum_k h(gamma_k)                            (summed in the order k = 0 .. K-1)
+ *     a = dcost/dmu = -(sign / (K s)) sum_k h'(gamma_k)         b = dcost/dvar = (sgn(var) / (2 K s^2)) sum_k h'(gamma_k) gamma_k
+ * h and h' are formed without cancellation for every finite gamma (a continued fraction of erfcx below gamma = -2 sqrt 2: acq.hip),
+ * gamma = +inf gives h = h' = 0, gamma = -inf gives h = +inf.  The formulas are evaluated as written where var == 0 exactly (an exact
+ * duplicate of a training point under zero noise): a candidate whose mean lies on the optimum side of some ystar_k (mu < ystar_k
+ * for sampled minima) then has gamma_k = -inf and takes cost -inf, so it WINS the arg-min (its a and b are NaN); with the mean on
+ * the other side of every ystar its cost is -0.  Mask such candidates beforehand if they are not wanted.  ystar NULL or with a non-finite entry, K out of range and sign other
+ * than +1 / -1 are argument errors that name what is wrong.
+ * gpx_acq_mes: every rule of gpx_acq (cost / best / best_cost nullable; the FIRST arg-min among the non-NaN costs, -1 / NaN when
+ *   there is none; bits independent of the chunking under GPX_CROSS_BYTES; every kernel kind).
+ * gpx_acq_mes_grad: gpx_acq_grad's rules (stationary kernels only; NaN rows where var == 0 exactly); cost holds gpx_acq_mes's bits.
+ * gpx_acq_mes_batch: gpx_acq_batch's recurrence with ystar held fixed from pick to pick (there is no track_best); row 0 of all_costs
+ *   holds gpx_acq_mes's bits; two runs agree bit for bit. */
+#define GPX_MES_MAX_K 1024
+int gpx_acq_mes(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                const double* alpha, const gpx_mat* Z, const double* ystar, int64_t K, int sign, double* cost, int64_t* best,
+                double* best_cost);
+int gpx_acq_mes_grad(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                     const double* alpha, const gpx_mat* Z, const double* ystar, int64_t K, int sign, double* cost, double* grad);
+int gpx_acq_mes_batch(gpx_ctx* ctx, int kind, int d, const double* hyp, int nhyp, const gpx_mat* L, const gpx_mat* X,
+                      const double* alpha, const gpx_mat* C, double noise, const double* ystar, int64_t K, int sign, int lie,
+                      double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie, double* all_costs);
+
 /* ---- joint posterior samples, Thompson picks and Monte-Carlo q-EI -------------------------------------------------------------
  * The reference draws functions from the PRIOR (GP.generateSamples, gp.py:343-371: an SVD and numpy.random inside); these draw
  * from the posterior at the M points of Z JOINTLY, pick per draw, and score whole q-batches.  Two rules:
@@ -556,6 +586,16 @@ int gpx_vfe_acq_grad(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const do
 int gpx_vfe_acq_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* C, int acq, double param,
                       int track_best, int lie, double lie_value, int64_t q, int64_t* out_idx, double* out_cost, double* out_lie,
                       double* all_costs);
+/* gpx_acq_mes / gpx_acq_mes_grad / gpx_acq_mes_batch on a VFE model: the sequences of the three calls above with the MES cost on
+ * ystar (host, K doubles) and sign; rules, outputs and errors as theirs (a FITC model is refused; gradients for the stationary
+ * kernels only; the costs of the gradient call and row 0 of all_costs hold gpx_vfe_acq_mes's bits). */
+int gpx_vfe_acq_mes(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, const double* ystar,
+                    int64_t K, int sign, double* cost, int64_t* best, double* best_cost);
+int gpx_vfe_acq_mes_grad(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* Z, const double* ystar,
+                         int64_t K, int sign, double* cost, double* grad);
+int gpx_vfe_acq_mes_batch(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, const double* coeff, const gpx_mat* C,
+                          const double* ystar, int64_t K, int sign, int lie, double lie_value, int64_t q, int64_t* out_idx,
+                          double* out_cost, double* out_lie, double* all_costs);
 
 /* ---- posterior sampling on a VFE model --------------------------------------------------------------------------------------------
  * The two samplers above for the model gpx_vfe_fit built; the kernel parameters are the model's, S its inducing points, coeff =

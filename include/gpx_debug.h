@@ -110,6 +110,11 @@ int gpx_dbg_vfe_qei_blocks(gpx_ctx* ctx, const gpx_fitc* f, const gpx_mat* S, co
 int gpx_dbg_acq_epilogue(gpx_ctx* ctx, int acq, double param, const double* mean, const double* var, int64_t m, int64_t chunk,
                          double* cost, double* coef /* 2m, nullable */, int64_t* best, double* best_cost);
 
+/* Its twin for gpx_acq_mes / gpx_vfe_acq_mes: the MES epilogue on ystar (host, K doubles) and sign, and the arg-min, by their own
+   launches on host vectors, with the same sentinel bands.  tests/test_gpu_acq_mes.py. */
+int gpx_dbg_acq_mes_epilogue(gpx_ctx* ctx, const double* ystar, int64_t K, int sign, const double* mean, const double* var, int64_t m,
+                             int64_t chunk, double* cost, double* coef /* 2m, nullable */, int64_t* best, double* best_cost);
+
 #ifdef __cplusplus
 }
 #endif

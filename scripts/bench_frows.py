@@ -417,6 +417,24 @@ if want("acq"):
            note="two passes (costs to the host, then the arg-min alone); each one is N^2 M (the forward solve)")
     _, t1 = best(lambda: cf.bestCandidate(Za))
     report("gpx_acq (bestCandidate only)", "costFuncEI.evaluate", size, t1, flops=1.0 * Na * Na * Ma)
+    # max-value entropy search on the same model and candidates, K = 16 sampled optima below min y, beside the EI call above
+    import copy
+    from gpExp.experimentalDesign import costFuncMES
+    cfm = costFuncMES(cf.gaussianProcess, Xa, ya, 2, _Space(), yStar=float(np.min(ya)) - 0.05 * np.arange(16))
+    cfm.bestCandidate(Za)
+    cfm1 = copy.copy(cfm)                   # the same model with K = 1: the difference is 15 more samples in the epilogue alone
+    cfm1.yStar = cfm.yStar[:1]
+    ts_ei, ts_mes, ts_mes1 = [], [], []
+    for _ in range(3):                      # alternated, so that all see the same clocks
+        ts_ei.append(best(lambda: cf.bestCandidate(Za), reps=1)[1])
+        ts_mes.append(best(lambda: cfm.bestCandidate(Za), reps=1)[1])
+        ts_mes1.append(best(lambda: cfm1.bestCandidate(Za), reps=1)[1])
+    report("gpx_acq_mes (bestCandidate only, K = 16)", "none in the reference (no entropy search there)", dict(size, acq="MES", K=16),
+           min(ts_mes), flops=1.0 * Na * Na * Ma,
+           note="the posterior pass of gpx_acq with the MES epilogue (per candidate K short loops: a 73-term continued fraction "
+                "below gamma = -2 sqrt 2, else erfc / exp / log); ratio to gpx_acq (EI) alternated in this process: %.3f "
+                "(EI %.2f ms; K = 1: %.2f ms, so the 15 further samples of the epilogue cost %.3f ms over M candidates)"
+                % (min(ts_mes) / min(ts_ei), 1e3 * min(ts_ei), 1e3 * min(ts_mes1), 1e3 * (min(ts_mes) - min(ts_mes1))))
     _, t = best(lambda: cf.derivativeBatch(Za))
     report("gpx_acq_grad (derivativeBatch)", "none in the reference (BO costs have no gradient there)", size, t,
            flops=2.0 * Na * Na * Ma + 6.0 * Na * Ma * 8,
